@@ -28,6 +28,8 @@ Further legs in the same line (N = 1 or max over ranks, same barriers):
                     kernel DPVecEnv(packed=None) picks — what a caller gets that consumes every step's outputs (the drop-in for VecEnv.step);
   `horizon_launch`  the window rounded up to whole 256-step horizons through `dm_batch_rollout` (T steps per call).
 `--step-queue 0` times one launch set per `dm_batch_step` call (rounds 1-3's `value`); `--horizon-launch` makes the rollout call the timed leg.
+`--dump-outputs DIR` writes the last timed step's obs / reward / done (rank 0's shard) as DIR/<name>.npy: the same arguments give the same inputs, so
+two builds of the library can be compared output for output.
 
 Besides the contract fields the line carries (N = 1): `roofline` (HBM fraction from the algorithmic bytes per launch and the launch's duration by HIP
 events the library records around it; fp64 fraction from a flop count of the kernel's algorithm on the run's own row / sweep statistics; with
@@ -468,6 +470,8 @@ def main():
                     help="take the multi-rank code path with however many ranks there are, ONE included: process group (RCCL with --dist-backend nccl), "
                          "double-buffered device all-gather of the rollout block every 256 steps, max-reduced timing, the learner's all-mean on a gradient-sized vector")
     ap.add_argument("--alloc-gather-world", type=int, default=0, help="with --force-dist: also allocate (and touch) the two G-way gathered rollout buffers a G-rank job holds per rank")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed windows, write what the timed path returned for its last step (rank 0's shard: obs, reward, done) as DIR/<name>.npy")
     ap.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)   # profiled child of pmc_passes: GPU loop only, prints nothing
     args = ap.parse_args()
 
@@ -525,6 +529,8 @@ def main():
                                 world * HORIZON * n_log * 87 * 4 / 1e6))
             sys.stderr.flush()
 
+    if args.dump_outputs and args.workload in ("rollout", "standing"):
+        raise SystemExit("--dump-outputs covers the step workloads (cfg2 .. cfg5), not --workload %s" % args.workload)
     if args.workload == "rollout":
         return rollout_bench(args, dev, rank, world, local_dev)
     if args.workload == "standing":
@@ -647,6 +653,13 @@ def main():
 
         reps = 1 if args._child else max(1, args.repeats)
         windows = [timed_window(lambda: run_steps(0, args.steps)) for _ in range(reps)]
+        dumped = None
+        if args.dump_outputs and not args._child:
+            # the last timed step's outputs, as the caller of the timed path holds them (row t % HORIZON of the staging buffers), copied before the
+            # untimed legs below reuse those rows.  Inputs are fixed by the arguments (seeded actions, seeded resets), so runs compare output for output
+            k = (args.steps - 1) % HORIZON
+            dumped = {"obs": obs_T[k].to(torch.float64).cpu().numpy(), "reward": rew_T[k].to(torch.float64).cpu().numpy(),
+                      "done": done_T[k].to(torch.float32).cpu().numpy()}
         host_issue_us = float(np.median(issue_s[:reps])) / args.steps * 1e6
         # per-launch duration of the step kernel by HIP events on the stream it is launched on (pipelined: sub-batch 0's launch on
         # its own stream, while the other sub-batches keep the machine busy): untimed, sampled after the clock stopped
@@ -885,6 +898,10 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(clip, args.reward if full else "alive")
             except Exception as e:  # the baseline must never take the GPU number down with it
                 out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": os.cpu_count(), "kind": "port", "sample": "failed: %r" % (e,)}
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         print(json.dumps(out))
     if dist_on:
         dist.barrier()

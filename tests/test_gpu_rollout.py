@@ -206,12 +206,16 @@ def test_bench_rccl_code_path_runs_at_world_size_one():
 
 @pytest.mark.gpu
 def test_bench_eight_ranks_share_the_gpu_over_gloo():
-    """World size 8 — the driver's largest scaling point — on the ONE visible GPU: shard offsets 0 .. 7 N, eight-way gathered rollout
+    """World size 8 — the driver's largest scaling point: shard offsets 0 .. 7 N, eight-way gathered rollout
     blocks (DoubleBufferedGather, host-staged over gloo), MAX-reduced timing, exactly one JSON line from rank 0.  BASELINE.json
-    configs[4]'s clip and reset mode at a reduced shard size (eight processes share one device)."""
+    configs[4]'s clip and reset mode at a reduced shard size.  On one GPU, the eight ranks plus this process would hold the device from nine
+    processes at once, more than a shared GPU should carry: the test needs eight visible GPUs, one rank per device (LOCAL_RANK modulo the devices)."""
     import json
     import subprocess
     import sys
+    ndev = torch.cuda.device_count()
+    if ndev < 8:
+        pytest.skip("needs 8 GPUs (one rank per device), found %d" % ndev)
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", "29543",
            os.path.join(root, "bench.py"), "--gpus", "8", "--dist-backend", "gloo", "--workload", "cfg5", "--envs", "256", "--steps", "300",
@@ -225,12 +229,13 @@ def test_bench_eight_ranks_share_the_gpu_over_gloo():
     assert j["config"]["global_envs"] == 8 * 256 and j["config"]["gathers_completed"] >= 1 and j["scaling"] == "weak"
     assert j["config"]["clip"] == "dance_b" and j["value"] > 1e4 and "cpu_baseline" not in j
     assert "rollout gather" in out.stderr, "the multi-rank start-up line (rank count, gather size) is missing"
-    # what a SCALE record is read for (round 6): every rank reported its device over the process group, all eight sit on the one GPU of this box, and
-    # both blocks of the double buffer travelled (300 steps = one whole 256-step horizon + a started one)
+    # what a SCALE record is read for (round 6): every rank reported its device over the process group, the eight sit on min(8, visible) distinct GPUs,
+    # and both blocks of the double buffer travelled (300 steps = one whole 256-step horizon + a started one)
     c = j["config"]
-    assert len(c["rank_devices"]) == 8 and len(set(d.rsplit(".", 1)[0] for d in c["rank_devices"])) == 1
-    assert c["distinct_gpus"] == 1, "eight ranks on one visible device: %r" % (c["distinct_gpus"],)
-    assert "1 distinct GPU(s) for 8 rank(s)" in out.stderr
+    want = min(8, ndev)
+    assert len(c["rank_devices"]) == 8 and len(set(d.rsplit(".", 1)[0] for d in c["rank_devices"])) == want
+    assert c["distinct_gpus"] == want, "eight ranks on %d visible devices: %r" % (ndev, c["distinct_gpus"])
+    assert "%d distinct GPU(s) for 8 rank(s)" % want in out.stderr
     assert c["gathers_completed"] >= 1 and c["envs_per_gpu"] == 256
 
 

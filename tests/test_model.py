@@ -9,7 +9,8 @@ from deepmimic_mujoco_amd.mjcf import load_mjcf, to_mjcf
 from deepmimic_mujoco_amd.model import CompiledModel
 from tests import helpers as H
 
-REF_XML = "/root/reference/src/mujoco/humanoid_deepmimic/envs/asset/dp_env_v3.xml"
+# the reference's model file (src/mujoco/humanoid_deepmimic/envs/asset/dp_env_v3.xml), kept verbatim as a data fixture
+REF_XML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dp_env_v3.xml")
 
 
 def _same(a, b, path=""):
@@ -66,7 +67,6 @@ def test_mjcf_roundtrip_and_rejects_unsupported():
         load_mjcf('<mujoco><worldbody/><equality/></mujoco>')
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference checkout not present")
 def test_builtin_table_equals_reference_xml():
     _same(humanoid_spec(), load_mjcf(REF_XML))
 
