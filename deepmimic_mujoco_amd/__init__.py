@@ -11,6 +11,7 @@ Host side is pure Python over the C ABI of libdmenv.so (include/dmenv.h, HIP ker
     load_checkpoint   reader for the reference's tf.train.Saver bundles
     trpo.learn / TrpoLearner   the reference's TRPO learner on torch autograd + RCCL all-mean (src/trpo.py:97-319)
     logio             progress.csv / monitor.csv readers and writers
+    gail              the reference's GAIL learner: TransitionClassifier (the discriminator on the device), ExpertDataset, learn (src/gail.py)
 """
 from .config import Config  # noqa: F401
 from .mocap import MocapDM  # noqa: F401

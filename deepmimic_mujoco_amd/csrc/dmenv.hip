@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "vf_kernel.h"
 #include "pg_kernel.h"
+#include "disc_kernel.h"
 #include "model_host.h"
 
 using namespace dm;
@@ -979,6 +980,43 @@ extern "C" int dm_pg_fvp(const float* ob, int32_t stride, int32_t n, const float
                      (float*)nullptr, (const float*)nullptr, 0, theta, v, rms_mean, rms_std, 1.0f / (float)n, partial, lpart);
   hipLaunchKernelGGL(dmg::k_pg_reduce, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, (const float*)partial, (const double*)lpart, nblk, (int)dmg::MODE_FVP,
                      0.0f, v, 1.0 / (double)n, out_fv, (double*)nullptr);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
+// ---- the GAIL discriminator (csrc/disc_kernel.h) --------------------------------------------------------------------------------
+static bool have_device() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; } return n > 0; }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static int disc_blocks(int n) { return (n + dmd::SB - 1) / dmd::SB; }
+extern "C" int dm_disc_param_count(void) { return dmd::NP; }
+extern "C" size_t dm_disc_scratch_bytes(int32_t n_g, int32_t n_e) {
+  if (n_g < 1 || n_e < 1) return 0;
+  return (size_t)(disc_blocks(n_g) + disc_blocks(n_e)) * dmd::NPAD * sizeof(float);
+}
+extern "C" int dm_disc_reward(const float* theta, const float* rms_mean, const float* rms_std, const double* ob, const double* ac, int32_t n, double* reward,
+                              void* hip_stream) {
+  if (!theta || !rms_mean || !rms_std || !ob || !ac || !reward || n < 1 || !aligned16(theta)) return fail(DM_EINVAL, "dm_disc_reward: bad argument");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_disc_reward: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_disc_reward: hipSetDevice failed");
+  hipLaunchKernelGGL(dmd::k_disc_reward, dim3(disc_blocks(n)), dim3(256), 0, (hipStream_t)hip_stream, ob, ac, (int)n, theta, rms_mean, rms_std, reward);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
+extern "C" int dm_disc_lossgrad(const float* theta, const float* rms_mean, const float* rms_std, const float* g_ob, const float* g_ac, int32_t n_g,
+                                const float* e_ob, const float* e_ac, int32_t n_e, double entcoeff, float* out_grad, double* out_losses, void* scratch,
+                                size_t scratch_bytes, void* hip_stream) {
+  if (!theta || !rms_mean || !rms_std || !g_ob || !g_ac || !e_ob || !e_ac || !out_grad || !out_losses || !scratch || n_g < 1 || n_e < 1 || !aligned16(theta) ||
+      !(entcoeff == entcoeff) || (int64_t)disc_blocks(n_g) + disc_blocks(n_e) > INT32_MAX / dmd::NPAD)
+    return fail(DM_EINVAL, "dm_disc_lossgrad: bad argument");
+  if (scratch_bytes < dm_disc_scratch_bytes(n_g, n_e)) return fail(DM_EINVAL, "dm_disc_lossgrad: scratch smaller than dm_disc_scratch_bytes(n_g, n_e)");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_disc_lossgrad: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_disc_lossgrad: hipSetDevice failed");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int nbg = disc_blocks(n_g), nblk = nbg + disc_blocks(n_e);
+  float* partial = (float*)scratch;
+  hipLaunchKernelGGL(dmd::k_disc_grad, dim3(nblk), dim3(256), 0, st, g_ob, g_ac, (int)n_g, e_ob, e_ac, (int)n_e, nbg, theta, rms_mean, rms_std,
+                     (float)entcoeff, partial);
+  hipLaunchKernelGGL(dmd::k_disc_reduce, dim3(dmd::RED_BLOCKS + 1), dim3(256), 0, st, (const float*)partial, nblk, nbg,
+                     (int)n_g, (int)n_e, (float)entcoeff, out_grad, out_losses);
   HIPCHK(hipGetLastError());
   return DM_OK;
 }

@@ -99,13 +99,13 @@ def can_fuse(pi, env, device=None):
 class _PendingEpisodes:
     """Episode statistics of a segment whose records are still on their way to the host (SegmentCollector._episodes_native)."""
 
-    def __init__(self, collector, event):
-        self.c, self.event, self.out = collector, event, None
+    def __init__(self, collector, event, slot="_ep"):
+        self.c, self.event, self.out, self.slot = collector, event, None, slot       # slot: which of the collector's record buffers
 
     def result(self):
         if self.out is None:
             import numpy as np
-            cnt, rec, h_cnt, h_rec = self.c._ep_buf
+            cnt, rec, h_cnt, h_rec = getattr(self.c, self.slot + "_buf")
             self.event.synchronize()
             k = min(int(h_cnt[0]), rec.shape[0])
             r = h_rec[:min(k, h_rec.shape[0])].numpy()
@@ -113,8 +113,8 @@ class _PendingEpisodes:
                 r = np.concatenate([r, rec[h_rec.shape[0]:k].cpu().numpy()], 0)
             order = np.argsort(r[:, 0], kind="stable")                     # word 0 = t << 32 | env: time-major, then env
             self.out = (r[order, 1].copy().view(np.float64).tolist(), r[order, 2].tolist())
-            if self.c._ep_pending is self:
-                self.c._ep_pending = None
+            if getattr(self.c, self.slot + "_pending") is self:
+                setattr(self.c, self.slot + "_pending", None)
         return self.out
 
 
@@ -123,6 +123,7 @@ class Segment(dict):
     (`finish_episode_stats()` does it explicitly — the learner calls it where the host would otherwise wait for the device)."""
 
     pending_episodes = None
+    pending_true = None                  # with a reward_giver: the env's own returns ("ep_true_rets"), also on their way to the host
     info = None                          # how the segment was produced (launch form, overflow rate of the packed path): diagnostics, not data
 
     def finish_episode_stats(self):
@@ -130,15 +131,23 @@ class Segment(dict):
             rets, lens = self.pending_episodes.result()
             self.pending_episodes = None
             dict.__setitem__(self, "ep_rets", rets); dict.__setitem__(self, "ep_lens", lens)
+        if self.pending_true is not None:
+            rets, _ = self.pending_true.result()
+            self.pending_true = None
+            dict.__setitem__(self, "ep_true_rets", rets)
+
+    def _pending(self, key):
+        return ((key in ("ep_rets", "ep_lens") and self.pending_episodes is not None)
+                or (key == "ep_true_rets" and self.pending_true is not None))
 
     def __missing__(self, key):
-        if key in ("ep_rets", "ep_lens") and self.pending_episodes is not None:
+        if self._pending(key):
             self.finish_episode_stats()
             return dict.__getitem__(self, key)
         raise KeyError(key)
 
     def __contains__(self, key):
-        return dict.__contains__(self, key) or (key in ("ep_rets", "ep_lens") and self.pending_episodes is not None)
+        return dict.__contains__(self, key) or self._pending(key)
 
     # whoever walks the dict sees all of it
     def __iter__(self):
@@ -163,9 +172,14 @@ class Segment(dict):
 class SegmentCollector(object):
     """One env batch's side of `traj_segment_generator`, split into `launch()` (enqueue T policy + env steps, no host wait) and
     `collect()` (episode bookkeeping, the one host transfer per segment) so that several env batches can be in flight at once.
-    With `stream` (a torch CUDA stream) everything this collector enqueues runs on that stream."""
+    With `stream` (a torch CUDA stream) everything this collector enqueues runs on that stream.
 
-    def __init__(self, pi, env, horizon, stochastic=True, device=None, first_reset="rsi", stream=None, fused=False):
+    With `reward_giver` (gail.TransitionClassifier: src/gail.py:27's generator) the segment's rewards are D's: one `reward_into` call
+    (dm_disc_reward, one launch) per segment after the horizon fills a second [T, N] float64 buffer from the segment's (ob, ac) — D is
+    fixed for the whole segment, so this is the reference's per-step `reward_giver.get_reward(ob, ac)` (:78).  seg["rew"] and
+    "ep_rets" then come from it, "ep_true_rets" from the env's reward through a second episode scan with its own carry (:85-91)."""
+
+    def __init__(self, pi, env, horizon, stochastic=True, device=None, first_reset="rsi", stream=None, fused=False, reward_giver=None):
         import torch
         self.pi, self.env, self.T, self.stochastic, self.stream = pi, env, int(horizon), stochastic, stream
         n, T = env.num_envs, self.T
@@ -182,6 +196,11 @@ class SegmentCollector(object):
         self.last_ac = torch.zeros((n, 28), dtype=f32, device=device)              # prevac of row 0 (trpo.py:29 samples a random one)
         self.cur_ret = torch.zeros(n, dtype=f64, device=device)                    # running return / length of the open episodes
         self.cur_len = torch.zeros(n, dtype=torch.int64, device=device)
+        self.reward_giver = reward_giver
+        if reward_giver is not None:
+            self.drew64 = torch.zeros((T, n), dtype=f64, device=device)            # D's reward of every (ob, ac) of the segment
+            self.cur_true_ret = torch.zeros(n, dtype=f64, device=device)           # the env's return of the open episodes
+            self.cur_true_len = torch.zeros(n, dtype=torch.int64, device=device)
         self.as_buf = (lambda x: x) if device.type == "cuda" else (lambda x: x.numpy())   # host tensors: shared-memory views
         self.step_idx = torch.arange(1, T + 1, device=device, dtype=torch.int64)[:, None]
         # fused path: the env step kernel also runs the policy on the observation it produced (dm_batch_step_act), one launch per step.
@@ -309,6 +328,11 @@ class SegmentCollector(object):
         if prof:
             torch.cuda.synchronize(device); t_c = time.perf_counter()
         ob64, ac64, rew64, done8, vpreds = self.ob64, self.ac64, self.rew64, self.done8, self.vpreds
+        true64 = None
+        if self.reward_giver is not None:
+            with torch.no_grad():
+                self.reward_giver.reward_into(ob64[:T], ac64[:T], self.drew64)        # gail.py:78, the whole segment at once
+            true64, rew64 = rew64, self.drew64
         done = done8.to(torch.bool)
         new = torch.cat([self.first[None], done8[:-1].to(torch.int32)], 0)
         acs = ac64[:T].to(f32)
@@ -320,8 +344,12 @@ class SegmentCollector(object):
         seg.info = {"packed": self._packed_now, "kernel_switches": self.kernel_switches, "redo_rate": getattr(self, "_last_redo_rate", None)}
         if native_eps:
             seg.pending_episodes = self._episodes_native(rew64, done8)
+            if true64 is not None:
+                seg.pending_true = self._episodes_native(true64, done8, true=True)
         else:
             seg["ep_rets"], seg["ep_lens"] = self._episodes_torch(rew64, done, T, n, device)
+            if true64 is not None:
+                seg["ep_true_rets"] = self._episodes_torch(true64, done, T, n, device, true=True)[0]
         seg.update({"ob": ob64[:T].to(f32), "rew": rew64.to(f32), "vpred": vpreds[:T].clone(), "new": new, "ac": acs, "prevac": prevacs,
                     "nextvpred": vpreds[T] * (1 - done8[-1].to(f32))})
         self.first = done8[-1].to(torch.int32)
@@ -338,7 +366,7 @@ class SegmentCollector(object):
 
     EP_HEAD = 16384                      # episode records fetched with the count in one asynchronous copy (more than that: a second copy)
 
-    def _episodes_native(self, rew64, done8):
+    def _episodes_native(self, rew64, done8, true=False):
         """One launch (dm_episode_scan: thread = env walks its column of the segment) and a host sort of the few episodes that ended, instead
         of ~100 launch-bound tensor ops.  Returns are float64 sums in step order, like the reference's `cur_ep_ret += rew`.  Nothing waits
         here: the records travel to pinned memory behind the kernel, and `_PendingEpisodes.result()` sorts them when somebody asks — the
@@ -347,31 +375,34 @@ class SegmentCollector(object):
         import torch
         from . import _abi as A
         T, n, dev = self.T, self.n, self.device
-        if getattr(self, "_ep_buf", None) is None:
+        slot = "_ept" if true else "_ep"                                   # true: the env's returns beside D's (reward_giver), own buffers / carry
+        cur_ret, cur_len = (self.cur_true_ret, self.cur_true_len) if true else (self.cur_ret, self.cur_len)
+        if getattr(self, slot + "_buf", None) is None:
             cap = T * n
             head = min(cap, self.EP_HEAD)
-            self._ep_buf = (torch.zeros(1, dtype=torch.int32, device=dev), torch.empty((cap, 3), dtype=torch.int64, device=dev),
-                            torch.zeros(1, dtype=torch.int32).pin_memory(), torch.empty((head, 3), dtype=torch.int64).pin_memory())
-            self._ep_pending = None
-        if self._ep_pending is not None:
-            self._ep_pending.result()                                      # (its pinned buffers are about to be overwritten)
-        cnt, rec, h_cnt, h_rec = self._ep_buf
+            setattr(self, slot + "_buf", (torch.zeros(1, dtype=torch.int32, device=dev), torch.empty((cap, 3), dtype=torch.int64, device=dev),
+                                          torch.zeros(1, dtype=torch.int32).pin_memory(), torch.empty((head, 3), dtype=torch.int64).pin_memory()))
+            setattr(self, slot + "_pending", None)
+        if getattr(self, slot + "_pending") is not None:
+            getattr(self, slot + "_pending").result()                     # (its pinned buffers are about to be overwritten)
+        cnt, rec, h_cnt, h_rec = getattr(self, slot + "_buf")
         p = lambda x: C.c_void_p(x.data_ptr())
         L = A.load()
-        A.check(L.dm_episode_scan(p(rew64), p(done8), T, n, p(self.cur_ret), p(self.cur_len), p(cnt), rec.shape[0], p(rec),
+        A.check(L.dm_episode_scan(p(rew64), p(done8), T, n, p(cur_ret), p(cur_len), p(cnt), rec.shape[0], p(rec),
                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), L)
         h_cnt.copy_(cnt, non_blocking=True)
         h_rec.copy_(rec[:h_rec.shape[0]], non_blocking=True)
         ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(dev))
-        self._ep_pending = _PendingEpisodes(self, ev)
-        return self._ep_pending
+        pending = _PendingEpisodes(self, ev, slot)
+        setattr(self, slot + "_pending", pending)
+        return pending
 
-    def _episodes_torch(self, rew64, done, T, n, device):
+    def _episodes_torch(self, rew64, done, T, n, device, true=False):
         import torch
         csum = torch.cumsum(rew64, 0)
         ends = done.nonzero()                                              # [K, 2] (t, env), sorted by t then env
         ep_rets, ep_lens = [], []
-        cur_ret, cur_len = self.cur_ret, self.cur_len
+        cur_ret, cur_len = (self.cur_true_ret, self.cur_true_len) if true else (self.cur_ret, self.cur_len)
         if ends.numel():
             te, ee = ends[:, 0], ends[:, 1]
             # previous end of the same env inside the segment (or -1): sort by (env, t) and shift
@@ -390,12 +421,16 @@ class SegmentCollector(object):
         # carry the open episodes into the next segment
         last_end = torch.where(done, self.step_idx.expand(T, n), torch.zeros((T, n), dtype=torch.int64, device=device)).amax(0)   # 1-based
         tail_ret = csum[-1] - torch.where(last_end > 0, csum[(last_end - 1).clamp(min=0), torch.arange(n, device=device)], torch.zeros_like(csum[-1]))
-        self.cur_ret = torch.where(last_end > 0, tail_ret, cur_ret + tail_ret)
-        self.cur_len = torch.where(last_end > 0, T - last_end, cur_len + T)
+        new_ret = torch.where(last_end > 0, tail_ret, cur_ret + tail_ret)
+        new_len = torch.where(last_end > 0, T - last_end, cur_len + T)
+        if true:
+            self.cur_true_ret, self.cur_true_len = new_ret, new_len
+        else:
+            self.cur_ret, self.cur_len = new_ret, new_len
         return ep_rets, ep_lens
 
 
-def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False):
+def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None):
     """Batched `traj_segment_generator` (src/trpo.py:27-80): N envs advance in lock step on the device.
 
     pi: policy.MlpPolicy; env: DPVecEnv created with autoreset="init" — the kernel then applies, on `done`, exactly what
@@ -410,8 +445,11 @@ def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first
     (see `can_fuse`) even the policy forward is gone: the env step kernel runs it on the observation it has just produced
     (`dm_batch_step_act`), a step is ONE launch, and with `DM_OPT_PIPELINE` on the batch consecutive steps overlap.  The float32
     segment views, `new`, `prevac` and the episode statistics are derived once per segment with [T, N]-wide ops.
-    Nothing leaves the device or the stream."""
-    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused)
+    Nothing leaves the device or the stream.
+
+    reward_giver (src/gail.py:27-92): the rewards are the discriminator's (see SegmentCollector); the segment also carries
+    "ep_true_rets", the env's returns of the same episodes."""
+    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver)
     while True:
         c.launch()
         yield c.collect()

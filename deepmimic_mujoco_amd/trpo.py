@@ -26,6 +26,7 @@ import os
 import time
 from collections import deque
 
+import numpy as np
 import torch
 
 from .rollout import add_vtarg_and_adv, flatten_segment, traj_segment_generator, pipelined_segment_generator
@@ -763,11 +764,14 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
     return history
 
 
-def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print):
+def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print, save_sample=None):
     """`runner()` + `traj_1_generator()` of src/trpo.py:356-436 (`--task evaluate`), one trajectory per env of the batch at once: from
     `env.reset(); env.reset_model_init()` each env runs `pi.act(stochastic, ob)` -> `env.step(ac)` until its first `done` or until
     `timesteps_per_batch + 1` steps.  Returns (average length, average return) as the reference prints them, plus the per-trajectory
-    arrays.  `pi` comes from `MlpPolicy.from_tf_checkpoint(path)` (= U.load_state) or `from_npz`."""
+    arrays.  `pi` comes from `MlpPolicy.from_tf_checkpoint(path)` (= U.load_state) or `from_npz`.
+    save_sample: a path — the trajectories are also written there as `--save_sample` does (:385-388): obs / acs (N, L, ...) when every
+    trajectory has the same length, else object arrays of N (L_i, ...) arrays, lens, rets; and the same returns as `ep_rets`, the key the
+    GAIL expert reader (src/utils/mujoco_dset.py) reads.  gail.ExpertDataset accepts the file."""
     n = env.num_envs
     dev = pi.device
     with torch.no_grad():
@@ -775,8 +779,11 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
         env.reset("init", out=ob if ob.is_cuda else ob.numpy())
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         ep_len = torch.zeros(n, dtype=torch.int64, device=dev); ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
+        obs_hist, acs_hist = [], []
         for t in range(int(timesteps_per_batch) + 1):
             ac, _ = pi.act(stochastic_policy, ob)
+            if save_sample:
+                obs_hist.append(ob.clone()); acs_hist.append(torch.as_tensor(ac, device=dev).to(torch.float32).clone())
             res = env.step(ac if ac.is_cuda else ac.numpy())
             ob = torch.as_tensor(res[0], dtype=torch.float64, device=dev)
             rew = torch.as_tensor(res[1], dtype=torch.float64, device=dev); done = torch.as_tensor(res[2], device=dev).to(torch.bool)
@@ -785,6 +792,15 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
             if not bool(alive.any()):
                 break
     lens, rets = ep_len.cpu().numpy(), ep_ret.cpu().numpy()
+    if save_sample:
+        obs_all = torch.stack(obs_hist, 1).cpu().numpy(); acs_all = torch.stack(acs_hist, 1).cpu().numpy()     # [n, steps, ...]
+        if (lens == lens[0]).all():
+            obs_s, acs_s = obs_all[:, :lens[0]], acs_all[:, :lens[0]]
+        else:
+            obs_s = np.empty(n, dtype=object); acs_s = np.empty(n, dtype=object)
+            for e in range(n):
+                obs_s[e] = obs_all[e, :lens[e]]; acs_s[e] = acs_all[e, :lens[e]]
+        np.savez(save_sample, obs=obs_s, acs=acs_s, lens=lens, rets=rets, ep_rets=rets)
     log("stochastic policy:" if stochastic_policy else "deterministic policy:")
     log("Average length: %s" % (lens.sum() / len(lens)))
     log("Average return: %s" % (rets.sum() / len(rets)))

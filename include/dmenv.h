@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 4
+#define DM_ABI_VERSION 5
 
 /* fixed sizes of the DeepMimic humanoid (dp_env_v3.xml:21-156): the kernels are specialised to this tree */
 #define DM_NBODY 14
@@ -324,6 +324,26 @@ int dm_pg_losses(const float* ob, int32_t n, const float* ac, const float* atarg
                  float* out_grad, double* out_losses, void* scratch, void* hip_stream, int32_t max_blocks);
 int dm_pg_fvp(const float* ob, int32_t stride, int32_t n, const float* theta, const float* v, const float* rms_mean, const float* rms_std,
               float* out_fv, void* scratch, void* hip_stream, int32_t max_blocks);
+
+/* The GAIL discriminator (src/adversary.py TransitionClassifier, driven by src/gail.py) on the device, fp32 like the reference:
+ * logit = fc(100->1)(tanh fc(100->100)(tanh fc(84->100)(concat((ob - rms_mean) / rms_std, ac)))), no clip of the normalised observation.
+ * theta: dm_disc_param_count() = 18 701 floats = adversary/fully_connected/{weights,biases}, fully_connected_1/..., fully_connected_2/...
+ * (weights row-major [in][out]), 16-byte aligned; rms_mean / rms_std [56] float32 (the adversary's own obs filter).  Every pointer is a
+ * DEVICE pointer on one device; the work is enqueued on `hip_stream`; no device visible -> DM_ENODEVICE.
+ *   dm_disc_reward    Replaces: reward_giver.get_reward(ob, ac) (src/gail.py:78, once per env step there) for a whole segment in one launch:
+ *                     ob [n, 56], ac [n, 28] float64 (the rollout's buffers), reward [n] float64 = -log(1 - sigmoid(logit) + 1e-8) in fp32.
+ *   dm_disc_lossgrad  Replaces: reward_giver.lossandgrad(ob, ac, ob_expert, ac_expert) (src/gail.py:336): generator rows g_ob [n_g, 56] /
+ *                     g_ac [n_g, 28] and expert rows e_ob [n_e, 56] / e_ac [n_e, 28], float32.  out_grad [18 701] float32 = flat gradient of
+ *                     mean_g CE(x, 0) + mean_e CE(x, 1) - entcoeff * mean H(x); out_losses [6] float64 = generator_loss, expert_loss, entropy,
+ *                     entropy_loss, generator_acc, expert_acc.  scratch: dm_disc_scratch_bytes(n_g, n_e) bytes.  Sums are taken in a fixed
+ *                     order: two calls with the same inputs give bitwise-identical results. */
+int dm_disc_param_count(void);
+size_t dm_disc_scratch_bytes(int32_t n_g, int32_t n_e);
+int dm_disc_reward(const float* theta, const float* rms_mean, const float* rms_std, const double* ob, const double* ac, int32_t n, double* reward,
+                   void* hip_stream);
+int dm_disc_lossgrad(const float* theta, const float* rms_mean, const float* rms_std, const float* g_ob, const float* g_ac, int32_t n_g,
+                     const float* e_ob, const float* e_ac, int32_t n_e, double entcoeff, float* out_grad, double* out_losses, void* scratch,
+                     size_t scratch_bytes, void* hip_stream);
 
 /* Diagnostics of DM_OPT_PACKED (four environments per wavefront, csrc/slot_kernel.h): env-steps so far that exceeded a capacity of that
  * path (DM_PACKED_*: rows, contacts / contact pairs, pairs past the bounding spheres, box staging slots; or a PGS step the cost test would

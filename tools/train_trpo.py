@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--load-model-path", default=None, help="evaluate: a tf.train.Saver checkpoint prefix (the reference's or one written by --save) or an .npz")
     ap.add_argument("--number-trajs", type=int, default=10, help="evaluate: trajectories (one env each; src/trpo.py:483)")
     ap.add_argument("--stochastic-policy", action="store_true")
+    ap.add_argument("--save-sample", default=None, help="evaluate: also write the trajectories to this .npz (obs, acs, lens, rets and ep_rets: "
+                                                        "the reference's `--save_sample` file, readable by its GAIL expert reader and tools/train_gail.py)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--log-dir", default=None, help="write progress.csv and monitor.csv in the reference's formats")
@@ -67,7 +69,7 @@ def main():
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
         env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, autoreset="init", seed=args.seed, frame_skip=fs)
-        runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy)
+        runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=args.save_sample)
         return
     P = max(1, args.pipeline)
     if args.unfused:
