@@ -14,34 +14,28 @@
 // A block owns a fixed set of 32-sample tiles (tile t -> block t mod gridDim.x) and keeps its weight-gradient tiles in REGISTERS across all of
 // them; partial gradients are written once per block and summed in block order by k_pg_reduce: results do not depend on timing.
 //
-// Every product runs on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32; the 28-wide output layer as 16x16x4 tiles), operands straight from
-// LDS with no re-layout between layers:
-//   * activations sit transposed, [unit][sample] with a row stride of 33 floats: a row pair [k, k+1][32 samples] is a B operand (forward,
-//     "units x samples" results), a column pair [32 units][s, s+1] is an A or B operand of the weight-gradient products (sum over samples);
-//     both reads are bank-conflict free;
-//   * the parameters are ONE copy of theta in LDS.  theta's order (W1, b1, W2, b2, W3, b3) makes each bias the row after its matrix, so with a
-//     constant row of ones appended to z / h1 / h2 the biases are part of the products, forward AND backward: the bias gradients are row
-//     56 / 100 / 100 of the weight-gradient tiles, which land in theta order by themselves;
-//   * wave w owns output units 32 w .. 32 w + 31 of the hidden layers (100 padded to 128: rows past 99 read finite junk and are never stored);
-//     a Fisher product keeps ITS slices of the direction v in registers for the whole launch (106 per lane) instead of streaming v per tile.
+// The tile layout is mlp_tile.h's (the 28-wide output layer as 16x16x4 tiles; a ones row under h2 as well, for b3): the bias gradients are row
+// 56 / 100 / 100 of the weight-gradient tiles.  A Fisher product keeps ITS slices of the direction v in registers for the whole launch (106 per
+// lane) instead of streaming v per tile.
 // fp32 like the reference's TF graph; loss sums leave the block in float64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mlp_tile.h"
 
 namespace dmg {
+using namespace dml;
 
-constexpr int OB = 56, H = 100, AC = 28, SB = 32, SBP = SB + 1;
+constexpr int OB = 56, AC = 28;
 constexpr int O_W1 = 0, O_B1 = O_W1 + OB * H, O_W2 = O_B1 + H, O_B2 = O_W2 + H * H, O_W3 = O_B2 + H, O_B3 = O_W3 + H * AC, O_LS = O_B3 + AC, NP = O_LS + AC;
 constexpr int NPAD = (NP + 63) / 64 * 64;
 constexpr int NWT = (O_LS + 3) / 4 * 4 + 4;           // theta up to logstd, as float4s (the pad holds the first logstd entries: never used as a weight)
 constexpr int MAX_BLOCKS = 256;                       // one block per CU (LDS-limited)
-constexpr int ZR = OB + 2, HR = H + 4, MR = 32;       // rows: z + {ones, zeros};  h + {ones, 3 x zeros};  action rows padded to a tile
+constexpr int ZR = OB + 2, MR = 32;                   // rows: z + {ones, zeros};  action rows padded to a tile
 enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_FVP = 2 };
 static_assert(O_LS % 4 == 0 && NP >= NWT, "theta is copied to LDS as float4s");
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 struct alignas(16) PgShared {
   float Wt[NWT];                                      // theta: W1 [56][100], b1, W2 [100][100], b2, W3 [100][28], b3
@@ -58,17 +52,7 @@ static_assert(sizeof(PgShared) <= 160 * 1024, "PgShared must fit a CU's LDS");
 // operand reads past a buffer's rows (padded unit tiles) must stay inside the struct: the furthest is W3's row 127 as an A operand
 static_assert(O_W3 + 127 * AC + AC <= NWT + ZR * SBP, "padded W3 rows read into z");
 
-__device__ inline v16f mfma32(float a, float b, v16f c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ inline v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// tanh(x) = sign(x) (1 - t) / (1 + t), t = exp(-2 |x|): the hardware exponential and reciprocal, absolute error ~1e-7 — an ulp of the
-// activation's range, like the float32 graph of the reference.  (The library tanhf is ~60 instructions with two divergent branches: with the
-// products on the matrix cores it was a quarter of a tile's time.)
-__device__ inline float tanh_fast(float x) {
-  const float t = __expf(-2.0f * fabsf(x));
-  return copysignf((1.0f - t) * __frcp_rn(1.0f + t), x);
-}
-// row of a 32x32 result tile held in register r by the lanes of half `hf`
-__device__ inline int row32(int r, int hf) { return 8 * (r / 4) + 4 * hf + (r % 4); }
 
 // ob: [.., 56] f32, sample i at row i * stride.  theta: packed policy parameters (NP).  MODE_LOSS / MODE_GRAD: ac [n, 28], atarg [n],
 // old_logstd [28], old_mean [n, 28] — with write_old != 0 the kernel treats old == new and WRITES old_mean (src/trpo.py:247 assign_old_eq_new).
@@ -352,16 +336,7 @@ __global__ __launch_bounds__(256) void k_pg_reduce(const float* __restrict__ par
   }
   if (p >= NP || mode == MODE_LOSS) return;
   if (mode == MODE_FVP && p >= O_LS) { out[p] = 2.0f * v[p]; return; }
-  float g = 0.0f;
-  int b = 0;
-  for (; b + 8 <= nblk; b += 8) {
-    float x[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) x[u] = partial[(size_t)(b + u) * NPAD + p];
-#pragma unroll
-    for (int u = 0; u < 8; u++) g += x[u];
-  }
-  for (; b < nblk; b++) g += partial[(size_t)b * NPAD + p];
+  float g = column_sum<8>(partial, NPAD, p, 0, nblk);
   if (mode == MODE_GRAD && p >= O_LS) g += entcoeff;
   out[p] = g;
 }

@@ -14,12 +14,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mlp_tile.h"
 
 namespace dmv {
+using namespace dml;
 
-constexpr int OB = 56, H = 100, SB = 32;            // SB: samples per block of k_vf_grad (a 4 096-sample minibatch is 128 blocks: the policy step can have the other CUs)
-constexpr int O_W1 = 0, O_B1 = O_W1 + OB * H, O_W2 = O_B1 + H, O_B2 = O_W2 + H * H, O_W3 = O_B2 + H, O_B3 = O_W3 + H, NP = O_B3 + 1;
-constexpr int NPAD = (NP + 63) / 64 * 64;
+constexpr int OB = 56;                              // k_vf_grad takes SB = 32 samples per block (a 4 096-sample minibatch is 128 blocks: the policy step can have the other CUs)
+using VfShared = MlpShared<OB>;
+constexpr int NP = VfShared::NP, NPAD = VfShared::NPAD;
 constexpr int RMS_BLOCKS = 64;
 
 // ---- obs filter ----------------------------------------------------------------------------------------------------------------
@@ -72,180 +74,43 @@ __global__ __launch_bounds__(256) void k_vf_rms(const float* __restrict__ ob, in
 }
 
 // ---- forward + backward of 32 samples ------------------------------------------------------------------------------------------
-// Every product runs on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32), laid out like the policy kernels (pg_kernel.h): activations
-// transposed in LDS ([unit][sample], row stride 33 floats: conflict-free as the B operand of a layer and as an operand of the weight-gradient
-// products, which sum over the samples), ONE copy of theta in LDS whose order (W1, b1, W2, b2, w3, b3) makes each bias the row after its
-// matrix — a constant row of ones under z / h1 makes the biases part of the products, forward and backward, and the bias gradients rows 56 /
-// 100 of the weight-gradient tiles.  Wave w owns hidden units 32 w .. 32 w + 31 (100 padded to 128: rows past 99 read finite junk and are
-// never stored).  (Rounds 2-3: 4 x 4 / 2 x 4 register tiles of FMAs on 16-sample blocks, 28 us per 4 096-sample minibatch.)
-constexpr int SBP = SB + 1, ZR = OB + 2, HR = H + 4;
-constexpr int NWT = (NP + 3) / 4 * 4;
-typedef float v16f __attribute__((ext_vector_type(16)));
-struct alignas(16) VfShared {
-  float Wt[NWT];                                      // theta: W1 [56][100], b1, W2 [100][100], b2, w3 [100], b3
-  float z[ZR][SBP];                                   // row 56 = 1, row 57 = 0
-  float h1[HR][SBP], h2[HR][SBP];                     // h1: row 100 = 1, row 101 = 0
-  float d2[HR][SBP], d1[HR][SBP];                     // (as operands of the weight-gradient products their 128-row tiles read on into what follows)
-  float vpart[8][SB], dv[SB];
-  float tail[24 * SBP];                               // ... zeros
-};
+// The tile layout of mlp_tile.h, on 128 blocks of a 4 096-sample minibatch.  (Rounds 2-3: 4 x 4 / 2 x 4 register tiles of FMAs on 16-sample
+// blocks, 28 us per 4 096-sample minibatch.)
 static_assert(SB * OB % 256 == 0, "the observation tile is read in whole rounds of the block");
-static_assert(sizeof(VfShared) <= 160 * 1024, "VfShared must fit a CU's LDS");
-static_assert(O_W2 + 127 * H + H <= NWT + (ZR + HR) * SBP, "padded W2 rows (A operand of the backward product) read into z / h1");
-__device__ inline v16f mfma32(float a, float b, v16f c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ inline int row32(int r, int hf) { return 8 * (r / 4) + 4 * hf + (r % 4); }      // row of a 32x32 result tile in register r of the lanes of half hf
-// tanh(x) = sign(x) (1 - t) / (1 + t), t = exp(-2 |x|), on the hardware exponential / reciprocal (absolute error ~1e-7; pg_kernel.h)
-__device__ inline float fast_tanh(float x) {
-  const float t = __expf(-2.0f * fabsf(x));
-  return copysignf((1.0f - t) * __frcp_rn(1.0f + t), x);
-}
 
 // forward + backward of samples s0 .. s0 + SB - 1 of the minibatch; the tile's partial gradient goes to `out` (NPAD floats, theta order)
 __global__ __launch_bounds__(256) void k_vf_grad(const float* __restrict__ ob, const float* __restrict__ ret, int bs, const float* __restrict__ theta,
                                                  const float* __restrict__ mean, const float* __restrict__ stdv, float* __restrict__ partial) {
   __shared__ VfShared S;                                      // 126 KB: one block per CU
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 31, hf = l >> 5, u0 = 32 * w;
-  const int s0 = blockIdx.x * SB;
-  float* out = partial + (size_t)blockIdx.x * NPAD;
-  {
-    // One round trip for everything the block reads: the tile's observations (with the filter's mean / std) and theta are requested together,
-    // the pads are zeroed while they are in flight (operands that reach into pad rows / columns must be finite).
-    constexpr int NZ = SB * OB / 256, NT = (NP / 4 + 255) / 256;
-    float x[NZ], mu[NZ], sd[NZ];
+  const int tid = threadIdx.x, s0 = blockIdx.x * SB;
+  // One round trip for everything the block reads: the tile's observations (with the filter's mean / std) are requested here, theta right
+  // after them by mlp_stage, and the pads are zeroed while they are in flight.
+  constexpr int NZ = SB * OB / 256;
+  float x[NZ], mu[NZ], sd[NZ];
 #pragma unroll
-    for (int j = 0; j < NZ; j++) {
-      const int i = tid + 256 * j, sm = i / OB, k = i % OB, r = s0 + sm;
-      x[j] = r < bs ? ob[(size_t)r * OB + k] : 0.0f; mu[j] = mean[k]; sd[j] = stdv[k];
-    }
-    const float4* g = reinterpret_cast<const float4*>(theta);
-    float4 th[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) { const int i = tid + 256 * j; th[j] = i < NP / 4 ? g[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-    const float last = tid < NWT - NP / 4 * 4 && NP / 4 * 4 + tid < NP ? theta[NP / 4 * 4 + tid] : 0.0f;
-    float4* act = reinterpret_cast<float4*>(&S.z[0][0]);
-    for (int i = tid; i < (int)((sizeof(VfShared) - sizeof(S.Wt)) / 16); i += 256) act[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    __syncthreads();
-    float4* d = reinterpret_cast<float4*>(S.Wt);
-#pragma unroll
-    for (int j = 0; j < NT; j++) { const int i = tid + 256 * j; if (i < NP / 4) d[i] = th[j]; }
-    if (tid < NWT - NP / 4 * 4) S.Wt[NP / 4 * 4 + tid] = last;
-    if (tid < SB) { S.z[OB][tid] = 1.0f; S.h1[H][tid] = 1.0f; }
+  for (int j = 0; j < NZ; j++) {
+    const int i = tid + 256 * j, sm = i / OB, k = i % OB, r = s0 + sm;
+    x[j] = r < bs ? ob[(size_t)r * OB + k] : 0.0f; mu[j] = mean[k]; sd[j] = stdv[k];
+  }
+  mlp_stage(S, theta, [&] {
 #pragma unroll
     for (int j = 0; j < NZ; j++) {                            // coalesced read of [sample][input], transposed store
       const int i = tid + 256 * j, sm = i / OB, k = i % OB;
       S.z[k][sm] = (s0 + sm < bs) ? fminf(fmaxf((x[j] - mu[j]) / sd[j], -5.0f), 5.0f) : 0.0f;
     }
-  }
-  __syncthreads();
-  {   // layer 1: h1 = tanh(W1ext^T zext)
-    v16f acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < (OB + 2) / 2; t++) { const int k = 2 * t + hf; acc = mfma32(S.Wt[O_W1 + k * H + u0 + li], S.z[k][li], acc); }
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const int u = u0 + row32(r, hf); if (u < H) S.h1[u][li] = fast_tanh(acc[r]); }
-  }
-  __syncthreads();
-  {   // layer 2
-    v16f acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < (H + 2) / 2; t++) { const int k = 2 * t + hf; acc = mfma32(S.Wt[O_W2 + k * H + u0 + li], S.h1[k][li], acc); }
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const int u = u0 + row32(r, hf); if (u < H) S.h2[u][li] = fast_tanh(acc[r]); }
-  }
-  __syncthreads();
-  {   // output: vpred = w3 . h2 + b3, eight partial sums per sample
-    const int sm = tid % SB, part = tid / SB;
-    float v = 0.0f;
-    for (int j = part; j < H; j += 8) v += S.h2[j][sm] * S.Wt[O_W3 + j];
-    S.vpart[part][sm] = v;
-  }
-  __syncthreads();
-  if (tid < SB) {                                             // error, d loss / d vpred  (loss = mean over the minibatch of (vpred - ret)^2)
-    float v = S.Wt[O_B3];
-#pragma unroll
-    for (int p = 0; p < 8; p++) v += S.vpart[p][tid];
-    S.dv[tid] = (s0 + tid < bs) ? 2.0f * (v - ret[s0 + tid]) / (float)bs : 0.0f;
-  }
-  __syncthreads();
-  // delta2 = dv w3 (1 - h2^2);  dw3, db3
-  for (int i = tid; i < SB * H; i += 256) { const int j = i / SB, sm = i % SB; const float h = S.h2[j][sm]; S.d2[j][sm] = S.dv[sm] * S.Wt[O_W3 + j] * (1.0f - h * h); }
-  if (tid < H) { float a = 0.0f; for (int sm = 0; sm < SB; sm++) a += S.h2[tid][sm] * S.dv[sm]; out[O_W3 + tid] = a; }
-  if (tid == H) { float a = 0.0f; for (int sm = 0; sm < SB; sm++) a += S.dv[sm]; out[O_B3] = a; }
-  __syncthreads();
-  const int col = u0 + li;
-  {
-    v16f g2[4], acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) { g2[0][r] = 0.0f; g2[1][r] = 0.0f; g2[2][r] = 0.0f; g2[3][r] = 0.0f; acc[r] = 0.0f; }
-#pragma unroll
-    for (int t = 0; t < SB / 2; t++) {                        // dW2ext = h1ext delta2^T  (row 100: db2)
-      const float b = S.d2[u0 + li][2 * t + hf];
-#pragma unroll
-      for (int mt = 0; mt < 4; mt++) g2[mt] = mfma32(S.h1[32 * mt + li][2 * t + hf], b, g2[mt]);
-    }
-#pragma unroll
-    for (int t = 0; t < H / 2; t++) acc = mfma32(S.Wt[O_W2 + (u0 + li) * H + 2 * t + hf], S.d2[2 * t + hf][li], acc);    // W2 delta2
-#pragma unroll
-    for (int r = 0; r < 16; r++) {                            // delta1 = (W2 delta2) (1 - h1^2)
-      const int u = u0 + row32(r, hf);
-      if (u < H) { const float h = S.h1[u][li]; S.d1[u][li] = acc[r] * (1.0f - h * h); }
-    }
-    if (col < H) {
-#pragma unroll
-      for (int r = 0; r < 16; r++)
-#pragma unroll
-        for (int mt = 0; mt < 4; mt++) { const int i = 32 * mt + row32(r, hf); if (i <= H) out[O_W2 + i * H + col] = g2[mt][r]; }
-    }
-  }
-  __syncthreads();
-  {
-    v16f g1[2];
-#pragma unroll
-    for (int r = 0; r < 16; r++) { g1[0][r] = 0.0f; g1[1][r] = 0.0f; }
-#pragma unroll
-    for (int t = 0; t < SB / 2; t++) {                        // dW1ext = zext delta1^T  (row 56: db1)
-      const float b = S.d1[u0 + li][2 * t + hf];
-#pragma unroll
-      for (int mt = 0; mt < 2; mt++) g1[mt] = mfma32(S.z[32 * mt + li][2 * t + hf], b, g1[mt]);
-    }
-    if (col < H) {
-#pragma unroll
-      for (int r = 0; r < 16; r++)
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++) { const int i = 32 * mt + row32(r, hf); if (i <= OB) out[O_W1 + i * H + col] = g1[mt][r]; }
-    }
-  }
+  });
+  // error, d loss / d vpred  (loss = mean over the minibatch of (vpred - ret)^2)
+  mlp_forward(S, [&](int sm, float v) { S.dy[sm] = (s0 + sm < bs) ? 2.0f * (v - ret[s0 + sm]) / (float)bs : 0.0f; });
+  mlp_backward(S, partial + (size_t)blockIdx.x * NPAD);
 }
 
-// ---- gradient reduction + MpiAdam step (src/mpi_adam.py:21-35) -----------------------------------------------------------------
-// A block takes 64 parameters; its four waves each sum a quarter of the blocks' partials (in block order, sixteen loads in flight), the
-// quarters are added in order: a fixed summation tree — results do not depend on timing.
-constexpr int ADAM_PARAMS = 64;
+// ---- gradient reduction + MpiAdam step (src/mpi_adam.py:21-35): the summation tree of quarter_sum (mlp_tile.h) ---------------------
+constexpr int ADAM_PARAMS = QCOLS;
 __global__ __launch_bounds__(256) void k_vf_adam(const float* __restrict__ partial, int nblk, float* __restrict__ theta, float* __restrict__ m,
                                                  float* __restrict__ v, float a, float beta1, float beta2, float eps) {
-  __shared__ float quarter[4][ADAM_PARAMS];
-  const int w = threadIdx.x / ADAM_PARAMS, p = blockIdx.x * ADAM_PARAMS + threadIdx.x % ADAM_PARAMS;
-  const int per = (nblk + 3) / 4, b0 = w * per, b1 = min(nblk, b0 + per);
-  float g = 0.0f;
-  if (p < NP) {
-    int b = b0;
-    for (; b + 16 <= b1; b += 16) {
-      float x[16];
-#pragma unroll
-      for (int u = 0; u < 16; u++) x[u] = partial[(size_t)(b + u) * NPAD + p];
-#pragma unroll
-      for (int u = 0; u < 16; u++) g += x[u];
-    }
-    for (; b < b1; b++) g += partial[(size_t)b * NPAD + p];
-  }
-  quarter[w][threadIdx.x % ADAM_PARAMS] = g;
-  __syncthreads();
-  if (w != 0 || p >= NP) return;
-  g = ((quarter[0][threadIdx.x] + quarter[1][threadIdx.x]) + quarter[2][threadIdx.x]) + quarter[3][threadIdx.x];
+  const int p = blockIdx.x * ADAM_PARAMS + threadIdx.x % ADAM_PARAMS;
+  const float g = quarter_sum<NP, NPAD>(partial, nblk);
+  if (threadIdx.x >= ADAM_PARAMS || p >= NP) return;
   const float mm = beta1 * m[p] + (1.0f - beta1) * g;
   const float vv = beta2 * v[p] + (1.0f - beta2) * g * g;
   m[p] = mm; v[p] = vv;
