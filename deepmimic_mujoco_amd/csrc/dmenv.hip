@@ -959,10 +959,10 @@ extern "C" int dm_pg_losses(const float* ob, int32_t n, const float* ac, const f
   double* lpart = (double*)((char*)scratch + (((size_t)dmg::MAX_BLOCKS * dmg::NPAD * sizeof(float) + 255) / 256) * 256);
   if (with_grad)
     hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_GRAD>, dim3(nblk), dim3(256), 0, st, ob, 1, (int)n, ac, atarg, old_mean, old_logstd, (int)write_old, theta,
-                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart);
+                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
   else
     hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_LOSS>, dim3(nblk), dim3(256), 0, st, ob, 1, (int)n, ac, atarg, old_mean, old_logstd, (int)write_old, theta,
-                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart);
+                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
   hipLaunchKernelGGL(dmg::k_pg_reduce, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, (const float*)partial, (const double*)lpart, nblk,
                      with_grad ? (int)dmg::MODE_GRAD : (int)dmg::MODE_LOSS, (float)entcoeff, (const float*)nullptr, 1.0 / (double)n, out_grad, out_losses);
   HIPCHK(hipGetLastError());
@@ -977,7 +977,7 @@ extern "C" int dm_pg_fvp(const float* ob, int32_t stride, int32_t n, const float
   float* partial = (float*)scratch;
   double* lpart = (double*)((char*)scratch + (((size_t)dmg::MAX_BLOCKS * dmg::NPAD * sizeof(float) + 255) / 256) * 256);
   hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_FVP>, dim3(nblk), dim3(256), 0, st, ob, (int)stride, (int)n, (const float*)nullptr, (const float*)nullptr,
-                     (float*)nullptr, (const float*)nullptr, 0, theta, v, rms_mean, rms_std, 1.0f / (float)n, partial, lpart);
+                     (float*)nullptr, (const float*)nullptr, 0, theta, v, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
   hipLaunchKernelGGL(dmg::k_pg_reduce, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, (const float*)partial, (const double*)lpart, nblk, (int)dmg::MODE_FVP,
                      0.0f, v, 1.0 / (double)n, out_fv, (double*)nullptr);
   HIPCHK(hipGetLastError());
@@ -1017,6 +1017,60 @@ extern "C" int dm_disc_lossgrad(const float* theta, const float* rms_mean, const
                      (float)entcoeff, partial);
   hipLaunchKernelGGL(dmd::k_disc_reduce, dim3(dmd::RED_BLOCKS + 1), dim3(256), 0, st, (const float*)partial, nblk, nbg,
                      (int)n_g, (int)n_e, (float)entcoeff, out_grad, out_losses);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
+// ---- behaviour cloning of the policy on expert transitions (csrc/pg_kernel.h MODE_BC) -----------------------------------------------
+static int bc_blocks(int n) { return pg_blocks((n + dmg::SB - 1) / dmg::SB, 0); }
+static size_t bc_lpart_offset(int n) { return up256((size_t)bc_blocks(n) * dmg::NPAD * sizeof(float)); }
+extern "C" size_t dm_bc_scratch_bytes(int32_t bs) {
+  if (bs < 1) return 0;
+  return bc_lpart_offset(bs) + (size_t)bc_blocks(bs) * 2 * sizeof(double);
+}
+// k_pg<BC> over rows idx[0 .. n) (or 0 .. n) and the reduction: partial / lpart in scratch (dm_bc_scratch_bytes(n) bytes)
+static void bc_launch(const float* ob_all, const float* ac_all, const int32_t* idx, int n, const float* theta, const float* rms_mean, const float* rms_std,
+                      int stochastic, uint64_t seed, uint64_t counter, int grad, void* scratch, hipStream_t st) {
+  float* partial = (float*)scratch;
+  double* lpart = (double*)((char*)scratch + bc_lpart_offset(n));
+  const dmg::BcArgs bc{idx, (unsigned long long)seed, (unsigned long long)counter, stochastic ? 1 : 0, grad};
+  hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_BC>, dim3(bc_blocks(n)), dim3(256), 0, st, ob_all, 1, n, ac_all, (const float*)nullptr, (float*)nullptr,
+                     (const float*)nullptr, 1, theta, (const float*)nullptr, rms_mean, rms_std, (float)(1.0 / (28.0 * (double)n)), partial, lpart, bc);
+}
+extern "C" int dm_bc_lossgrad(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean,
+                              const float* rms_std, int32_t stochastic, uint64_t seed, uint64_t counter, float* out_grad, double* out_loss, void* scratch,
+                              size_t scratch_bytes, void* hip_stream) {
+  if (!ob_all || !ac_all || !theta || !rms_mean || !rms_std || !out_loss || !scratch || n < 1 || n > INT32_MAX / dmg::AC || !aligned16(theta))
+    return fail(DM_EINVAL, "dm_bc_lossgrad: bad argument");
+  if (scratch_bytes < dm_bc_scratch_bytes(n)) return fail(DM_EINVAL, "dm_bc_lossgrad: scratch smaller than dm_bc_scratch_bytes(n)");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_bc_lossgrad: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_bc_lossgrad: hipSetDevice failed");
+  hipStream_t st = (hipStream_t)hip_stream;
+  bc_launch(ob_all, ac_all, idx, (int)n, theta, rms_mean, rms_std, (int)stochastic, seed, counter, out_grad ? 1 : 0, scratch, st);
+  const float* partial = (const float*)scratch;
+  const double* lpart = (const double*)((const char*)scratch + bc_lpart_offset(n));
+  hipLaunchKernelGGL(dmg::k_pg_reduce, dim3(out_grad ? (dmg::NP + 255) / 256 : 1), dim3(256), 0, st, partial, lpart, bc_blocks(n), (int)dmg::MODE_BC, 0.0f,
+                     (const float*)nullptr, 1.0 / (28.0 * (double)n), out_grad, out_loss);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
+extern "C" int dm_bc_fit(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
+                         const float* step_scale_host, double beta1, double beta2, double eps, const float* rms_mean, const float* rms_std, int32_t stochastic,
+                         uint64_t seed, uint64_t counter0, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
+  if (!ob_all || !ac_all || !theta || !adam_m || !adam_v || !step_scale_host || !rms_mean || !rms_std || !out_loss || !scratch || iters < 1 || bs < 1 ||
+      bs > INT32_MAX / dmg::AC || !aligned16(theta) || !std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps))
+    return fail(DM_EINVAL, "dm_bc_fit: bad argument");
+  for (int i = 0; i < iters; i++) if (!std::isfinite(step_scale_host[i])) return fail(DM_EINVAL, "dm_bc_fit: non-finite step scale");
+  if (scratch_bytes < dm_bc_scratch_bytes(bs)) return fail(DM_EINVAL, "dm_bc_fit: scratch smaller than dm_bc_scratch_bytes(bs)");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_bc_fit: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_bc_fit: hipSetDevice failed");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const float* partial = (const float*)scratch;
+  const double* lpart = (const double*)((const char*)scratch + bc_lpart_offset(bs));
+  for (int i = 0; i < iters; i++) {
+    bc_launch(ob_all, ac_all, idx ? idx + (size_t)i * bs : nullptr, (int)bs, theta, rms_mean, rms_std, (int)stochastic, seed, counter0 + (uint64_t)i, 1, scratch, st);
+    hipLaunchKernelGGL(dmg::k_bc_adam, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, partial, lpart, bc_blocks(bs), 1.0 / (28.0 * (double)bs), theta, adam_m,
+                       adam_v, step_scale_host[i], (float)beta1, (float)beta2, (float)eps, out_loss + i);
+  }
   HIPCHK(hipGetLastError());
   return DM_OK;
 }

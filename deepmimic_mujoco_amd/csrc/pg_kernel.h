@@ -17,11 +17,18 @@
 // The tile layout is mlp_tile.h's (the 28-wide output layer as 16x16x4 tiles; a ones row under h2 as well, for b3): the bias gradients are row
 // 56 / 100 / 100 of the weight-gradient tiles.  A Fisher product keeps ITS slices of the direction v in registers for the whole launch (106 per
 // lane) instead of streaming v per tile.
+//
+// Behaviour cloning (MODE_BC, the `behavior_clone.learn` that src/gail.py:490-495 calls): loss = mean over the batch x 28 of (x - pi.ac)^2 with
+// the stochastic action pi.ac = m + exp(logstd) eps, eps = normal_from(seed, counter, s * 28 + a) (rng.h; s = the row's position in the batch),
+// or the mean with stochastic = 0.  Rows are gathered by idx from the expert's (ob, ac); the forward and reverse passes are the ones above, the
+// output gradient is G = 2 r / (28 n) with r = m + sigma eps - x, and d loss / d logstd_a = sum_s G sigma eps.  k_bc_adam sums the partials
+// like k_pg_reduce and takes the MpiAdam step on the policy's parameters: one BC iteration is two launches.
 // fp32 like the reference's TF graph; loss sums leave the block in float64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mlp_tile.h"
+#include "rng.h"
 
 namespace dmg {
 using namespace dml;
@@ -32,7 +39,7 @@ constexpr int NPAD = (NP + 63) / 64 * 64;
 constexpr int NWT = (O_LS + 3) / 4 * 4 + 4;           // theta up to logstd, as float4s (the pad holds the first logstd entries: never used as a weight)
 constexpr int MAX_BLOCKS = 256;                       // one block per CU (LDS-limited)
 constexpr int ZR = OB + 2, MR = 32;                   // rows: z + {ones, zeros};  action rows padded to a tile
-enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_FVP = 2 };
+enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_FVP = 2, MODE_BC = 3 };
 static_assert(O_LS % 4 == 0 && NP >= NWT, "theta is copied to LDS as float4s");
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -52,16 +59,20 @@ static_assert(sizeof(PgShared) <= 160 * 1024, "PgShared must fit a CU's LDS");
 // operand reads past a buffer's rows (padded unit tiles) must stay inside the struct: the furthest is W3's row 127 as an A operand
 static_assert(O_W3 + 127 * AC + AC <= NWT + ZR * SBP, "padded W3 rows read into z");
 
+// what only MODE_BC reads: idx [n] rows of ob / ac (null: rows 0 .. n - 1), the noise's seed / counter, and whether to run the reverse pass
+struct BcArgs { const int* idx; unsigned long long seed, counter; int stochastic, grad; };
+
 __device__ inline v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // ob: [.., 56] f32, sample i at row i * stride.  theta: packed policy parameters (NP).  MODE_LOSS / MODE_GRAD: ac [n, 28], atarg [n],
 // old_logstd [28], old_mean [n, 28] — with write_old != 0 the kernel treats old == new and WRITES old_mean (src/trpo.py:247 assign_old_eq_new).
 // MODE_FVP: v = the direction (NP, in global memory).  partial: [gridDim.x][NPAD] f32 gradients; lpart: [gridDim.x][2] f64 (sum of ratio * atarg, sum of KL).
+// MODE_BC: ob [N, 56] / ac [N, 28] are the expert's, rows gathered by bc.idx; write_old = 1; inv_n = 1 / (28 n); lpart = {sum of r^2, 0}.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int stride, int n, const float* __restrict__ ac, const float* __restrict__ atarg,
                                             float* __restrict__ old_mean, const float* __restrict__ old_logstd, int write_old,
                                             const float* __restrict__ theta, const float* __restrict__ v, const float* __restrict__ mean, const float* __restrict__ stdv,
-                                            float inv_n, float* __restrict__ partial, double* __restrict__ lpart) {
+                                            float inv_n, float* __restrict__ partial, double* __restrict__ lpart, BcArgs bc) {
   __shared__ PgShared S;                                      // 141 KB: one block per CU
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 31, hf = l >> 5, l16 = l & 15, q = l >> 4;
   const int u0 = 32 * w;                                      // this wave's hidden-unit tile
@@ -102,6 +113,19 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
   for (int j = 0; j < NZ; j++) { const int k = (tid + 256 * j) % OB; mu[j] = mean[k]; sd[j] = stdv[k]; }
   auto fetch = [&](int tile) {
     const int s0n = tile * SB;
+    if constexpr (MODE == MODE_BC) {                          // gathered rows: each element reads its row's index (rows past n read nothing)
+#pragma unroll
+      for (int j = 0; j < NZ; j++) {
+        const int i = tid + 256 * j, r = s0n + i / OB;
+        obx[j] = r < n ? ob[(size_t)(bc.idx ? bc.idx[r] : r) * OB + i % OB] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < NA; j++) {
+        const int i = tid + 256 * j, r = s0n + i / AC;
+        acx[j] = (i < SB * AC && r < n) ? ac[(size_t)(bc.idx ? bc.idx[r] : r) * AC + i % AC] : 0.0f;
+      }
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < NZ; j++) { const int i = tid + 256 * j, r = s0n + i / OB; obx[j] = r < n ? ob[(size_t)r * stride * OB + i % OB] : 0.0f; }
     if (MODE != MODE_FVP) {
@@ -126,7 +150,10 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
       const int i = tid + 256 * j, sm = i / OB, k = i % OB;
       S.z[k][sm] = (s0g + sm < n) ? fminf(fmaxf((obx[j] - mu[j]) / sd[j], -5.0f), 5.0f) : 0.0f;
     }
-    if (MODE != MODE_FVP) {
+    if constexpr (MODE == MODE_BC) {
+#pragma unroll
+      for (int j = 0; j < NA; j++) { const int i = tid + 256 * j; if (i < SB * AC) S.act[i % AC][i / AC] = acx[j]; }
+    } else if (MODE != MODE_FVP) {
 #pragma unroll
       for (int j = 0; j < NA; j++) { const int i = tid + 256 * j; if (i < SB * AC) { S.act[i % AC][i / AC] = acx[j]; S.om[i % AC][i / AC] = omx[j]; } }
       if (tid < SB) S.at[tid] = atx;
@@ -199,7 +226,41 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
       for (int r = 0; r < 4; r++) { const int a = a0 + 4 * q + r; if (a < AC) S.mo[a][s0 + l16] = acc[r]; }
     }
     __syncthreads();
-    if (MODE == MODE_FVP) {
+    if constexpr (MODE == MODE_BC) {
+      // ---- residual r = m + sigma eps - x, its squares, and G = 2 r / (28 n) in place of the mean: thread = (sample, one of eight action groups) ----
+      const int sm = tid % SB, grp = tid / SB;
+      const bool ok = s0g + sm < n;
+      float sq = 0.0f;
+#pragma unroll
+      for (int j = 0; j < NA; j++) {
+        const int a = grp + 8 * j;
+        float e2 = 0.0f;
+        if (a < AC) {
+          const float eps = (bc.stochastic && ok) ? dmr::normal_from(bc.seed, bc.counter, (unsigned)((s0g + sm) * AC + a)) : 0.0f;
+          const float se = expf(S.ls[a]) * eps;
+          const float r = ok ? (S.mo[a][sm] + se) - S.act[a][sm] : 0.0f;
+          sq += r * r;
+          const float g = 2.0f * r * inv_n;
+          S.mo[a][sm] = g;
+          e2 = g * se;                                        // d loss / d logstd_a of this sample
+        }
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) e2 += __shfl_xor(e2, o, 32);
+        gls[j] += e2;
+      }
+      S.redp[grp][sm][0] = sq;
+      __syncthreads();
+      if (tid < SB) {
+        float q = 0.0f;
+#pragma unroll
+        for (int g8 = 0; g8 < 8; g8++) q += S.redp[g8][tid][0];
+        double b0 = (double)q;                                // the tile's sum of squares: a butterfly over the 32 lanes, in float64
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) b0 += __shfl_xor(b0, o, 32);
+        lsum0 += b0;
+      }
+      if (!bc.grad) continue;
+    } else if (MODE == MODE_FVP) {
       // ---- output gradient of the Fisher product: u = (J v) / sigma^2 / N, in place ----
       for (int i = tid; i < AC * SB; i += 256) {
         const int a = i / SB, sm = i % SB;
@@ -304,6 +365,7 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
   }
   if (tid == 0) { lpart[2 * blockIdx.x] = lsum0; lpart[2 * blockIdx.x + 1] = lsum1; }
   if (MODE == MODE_LOSS) return;
+  if constexpr (MODE == MODE_BC) { if (!bc.grad) return; }
   float* out = partial + (size_t)blockIdx.x * NPAD;
   const int col = u0 + li;
 #pragma unroll
@@ -325,20 +387,42 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
 
 // partial gradients summed in block order (eight loads in flight; the additions stay in order), plus the parts that do not come from the samples:
 // gradient: + entcoeff on logstd (d (entcoeff * mean entropy) / d logstd_a = entcoeff);  Fisher product: 2 v on logstd.
-// Thread 0 of block 0 also finishes the losses: out_losses = {surrgain, meankl} = sums / n.
+// Thread 0 of block 0 also finishes the losses: out_losses = {surrgain, meankl} = sums / n;  MODE_BC: out_losses[0] = the BC loss = sum / (28 n)
+// (inv_n = 1 / (28 n)), and out == null asks for the loss alone.
 __global__ __launch_bounds__(256) void k_pg_reduce(const float* __restrict__ partial, const double* __restrict__ lpart, int nblk, int mode, float entcoeff,
                                                    const float* __restrict__ v, double inv_n, float* __restrict__ out, double* __restrict__ out_losses) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p == 0 && mode != MODE_FVP) {
     double a0 = 0.0, a1 = 0.0;
     for (int b = 0; b < nblk; b++) { a0 += lpart[2 * b]; a1 += lpart[2 * b + 1]; }
-    out_losses[0] = a0 * inv_n; out_losses[1] = a1 * inv_n;
+    out_losses[0] = a0 * inv_n;
+    if (mode != MODE_BC) out_losses[1] = a1 * inv_n;
   }
-  if (p >= NP || mode == MODE_LOSS) return;
+  if (p >= NP || mode == MODE_LOSS || !out) return;
   if (mode == MODE_FVP && p >= O_LS) { out[p] = 2.0f * v[p]; return; }
   float g = column_sum<8>(partial, NPAD, p, 0, nblk);
   if (mode == MODE_GRAD && p >= O_LS) g += entcoeff;
   out[p] = g;
+}
+
+// One BC iteration's MpiAdam step (src/mpi_adam.py:21-35) on the policy's NP parameters: the partials summed as k_pg_reduce sums them (so one
+// dm_bc_fit step equals dm_bc_lossgrad + the host's Adam rule), then k_vf_adam's arithmetic.  a = stepsize sqrt(1 - beta2^t) / (1 - beta1^t).
+// Thread 0 of block 0 writes the iteration's loss, sum / (28 n) (inv_n), in k_pg_reduce's order.
+__global__ __launch_bounds__(256) void k_bc_adam(const float* __restrict__ partial, const double* __restrict__ lpart, int nblk, double inv_n,
+                                                 float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v, float a, float beta1, float beta2,
+                                                 float eps, double* __restrict__ out_loss) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p == 0) {
+    double a0 = 0.0;
+    for (int b = 0; b < nblk; b++) a0 += lpart[2 * b];
+    *out_loss = a0 * inv_n;
+  }
+  if (p >= NP) return;
+  const float g = column_sum<8>(partial, NPAD, p, 0, nblk);
+  const float mm = beta1 * m[p] + (1.0f - beta1) * g;
+  const float vv = beta2 * v[p] + (1.0f - beta2) * g * g;
+  m[p] = mm; v[p] = vv;
+  theta[p] += (-a) * mm / (sqrtf(vv) + eps);
 }
 
 }  // namespace dmg

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rng.h"
 
 namespace dmp {
 
@@ -18,19 +19,7 @@ constexpr int O_PW3 = O_PB2 + HID, O_PB3 = O_PW3 + HID * AC, O_LOGSTD = O_PB3 + 
 constexpr int O_VW1 = O_LOGSTD + AC, O_VB1 = O_VW1 + OB * HID, O_VW2 = O_VB1 + HID, O_VB2 = O_VW2 + HID * HID;
 constexpr int O_VW3 = O_VB2 + HID, O_VB3 = O_VW3 + HID, N_WEIGHTS = O_VB3 + 1;
 
-__device__ inline unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// standard normal from a counter: two 24-bit uniforms, Box-Muller
-__device__ inline float normal_from(unsigned long long seed, unsigned long long counter, unsigned idx) {
-  const unsigned long long h = mix64(mix64(seed ^ (counter * 0xD1342543DE82EF95ull)) + idx);
-  const float u1 = ((float)((h >> 40) & 0xFFFFFF) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-  const float u2 = (float)((h >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
+using dmr::normal_from;
 
 // one dense layer for EB environments: thread u (< 2 * HID) owns hidden unit (net = u / HID, j = u % HID)
 template <int K>

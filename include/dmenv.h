@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 5
+#define DM_ABI_VERSION 6
 
 /* fixed sizes of the DeepMimic humanoid (dp_env_v3.xml:21-156): the kernels are specialised to this tree */
 #define DM_NBODY 14
@@ -344,6 +344,30 @@ int dm_disc_reward(const float* theta, const float* rms_mean, const float* rms_s
 int dm_disc_lossgrad(const float* theta, const float* rms_mean, const float* rms_std, const float* g_ob, const float* g_ac, int32_t n_g,
                      const float* e_ob, const float* e_ac, int32_t n_e, double entcoeff, float* out_grad, double* out_losses, void* scratch,
                      size_t scratch_bytes, void* hip_stream);
+
+/* Behaviour cloning of the policy on expert transitions: the `behavior_clone.learn(pi, dataset, max_iters=BC_max_iter)` that src/gail.py:490-495
+ * calls for --pretrained (OpenAI baselines' GAIL; the module is not in the reference's tree).  loss = mean over n rows x 28 of (x - pi.ac)^2
+ * with the stochastic action pi.ac = mean + exp(logstd) eps, eps = the policy's counter noise normal_from(seed, counter, s * 28 + a) (s: the
+ * row's position in the batch; stochastic = 0: eps = 0, the mode).  theta: the policy's dm_pg_param_count() floats (dm_pg_* order), 16-byte
+ * aligned; rms_mean / rms_std [56]: the policy's obs filter, read and never updated.  ob_all [N, 56] / ac_all [N, 28] float32: the expert's
+ * transitions; rows are gathered by idx.  idx is NOT checked: every entry must lie in 0 .. N - 1 (a null idx takes rows 0 .. n - 1, resp.
+ * 0 .. bs - 1 every iteration).  Every pointer but step_scale_host is a DEVICE pointer on one device; the work is enqueued on `hip_stream`;
+ * no device visible -> DM_ENODEVICE.  Sums are taken in a fixed order: two calls with the same inputs give bitwise-identical results.
+ *   dm_bc_scratch_bytes  scratch both calls need for a batch of bs rows (0 for bs < 1).
+ *   dm_bc_lossgrad       Replaces: `lossandgrad(ob, ac, True)` of one BC iteration: out_loss [1] float64 and, unless out_grad is null,
+ *                        out_grad [dm_pg_param_count()] float32 = the flat gradient of the loss (logstd included; the value net's is zero).
+ *   dm_bc_fit            Replaces: `iters` iterations of `lossandgrad` + `adam.update(g, optim_stepsize)` (MpiAdam(epsilon=adam_epsilon), one
+ *                        process): iteration i takes rows idx[i * bs .. (i + 1) * bs) and counter0 + i, and steps theta, adam_m, adam_v
+ *                        [dm_pg_param_count()] in place with the Adam rule of dm_vf_fit_epoch (step_scale_host [iters] on the HOST:
+ *                        a_t = stepsize sqrt(1 - beta2^t) / (1 - beta1^t)); out_loss [iters] float64 = each iteration's loss before its step.
+ *                        Two launches per iteration, nothing comes back to the host. */
+size_t dm_bc_scratch_bytes(int32_t bs);
+int dm_bc_lossgrad(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean,
+                   const float* rms_std, int32_t stochastic, uint64_t seed, uint64_t counter, float* out_grad, double* out_loss, void* scratch,
+                   size_t scratch_bytes, void* hip_stream);
+int dm_bc_fit(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
+              const float* step_scale_host, double beta1, double beta2, double eps, const float* rms_mean, const float* rms_std, int32_t stochastic,
+              uint64_t seed, uint64_t counter0, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream);
 
 /* Diagnostics of DM_OPT_PACKED (four environments per wavefront, csrc/slot_kernel.h): env-steps so far that exceeded a capacity of that
  * path (DM_PACKED_*: rows, contacts / contact pairs, pairs past the bounding spheres, box staging slots; or a PGS step the cost test would

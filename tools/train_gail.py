@@ -3,20 +3,25 @@
 
     python tools/train_trpo.py --task evaluate --load-model-path tests/golden/ckpt/trpo-walk-0 --save-sample expert.npz
     python tools/train_gail.py --expert-path expert.npz --envs 4096 --horizon 128 --seconds 120 [--save gail.npz]
+    python tools/train_gail.py --expert-path expert.npz --pretrained --BC-max-iter 2000 --bc-save bc ...   (GAIL from a behaviour-cloned policy)
 
 --task evaluate runs the policy of --load-model-path like train_trpo.py's; --task sample does the same and writes the trajectories
 (--save-sample, default sample.npz).  --save writes the policy as train_trpo.py --save does and the adversary's variables to
 <save without .npz>.adversary.npz.
+--pretrained clones the expert first (src/gail.py:490-495, behavior_clone.learn: --BC-max-iter Adam iterations of 128 transitions) and GAIL
+starts from that policy; --bc-save writes the cloned policy (x.npz or a checkpoint prefix) for train_trpo.py --task evaluate.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy  # noqa: E402
+from deepmimic_mujoco_amd import behavior_clone  # noqa: E402
 from deepmimic_mujoco_amd.gail import ExpertDataset, TransitionClassifier, learn  # noqa: E402
 
 
@@ -47,6 +52,9 @@ def main():
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON")
     ap.add_argument("--log-dir", default=None, help="write progress.csv and monitor.csv in the reference's formats")
     ap.add_argument("--save", default=None, help="write the trained policy (x.npz or a checkpoint prefix) and the adversary (x.adversary.npz)")
+    ap.add_argument("--pretrained", action="store_true", help="behaviour-clone the expert before GAIL (the reference's --pretrained)")
+    ap.add_argument("--BC-max-iter", dest="BC_max_iter", type=int, default=10000, help="--pretrained: BC iterations (the reference's --BC_max_iter)")
+    ap.add_argument("--bc-save", default=None, help="--pretrained: write the cloned policy (x.npz or a checkpoint prefix) before GAIL")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -63,6 +71,15 @@ def main():
     expert = ExpertDataset(args.expert_path, traj_limitation=args.traj_limitation, seed=args.seed, device=dev)
     env = DPVecEnv(args.envs, motion=args.motion, device=0, reward=args.reward, autoreset="init", seed=args.seed)
     pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed)
+    if args.pretrained:                                     # src/gail.py:490-495
+        t0 = time.time()
+        train, _ = behavior_clone.learn(pi, expert, max_iters=args.BC_max_iter, verbose=True, seed=args.seed)
+        print("BC done: %d iterations in %.2f s, train loss %.6f -> %.6f (mean of the first / last %d)"
+              % (len(train), time.time() - t0, train[:100].mean(), train[-100:].mean(), min(100, len(train))))
+        if args.bc_save and args.bc_save.endswith(".npz"):
+            pi.save_npz(args.bc_save)
+        elif args.bc_save:
+            pi.save_tf_checkpoint(args.bc_save)
     reward_giver = TransitionClassifier(hidden_size=args.adversary_hidden_size, entcoeff=args.adversary_entcoeff, device=dev, seed=args.seed)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     hist = learn(env, pi, reward_giver, expert, g_step=args.g_step, d_step=args.d_step, d_stepsize=args.d_stepsize, timesteps_per_batch=args.horizon,
