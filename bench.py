@@ -22,19 +22,23 @@ windows of `--steps` steps each, every one bracketed by barrier + synchronize (`
 steps the [256, n, 87] f32 rollout block is all-gathered (RCCL with `--dist-backend nccl`, the default; `gloo` stages the block through pinned host
 memory so that the multi-rank code path can run where only one GPU is visible; `--force-dist` takes that path with ONE rank) — asynchronously,
 double-buffered; every gather completes inside the timed region.  Prints ONE JSON line (rank 0).
-
-Further legs in the same line (N = 1 or max over ranks, same barriers):
-  `vecenv_step`     the same number of steps through the facade `DPVecEnv.step(actions, out=...)` with nothing queued: one launch set per call on the
-                    kernel DPVecEnv(packed=None) picks — what a caller gets that consumes every step's outputs (the drop-in for VecEnv.step);
-  `horizon_launch`  the window rounded up to whole 256-step horizons through `dm_batch_rollout` (T steps per call).
 `--step-queue 0` times one launch set per `dm_batch_step` call (rounds 1-3's `value`); `--horizon-launch` makes the rollout call the timed leg.
 `--dump-outputs DIR` writes the last timed step's obs / reward / done (rank 0's shard) as DIR/<name>.npy: the same arguments give the same inputs, so
 two builds of the library can be compared output for output.
 
-Besides the contract fields the line carries (N = 1): `roofline` (HBM fraction from the algorithmic bytes per launch and the launch's duration by HIP
-events the library records around it; fp64 fraction from a flop count of the kernel's algorithm on the run's own row / sweep statistics; with
-rocprofv3 on PATH, live PMC passes of this very workload: HBM traffic, VALU issue fraction, lane efficiency), `cpu_baseline` (the oracle on the host
-cores), `single_env_gym_loop` (steps/s of a Python `DPEnv.step` loop, the path src/trpo.py:47-80 drives).
+A plain run does only what the headline needs: set-up, the untimed pre-warm and warm-up steps, the timed windows, the dump, the line.  Beside the
+contract fields it carries `value_spread`, the `config` of the run and the part of `roofline` that the timed windows' own HIP events give (`achieved`,
+`frac`, `kernel_ms`).  Everything else is measured or checked with `--full` only (the `--no-*` options leave parts of it out):
+  `vecenv_step`     the same number of steps through the facade `DPVecEnv.step(actions, out=...)` with nothing queued: one launch set per call on the
+                    kernel DPVecEnv(packed=None) picks — what a caller gets that consumes every step's outputs (the drop-in for VecEnv.step);
+  `horizon_launch`  the window rounded up to whole 256-step horizons through `dm_batch_rollout` (T steps per call);
+                    (both legs: N = 1 or max over ranks, same barriers)
+  `roofline`        the launch's own duration by HIP events the library records around it (`launch.avg_us`); the fp64 fraction from a flop count of
+                    the kernel's algorithm on row / sweep statistics of a few more steps (`fp64_*`, `config.mean_nefc` / `mean_pgs_sweeps`); N = 1 with
+                    rocprofv3 on PATH, live PMC passes of this very workload in child processes: HBM traffic, VALU issue fraction, lane efficiency;
+  `cpu_baseline`    (N = 1) the oracle on the host cores;
+  `single_env_gym_loop`  (N = 1) steps/s of a Python `DPEnv.step` loop, the path src/trpo.py:47-80 drives;
+  `config.learner_allmean_ok`  (N > 1 or `--force-dist`) the learner's all-mean on a gradient-sized vector over the process group.
 """
 import argparse
 import json
@@ -427,9 +431,7 @@ def distinct_gpus(rows):
 RANK_DEVICES = []      # per rank: PCI address of its GPU, gathered over the process group at start-up (multi-rank runs)
 
 
-def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "--_cpu-worker":
-        return cpu_baseline_worker(sys.argv[2], sys.argv[3], int(sys.argv[4]), float(sys.argv[5]))
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
@@ -447,9 +449,12 @@ def main():
     ap.add_argument("--unfused", action="store_true", help="rollout workload: separate policy launch per step (the round-1 form) instead of the fused step")
     ap.add_argument("--dtype", type=int, default=64, choices=[64, 32],
                     help="arithmetic of the kernels: 64 (the parity path, the judged line) or 32 (libdmenv32.so, the float32 build: informational)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 counter passes (N = 1 only; they add about a minute)")
-    ap.add_argument("--no-gym-loop", action="store_true", help="skip the single-env Python DPEnv.step loop (N = 1 only; ~3 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the vecenv_step and horizon_launch legs, the roofline's launch timing, "
+                         "flop count and live PMC passes, the single-env gym loop, the CPU baseline, the learner's all-mean (a plain run skips them all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (N = 1 only; ~15 s)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the live rocprofv3 counter passes (N = 1 only; they add about a minute)")
+    ap.add_argument("--no-gym-loop", action="store_true", help="with --full: skip the single-env Python DPEnv.step loop (N = 1 only; ~3 s)")
     ap.add_argument("--prewarm-horizons", type=int, default=6, help="untimed 256-step horizons before the warm-up steps (cold-box clock ramp, ~1 s)")
     ap.add_argument("--horizon-launch", action="store_true",
                     help="step through dm_batch_rollout: up to one %d-step horizon of pre-drawn actions per call (on the packed path ONE launch in which every "
@@ -459,8 +464,8 @@ def main():
                          "four environments through the queued steps at its own pace) when the queue is full or the caller joins; implies four environments per "
                          "wavefront.  0 = every call launches (rounds 1-3).  Applies to the full-contact workloads at up to 8192 envs per GPU")
     ap.add_argument("--repeats", type=int, default=3, help="timed windows of --steps steps each; `value` is the median window, `value_spread` min / median / max")
-    ap.add_argument("--no-vecenv-leg", action="store_true", help="skip the leg that times the same steps through DPVecEnv.step, one launch per call")
-    ap.add_argument("--no-horizon-leg", action="store_true", help="skip the second timed leg (the same steps through dm_batch_rollout, reported as `horizon_launch`)")
+    ap.add_argument("--no-vecenv-leg", action="store_true", help="with --full: skip the leg that times the same steps through DPVecEnv.step, one launch per call")
+    ap.add_argument("--no-horizon-leg", action="store_true", help="with --full: skip the second timed leg (the same steps through dm_batch_rollout, reported as `horizon_launch`)")
     ap.add_argument("--rollout-form", default="auto", choices=["auto", "launch", "steps"],
                     help="dm_batch_rollout on the packed path (DM option 106): one launch per call, the library's step launches, or chosen by batch size (default)")
     ap.add_argument("--horizon-chunk", type=int, default=HORIZON, help="--horizon-launch: steps per dm_batch_rollout call (the dispatch order — which environments share a wavefront — is renewed between calls)")
@@ -473,7 +478,14 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed windows, write what the timed path returned for its last step (rank 0's shard: obs, reward, done) as DIR/<name>.npy")
     ap.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)   # profiled child of pmc_passes: GPU loop only, prints nothing
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--_cpu-worker":
+        return cpu_baseline_worker(sys.argv[2], sys.argv[3], int(sys.argv[4]), float(sys.argv[5]))
+    args = parse_args()
+    extras = args.full and not args._child          # everything beyond the headline (module docstring)
 
     import torch
     import torch.distributed as dist
@@ -661,18 +673,18 @@ def main():
             dumped = {"obs": obs_T[k].to(torch.float64).cpu().numpy(), "reward": rew_T[k].to(torch.float64).cpu().numpy(),
                       "done": done_T[k].to(torch.float32).cpu().numpy()}
         host_issue_us = float(np.median(issue_s[:reps])) / args.steps * 1e6
-        # per-launch duration of the step kernel by HIP events on the stream it is launched on (pipelined: sub-batch 0's launch on
+        # --full: per-launch duration of the step kernel by HIP events on the stream it is launched on (pipelined: sub-batch 0's launch on
         # its own stream, while the other sub-batches keep the machine busy): untimed, sampled after the clock stopped
         launch_us = []
         queue_launch_steps = min(queue, args.steps) if queue else 0        # steps one horizon launch of the timed window carries
-        if not args._child and queue:
+        if extras and queue:
             env.batch.enable_timing(True)
             for _ in range(3):                                             # the horizon launch of a window-sized queue, by the library's events around it
                 run_steps(0, queue_launch_steps); env.batch.join()
                 launch_us.append(env.batch.last_step_ms() * 1e3)
             env.batch.enable_timing(False)
             drain(); env.batch.sync()
-        elif not args._child and not args.horizon_launch:
+        elif extras and not args.horizon_launch:
             env.batch.enable_timing(True)
             for t in range(args.steps, args.steps + 48):
                 one_step(t)
@@ -680,18 +692,18 @@ def main():
                     launch_us.append(env.batch.last_step_ms() * 1e3)
             env.batch.enable_timing(False)
             env.batch.sync()
-        # row / sweep statistics for the flop count: untimed, a few more steps sampled after the clock stopped
-        if not args._child:
+        # --full: row / sweep statistics for the flop count: untimed, a few more steps sampled after the clock stopped
+        if extras:
             for t in range(args.steps, args.steps + 8):
                 one_step(t)
                 env.batch.sync()
                 stat_nefc.append(env.batch.get(A.F_NEFC)); stat_iter.append(env.batch.get(A.F_SOLVER_ITER))
             drain()
-        # ---- further legs, reported beside the judged value (same state stream, same pre-drawn actions; max over ranks, same barriers) ----------
+        # ---- --full: further legs, reported beside the judged value (same state stream, same pre-drawn actions; max over ranks, same barriers) --
         # (1) `vecenv_step`: the same number of steps through the facade `DPVecEnv.step` (the drop-in for VecEnv.step, src/utils/vec_env/__init__.py:
         #     26-100), nothing queued: every call launches, on the kernel DPVecEnv(packed=None) picks for this batch size
         ve_elapsed = None; ve_kernel = None
-        if not args._child and args.dtype == 64 and not args.horizon_launch and not args.no_vecenv_leg:
+        if extras and args.dtype == 64 and not args.horizon_launch and not args.no_vecenv_leg:
             bt = env.batch
             was_packed = env.packed
             if queue:
@@ -715,7 +727,7 @@ def main():
         #     environments through all steps at its own pace (what a queue of 256 steps also becomes)
         hl_elapsed = None; hl_redo = None
         hl_steps = (args.steps + HORIZON - 1) // HORIZON * HORIZON          # whole horizons: a horizon launch shorter than a horizon has not averaged its waves yet
-        if not args._child and args.dtype == 64 and not args.horizon_launch and not args.no_horizon_leg:
+        if extras and args.dtype == 64 and not args.horizon_launch and not args.no_horizon_leg:
             bt = env.batch
             was_packed = env.packed; was_auto = bool(bt.__dict__.get("_auto", False))
             if was_auto:
@@ -732,7 +744,7 @@ def main():
     mid = order[reps // 2]                                                  # the median window is the one reported
     elapsed_all = [w[0] for w in windows]
     allmean_ok = None
-    if dist_on:
+    if dist_on and extras:
         from deepmimic_mujoco_amd.trpo import allmean
         gvec = torch.full((18656,), float(rank + 1), dtype=torch.float32, device=dev if args.dist_backend == "nccl" else "cpu")   # the flat gradient's size (src/trpo.py:175-180)
         allmean(gvec, force=True)
@@ -751,7 +763,8 @@ def main():
     elapsed = elapsed_all[mid]
     gpu_ms = windows[mid][1]
     status = env.batch.get(A.F_STATUS)
-    nefc = np.concatenate(stat_nefc); iters = np.concatenate(stat_iter)
+    nefc = np.concatenate(stat_nefc) if stat_nefc else None                 # (--full only)
+    iters = np.concatenate(stat_iter) if stat_iter else None
 
     if rank == 0:
         total_steps = world * n * args.steps
@@ -763,8 +776,7 @@ def main():
         label = wl["label"] % ((n, rew_name) if full else (n,))
         if wl["shards"] > 1 and world == 1:
             label += "; ONE shard timed (shard %d of %d: global env ids %d..%d, no gather)" % (shard, wl["shards"], shard * n, shard * n + n - 1)
-        flops = float(step_flops(nefc, iters).mean())
-        tflops = flops * n / (kernel_ms * 1e-3) / 1e12
+        flops = float(step_flops(nefc, iters).mean()) if nefc is not None else None
         out = {
             "metric": "env-steps/sec", "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -787,7 +799,8 @@ def main():
                                            "dm_batch_join); bit-identical to unqueued packed steps (tests/test_gpu_queue.py).  A closed loop that joins every step gets one launch "
                                            "per call: `vecenv_step`" % (queue, queue)) if queue else None,
                        "sim_steps_per_env_step": 1,
-                       "mean_nefc": round(float(nefc.mean()), 2), "mean_pgs_sweeps": round(float(iters.mean()), 2),
+                       "mean_nefc": round(float(nefc.mean()), 2) if nefc is not None else None,
+                       "mean_pgs_sweeps": round(float(iters.mean()), 2) if iters is not None else None,
                        "overflow_envs": int((status & 1).sum()),
                        "envs_per_wavefront": 4 if env.packed else 1, "kernel_switches_by_row_statistics": getattr(env.batch, "auto_switches", None), "packed_redo_env_steps": env.batch.redo_total() if env.packed else None,
                        "actions": ("i.i.d. N(0, 0.9^2) per (env, step) within a %d-step horizon, pre-drawn on the device (%d x %d x 28 f64), the same "
@@ -831,22 +844,26 @@ def main():
                                     {"kernel": step_kernel, "envs_per_launch": n, "steps_per_launch": queue_launch_steps,
                                      "algorithmic_bytes": ALGO_BYTES_PER_STEP * n * queue_launch_steps,
                                      "avg_us": round(float(np.mean(launch_us)), 1) if launch_us else None,
-                                     "measured": "HIP events the library records around the horizon launch on its stream (dm_batch_last_step_ms), %d launches of %d queued steps "
-                                                 "sampled after the timed region" % (len(launch_us), queue_launch_steps)}
+                                     "measured": ("HIP events the library records around the horizon launch on its stream (dm_batch_last_step_ms), %d launches of %d queued steps "
+                                                  "sampled after the timed region" % (len(launch_us), queue_launch_steps)) if launch_us else "not sampled (--full samples it)"}
                                     if queue else None) or {"kernel": step_kernel, "envs_per_launch": n // P_sub, "launches_per_step": P_sub,
                                     "algorithmic_bytes": ALGO_BYTES_PER_STEP * (n // P_sub),
                                     "avg_us": round(float(np.mean(launch_us)), 1) if launch_us else None,
-                                    "measured": "HIP events on the launch's own stream, %d launches sampled after the timed region" % len(launch_us),
+                                    "measured": ("HIP events on the launch's own stream, %d launches sampled after the timed region" % len(launch_us)) if launch_us
+                                                else "not sampled (--full samples it)",
                                     "launches_in_flight": round(float(np.mean(launch_us)) * 1e-3 * P_sub / kernel_ms, 2) if launch_us else None,
                                     "note": "`achieved` is the whole-GPU rate, bytes of one step / step interval: with pipelined sub-batches "
                                             "launches overlap, so bytes / one launch's duration is only that launch's share of the machine"},
-                         "note": "latency / fp64-issue bound path, not an HBM stream: see the fp64 and VALU fields",
-                         "fp64_flops_per_env_step": round(flops, 0),
-                         "fp64_flops_source": "flop count of the kernel's algorithm (bench.py eval_flops) on this run's nefc / PGS-sweep samples (%d env-steps)" % nefc.size,
-                         "fp64_tflops": round(tflops, 4), "fp64_valu_peak_tflops": FP64_VALU_PEAK_TFLOPS,
-                         "fp64_frac": round(tflops / FP64_VALU_PEAK_TFLOPS, 5)},
+                         "note": "latency / fp64-issue bound path, not an HBM stream: see the fp64 and VALU fields (--full)"},
         }
-        if world == 1 and not args.no_pmc:
+        if flops is not None:
+            tflops = flops * n / (kernel_ms * 1e-3) / 1e12
+            out["roofline"].update({
+                "fp64_flops_per_env_step": round(flops, 0),
+                "fp64_flops_source": "flop count of the kernel's algorithm (bench.py eval_flops) on this run's nefc / PGS-sweep samples (%d env-steps)" % nefc.size,
+                "fp64_tflops": round(tflops, 4), "fp64_valu_peak_tflops": FP64_VALU_PEAK_TFLOPS,
+                "fp64_frac": round(tflops / FP64_VALU_PEAK_TFLOPS, 5)})
+        if extras and world == 1 and not args.no_pmc:
             hz = args.horizon_launch or bool(queue)          # the profiled child runs exactly one HORIZON-step launch of k_rollout_packed
             tail = ["--workload", args.workload, "--reward", args.reward] + (["--steps", str(HORIZON), "--warmup", "0", "--prewarm-horizons", "0"] + (["--horizon-launch"] if args.horizon_launch else ["--step-queue", str(HORIZON)]) if hz
                                                                               else ["--steps", "48", "--warmup", "8", "--prewarm-horizons", "1", "--step-queue", "0"]) + [
@@ -887,13 +904,13 @@ def main():
                 if pmc.get("SQ_WAVE_CYCLES") and pmc.get("SQ_WAIT_ANY"):
                     r["wave_wait_frac"] = round(pmc["SQ_WAIT_ANY"] / pmc["SQ_WAVE_CYCLES"], 4)
                     r["wave_valu_frac"] = round(pmc.get("SQ_ACTIVE_INST_VALU", 0.0) / pmc["SQ_WAVE_CYCLES"], 4)
-        if world == 1 and not args.no_gym_loop:
+        if extras and world == 1 and not args.no_gym_loop:
             try:
                 env.close()
                 out["single_env_gym_loop"] = single_env_gym_loop(local_dev)
             except Exception as e:
                 out["single_env_gym_loop"] = {"value": None, "error": repr(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:
+        if extras and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(clip, args.reward if full else "alive")
             except Exception as e:  # the baseline must never take the GPU number down with it

@@ -120,13 +120,13 @@ def test_native_policy_kernel_matches_torch_forward():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    """bench.py's output contract: ONE JSON line with the metric, the roofline object and (N = 1) the CPU baseline."""
+    """bench.py's output contract: ONE JSON line with the metric, the roofline object and (N = 1, `--full`) the CPU baseline."""
     import json
     import subprocess
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "4", "--prewarm-horizons", "0",
-                          "--envs", "512"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--envs", "512", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -149,6 +149,35 @@ def test_bench_prints_one_contract_line():
     # the headline states its own precondition: the step queue is a non-default option, and what `value` therefore is
     assert j["config"]["non_default_options"] == ["DM_OPT_STEP_QUEUE=256"] and "vecenv_step" in j["config"]["value_is"]
     assert j["config"]["distinct_gpus"] == 1 and j["config"]["rank_devices"] is None        # (single process: no process group to gather the PCI addresses over)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_extras_to_full(tmp_path):
+    """A plain run does only what its headline needs: no further legs, no launch sampling or flop count, no gym loop, no CPU baseline.  `--full`
+    adds them after the same timed steps: both runs dump the same last timed step, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4", "--prewarm-horizons", "0", "--envs", "512"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-pmc", "--no-cpu-baseline", "--no-gym-loop"])):
+        out = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(got) == 1, out.stdout[-2000:]
+        lines[name] = json.loads(got[0])
+    p, f = lines["plain"], lines["full"]
+    for j in (p, f):
+        assert j["metric"] == "env-steps/sec" and j["unit"] == "env-steps/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+        assert j["value"] > 1e5 and j["ms_per_step"] > 0 and j["steps"] == 16 and j["warmup"] == 4 and j["value_spread"]["windows"] == 3
+    assert p["vecenv_step"] is None and p["horizon_launch"] is None and "cpu_baseline" not in p and "single_env_gym_loop" not in p
+    assert p["roofline"]["achieved"] > 0 and p["roofline"]["launch"]["avg_us"] is None and "fp64_frac" not in p["roofline"] and "pmc" not in p["roofline"]
+    assert p["config"]["mean_nefc"] is None
+    assert f["vecenv_step"]["value"] > 1e5 and f["horizon_launch"]["value"] > 1e5
+    assert f["roofline"]["launch"]["avg_us"] > 0 and f["roofline"]["fp64_frac"] > 0 and f["config"]["mean_nefc"] is not None
+    for name in ("obs", "reward", "done"):
+        assert np.array_equal(np.load(str(tmp_path / "plain" / (name + ".npy"))), np.load(str(tmp_path / "full" / (name + ".npy")))), name
 
 
 @pytest.mark.gpu
@@ -188,7 +217,7 @@ def test_bench_rccl_code_path_runs_at_world_size_one():
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "cfg5", "--steps", "512", "--warmup", "0", "--prewarm-horizons", "0",
-                          "--force-dist", "--dist-backend", "nccl", "--alloc-gather-world", "8", "--repeats", "1", "--no-pmc", "--no-cpu-baseline", "--no-gym-loop",
+                          "--force-dist", "--dist-backend", "nccl", "--alloc-gather-world", "8", "--repeats", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--no-gym-loop",
                           "--no-vecenv-leg", "--no-horizon-leg"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "nccl process group up, 1 ranks (backend reports nccl)" in out.stderr
@@ -309,7 +338,7 @@ def test_bench_other_workloads_print_the_contract_line(extra):
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "24", "--warmup", "4", "--prewarm-horizons", "0", "--envs", "768",
-                          "--no-pmc", "--no-cpu-baseline", "--no-gym-loop"] + extra, capture_output=True, text=True, timeout=600, cwd=root)
+                          "--full", "--no-pmc", "--no-cpu-baseline", "--no-gym-loop"] + extra, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
     assert j["value"] > 1e5 and j["n_gpus"] == 1 and j["steps"] == 24 and j["config"]["envs_per_gpu"] == 768

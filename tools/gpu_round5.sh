@@ -19,7 +19,7 @@ for WHAT in "$@"; do case "$WHAT" in
     # A/B of whole-library builds under build_ab/ inside one call: the driver's 20-step window and the 512-step default, alternating
     for rep in 1 2; do for v in ${WHAT#ab:}; do
       for st in "20 5" "512 64"; do set -- $st
-        o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py $Q --steps $1 --warmup $2 2>$OUT/ab_err.txt | python -c "
+        o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py --full $Q --steps $1 --warmup $2 2>$OUT/ab_err.txt | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 print('value %.3f M  spread %.2f..%.2f  vecenv %s  horizon %s  launch_us %s' % (j['value']/1e6, j['value_spread']['min']/1e6, j['value_spread']['max']/1e6,
@@ -30,7 +30,7 @@ print('value %.3f M  spread %.2f..%.2f  vecenv %s  horizon %s  launch_us %s' % (
   hl:*)
     # horizon-launch leg only, five windows of 1024 steps, imitation and alive rewards: tight A/B of builds whose difference is a per-cent
     for rep in 1 2; do for v in ${WHAT#hl:}; do for rw in ${HL_REWARDS:-imitation alive}; do
-      o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py $Q --no-vecenv-leg --no-horizon-leg --reward $rw --steps 1024 --warmup 0 --repeats 5 2>$OUT/hl_err.txt | python -c "
+      o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py --full $Q --no-vecenv-leg --no-horizon-leg --reward $rw --steps 1024 --warmup 0 --repeats 5 2>$OUT/hl_err.txt | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('value %.3f M  spread %.3f..%.3f  launch_us %s' % (j['value']/1e6, j['value_spread']['min']/1e6, j['value_spread']['max']/1e6, j['roofline']['launch'].get('avg_us')))")
       echo "$v $rw : ${o:-FAILED $(tail -2 $OUT/hl_err.txt | cut -c1-200)}" | tee -a $OUT/hl.log
@@ -38,7 +38,7 @@ j=json.loads(sys.stdin.read()); print('value %.3f M  spread %.3f..%.3f  launch_u
   ps:*)
     # one launch set per call (k_step_narrow at 4096 envs, k_step_packed at 8192): tight A/B of builds, five windows of 512 steps
     for rep in 1 2; do for v in ${WHAT#ps:}; do for wl in cfg3 cfg5; do
-      o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py $Q --no-vecenv-leg --no-horizon-leg --step-queue 0 --workload $wl --steps 512 --warmup 64 --repeats 5 2>$OUT/ps_err.txt | python -c "
+      o=$(DMENV_LIB=$PWD/build_ab/$v.so timeout 300 python bench.py --full $Q --no-vecenv-leg --no-horizon-leg --step-queue 0 --workload $wl --steps 512 --warmup 64 --repeats 5 2>$OUT/ps_err.txt | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('value %.3f M  spread %.3f..%.3f  kernel %s' % (j['value']/1e6, j['value_spread']['min']/1e6, j['value_spread']['max']/1e6, j['roofline']['kernel']))")
       echo "$v $wl : ${o:-FAILED $(tail -2 $OUT/ps_err.txt | cut -c1-200)}" | tee -a $OUT/ps.log
@@ -68,16 +68,16 @@ j=json.loads(sys.stdin.read()); print('standing packed %.3f M  one-env %.3f M' %
     ( timeout 1500 python -m pytest ${WHAT#pytest:} -x -q 2>&1 | tail -25 ) | tee -a $OUT/pytest_sel.log ;;
   bench)
     rm -rf $OUT/rawq $OUT/raw1; mkdir -p $OUT/raw
-    DM_PROFILE_KEEP=$OUT/rawq timeout 900 python bench.py > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; cut -c1-600 $OUT/bench_cfg3.json
+    DM_PROFILE_KEEP=$OUT/rawq timeout 900 python bench.py --full > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; cut -c1-600 $OUT/bench_cfg3.json
     for f in $OUT/rawq/*; do mv $f $OUT/raw/${TAGP:-r05}_cfg3_queue_$(basename $f); done
     # the one-launch-set-per-call form with its own counter passes (what vecenv_step times): raw exports for the k_step_narrow summary
-    DM_PROFILE_KEEP=$OUT/raw1 timeout 600 python bench.py --step-queue 0 --no-cpu-baseline --no-gym-loop --no-vecenv-leg --no-horizon-leg > $OUT/bench_cfg3_unqueued_pmc.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_unqueued_pmc.json
+    DM_PROFILE_KEEP=$OUT/raw1 timeout 600 python bench.py --full --step-queue 0 --no-cpu-baseline --no-gym-loop --no-vecenv-leg --no-horizon-leg > $OUT/bench_cfg3_unqueued_pmc.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_unqueued_pmc.json
     for f in $OUT/raw1/*; do mv $f $OUT/raw/${TAGP:-r05}_cfg3_kstep_$(basename $f); done
-    timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 $Q > $OUT/bench_cfg3_driver_window.json 2>/dev/null; cut -c1-300 $OUT/bench_cfg3_driver_window.json ;;
+    timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 $Q > $OUT/bench_cfg3_driver_window.json 2>/dev/null; cut -c1-300 $OUT/bench_cfg3_driver_window.json ;;
   benchall)
-    for rw in alive v3-config; do timeout 300 python bench.py --reward $rw $Q > $OUT/bench_cfg3_$rw.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_$rw.json; done
-    for wl in cfg2 cfg4 cfg5; do timeout 300 python bench.py --workload $wl $Q > $OUT/bench_$wl.json 2>/dev/null; cut -c1-200 $OUT/bench_$wl.json; done
-    timeout 300 python bench.py --step-queue 0 $Q > $OUT/bench_cfg3_unqueued.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_unqueued.json
+    for rw in alive v3-config; do timeout 300 python bench.py --full --reward $rw $Q > $OUT/bench_cfg3_$rw.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_$rw.json; done
+    for wl in cfg2 cfg4 cfg5; do timeout 300 python bench.py --full --workload $wl $Q > $OUT/bench_$wl.json 2>/dev/null; cut -c1-200 $OUT/bench_$wl.json; done
+    timeout 300 python bench.py --full --step-queue 0 $Q > $OUT/bench_cfg3_unqueued.json 2>/dev/null; cut -c1-200 $OUT/bench_cfg3_unqueued.json
     timeout 300 python bench.py --workload rollout --steps 2048 --warmup 256 > $OUT/bench_rollout_fused.json 2>/dev/null; cut -c1-200 $OUT/bench_rollout_fused.json ;;
   trace)
     # the judged command's kernel trace: the profiled child runs nothing but horizons of 256 queued steps (one untimed + the 512 timed ones = 3 launches)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fill the PMC table of a kernel summary (profiles/rNN_kstep*_summary.md) from the raw per-launch counter exports bench.py keeps with
+"""Fill the PMC table of a kernel summary (profiles/rNN_kstep*_summary.md) from the raw per-launch counter exports `bench.py --full` keeps with
 DM_PROFILE_KEEP (profiles/raw/<prefix>_{sq,fetch,write,grbm}_counters.csv): average per launch and number of launches per (kernel, counter).
 usage: python tools/pmc_table.py <summary.md> <raw prefix> [note]"""
 import collections
