@@ -1074,6 +1074,93 @@ extern "C" int dm_bc_fit(const float* ob_all, const float* ac_all, const int32_t
   HIPCHK(hipGetLastError());
   return DM_OK;
 }
+// ---- PPO's clipped-surrogate update of the policy and the value net (csrc/pg_kernel.h MODE_PPO, k_ppo_step; vf_kernel.h k_vf_grad_rows) -----
+// scratch: both halves' loss sums first (their offsets do not depend on n), then the gradient partials of a call with the gradient
+static int ppo_vf_blocks(int n, int grad) { const int t = (n + dmv::SB - 1) / dmv::SB; return grad ? t : (t < dmg::MAX_BLOCKS ? t : dmg::MAX_BLOCKS); }
+static_assert(dmg::NP % 4 == 0, "the value half of a PPO theta starts 16-byte aligned");
+struct PpoScratch { size_t pg_lp, vf_lp, pg_part, vf_part, total; };
+static PpoScratch ppo_scratch_layout(int n, int grad) {
+  PpoScratch L;
+  size_t o = 0;
+  L.pg_lp = o; o += up256((size_t)dmg::MAX_BLOCKS * dmg::PPO_LP * sizeof(double));
+  const int vb = ppo_vf_blocks(n, grad);
+  L.vf_lp = o; o += up256((size_t)(vb > dmg::MAX_BLOCKS ? vb : dmg::MAX_BLOCKS) * sizeof(double));
+  L.pg_part = o; if (grad) o += up256((size_t)pg_blocks((n + dmg::SB - 1) / dmg::SB, 0) * dmg::NPAD * sizeof(float));
+  L.vf_part = o; if (grad) o += up256((size_t)vb * dmv::NPAD * sizeof(float));
+  L.total = o;
+  return L;
+}
+extern "C" size_t dm_ppo_scratch_bytes(int32_t bs) {
+  if (bs < 1 || bs > INT32_MAX / dmg::AC) return 0;
+  return ppo_scratch_layout((int)bs, 1).total;
+}
+struct PpoRows { const float *ob, *ac, *atarg, *old_mean, *old_logstd, *ret; };
+// k_pg<PPO> and k_vf_grad_rows over rows idx[0 .. n) (or 0 .. n): partials and loss sums in scratch; -> the two grids
+static void ppo_grad_launch(const PpoRows& R, const int32_t* idx, int n, const float* theta, const float* rms_mean, const float* rms_std, float clip,
+                            int grad, const PpoScratch& L, void* scratch, hipStream_t st, int* pg_nblk, int* vf_nblk) {
+  char* base = (char*)scratch;
+  *pg_nblk = pg_blocks((n + dmg::SB - 1) / dmg::SB, 0);
+  *vf_nblk = ppo_vf_blocks(n, grad);
+  const dmg::BcArgs pa{idx, 0ull, 0ull, 0, grad, clip};
+  hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_PPO>, dim3(*pg_nblk), dim3(256), 0, st, R.ob, 1, n, R.ac, R.atarg, (float*)R.old_mean, R.old_logstd, 0, theta,
+                     (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, (float*)(base + L.pg_part), (double*)(base + L.pg_lp), pa);
+  if (grad)
+    hipLaunchKernelGGL(dmv::k_vf_grad_rows<true>, dim3(*vf_nblk), dim3(256), 0, st, R.ob, R.ret, idx, n, theta + dmg::NP, rms_mean, rms_std,
+                       (float*)(base + L.vf_part), (double*)(base + L.vf_lp));
+  else
+    hipLaunchKernelGGL(dmv::k_vf_grad_rows<false>, dim3(*vf_nblk), dim3(256), 0, st, R.ob, R.ret, idx, n, theta + dmg::NP, rms_mean, rms_std,
+                       (float*)nullptr, (double*)(base + L.vf_lp));
+}
+static bool ppo_rows_ok(const PpoRows& R) { return R.ob && R.ac && R.atarg && R.old_mean && R.old_logstd && R.ret; }
+extern "C" int dm_ppo_lossgrad(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
+                               const float* ret_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean, const float* rms_std,
+                               double clip, double entcoeff, float* out_grad, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
+  const PpoRows R{ob_all, ac_all, atarg_all, old_mean_all, old_logstd, ret_all};
+  if (!ppo_rows_ok(R) || !theta || !rms_mean || !rms_std || !out_loss || !scratch || n < 1 || n > INT32_MAX / dmg::AC || !aligned16(theta) ||
+      !std::isfinite(clip) || clip < 0.0 || !std::isfinite(entcoeff))
+    return fail(DM_EINVAL, "dm_ppo_lossgrad: bad argument");
+  const int grad = out_grad ? 1 : 0;
+  const PpoScratch L = ppo_scratch_layout((int)n, grad);
+  if (scratch_bytes < L.total) return fail(DM_EINVAL, "dm_ppo_lossgrad: scratch smaller than dm_ppo_scratch_bytes(n)");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_ppo_lossgrad: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_ppo_lossgrad: hipSetDevice failed");
+  hipStream_t st = (hipStream_t)hip_stream;
+  int pg_nblk, vf_nblk;
+  ppo_grad_launch(R, idx, (int)n, theta, rms_mean, rms_std, (float)clip, grad, L, scratch, st, &pg_nblk, &vf_nblk);
+  const char* base = (const char*)scratch;
+  hipLaunchKernelGGL(dmg::k_ppo_step, dim3(grad ? dmg::PPO_STEP_BLOCKS : 1), dim3(256), 0, st, (const float*)(base + L.pg_part),
+                     (const double*)(base + L.pg_lp), pg_nblk, (const float*)(base + L.vf_part), (const double*)(base + L.vf_lp), vf_nblk,
+                     1.0 / (double)n, (float)entcoeff, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.0f, 0.0f, 0.0f, 0.0f, out_grad, out_loss);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
+extern "C" int dm_ppo_fit(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
+                          const float* ret_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
+                          const float* step_scale_host, const float* clip_host, double beta1, double beta2, double eps, double entcoeff,
+                          const float* rms_mean, const float* rms_std, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
+  const PpoRows R{ob_all, ac_all, atarg_all, old_mean_all, old_logstd, ret_all};
+  if (!ppo_rows_ok(R) || !theta || !adam_m || !adam_v || !step_scale_host || !clip_host || !rms_mean || !rms_std || !out_loss || !scratch || iters < 1 ||
+      bs < 1 || bs > INT32_MAX / dmg::AC || !aligned16(theta) || !std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps) ||
+      !std::isfinite(entcoeff))
+    return fail(DM_EINVAL, "dm_ppo_fit: bad argument");
+  for (int i = 0; i < iters; i++)
+    if (!std::isfinite(step_scale_host[i]) || !std::isfinite(clip_host[i]) || clip_host[i] < 0.0f) return fail(DM_EINVAL, "dm_ppo_fit: bad step scale or clip");
+  const PpoScratch L = ppo_scratch_layout((int)bs, 1);
+  if (scratch_bytes < L.total) return fail(DM_EINVAL, "dm_ppo_fit: scratch smaller than dm_ppo_scratch_bytes(bs)");
+  if (!have_device()) return fail(DM_ENODEVICE, "dm_ppo_fit: no HIP device visible (libdmenv has no CPU path)");
+  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_ppo_fit: hipSetDevice failed");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const char* base = (const char*)scratch;
+  for (int i = 0; i < iters; i++) {
+    int pg_nblk, vf_nblk;
+    ppo_grad_launch(R, idx ? idx + (size_t)i * bs : nullptr, (int)bs, theta, rms_mean, rms_std, clip_host[i], 1, L, scratch, st, &pg_nblk, &vf_nblk);
+    hipLaunchKernelGGL(dmg::k_ppo_step, dim3(dmg::PPO_STEP_BLOCKS), dim3(256), 0, st, (const float*)(base + L.pg_part), (const double*)(base + L.pg_lp),
+                       pg_nblk, (const float*)(base + L.vf_part), (const double*)(base + L.vf_lp), vf_nblk, 1.0 / (double)bs, (float)entcoeff, theta,
+                       adam_m, adam_v, step_scale_host[i], (float)beta1, (float)beta2, (float)eps, (float*)nullptr, out_loss + (size_t)i * DM_PPO_NLOSS);
+  }
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
 extern "C" int dm_batch_redo_total(dm_batch* b, int64_t* out) {
   if (!b || !out) return fail(DM_EINVAL, "dm_batch_redo_total: null argument");
   HIPCHK(hipSetDevice(b->device));

@@ -152,7 +152,7 @@ __device__ inline void mlp_forward(MlpShared<IN>& S, Out out) {
 
 // Backward pass from S.dy = d loss / d output per sample (zero for samples past the end): the tile's partial gradient to out (NP floats, theta order).
 template <int IN>
-__device__ inline void mlp_backward(MlpShared<IN>& S, float* __restrict__ out) {
+__device__ __forceinline__ void mlp_backward(MlpShared<IN>& S, float* __restrict__ out) {
   using L = MlpShared<IN>;
   const int tid = threadIdx.x;
   // delta2 = dy w3 (1 - h2^2);  dw3, db3

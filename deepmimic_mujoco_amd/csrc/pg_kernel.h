@@ -23,12 +23,20 @@
 // or the mean with stochastic = 0.  Rows are gathered by idx from the expert's (ob, ac); the forward and reverse passes are the ones above, the
 // output gradient is G = 2 r / (28 n) with r = m + sigma eps - x, and d loss / d logstd_a = sum_s G sigma eps.  k_bc_adam sums the partials
 // like k_pg_reduce and takes the MpiAdam step on the policy's parameters: one BC iteration is two launches.
+//
+// PPO (MODE_PPO, the clipped surrogate of OpenAI baselines' ppo1 `pposgd_simple.learn`): rows gathered by idx from the whole segment's
+// (ob, ac, atarg, old_mean), old logstd beside them; ratio = exp(logp_new - logp_old), pol_surr = -mean(min(ratio A, clip(ratio, 1 +- eps) A)).
+// d pol_surr / d ratio = -A / n where ratio A <= clip(ratio) A (TF's `minimum` sends the gradient to its first argument on a tie), else 0:
+// the reverse pass is MODE_GRAD's with ratio atarg replaced by ratio * that coefficient.  lpart = {sum of -min(..), sum of KL(old || new),
+// rows with |ratio - 1| > eps, the entropy sum(logstd + 0.5 log(2 pi e))}.  The value net's half of the minibatch is k_vf_grad_rows
+// (vf_kernel.h); k_ppo_step sums both halves' partials and takes one MpiAdam step on both: one PPO minibatch is three launches.
 // fp32 like the reference's TF graph; loss sums leave the block in float64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mlp_tile.h"
 #include "rng.h"
+#include "vf_kernel.h"
 
 namespace dmg {
 using namespace dml;
@@ -39,7 +47,8 @@ constexpr int NPAD = (NP + 63) / 64 * 64;
 constexpr int NWT = (O_LS + 3) / 4 * 4 + 4;           // theta up to logstd, as float4s (the pad holds the first logstd entries: never used as a weight)
 constexpr int MAX_BLOCKS = 256;                       // one block per CU (LDS-limited)
 constexpr int ZR = OB + 2, MR = 32;                   // rows: z + {ones, zeros};  action rows padded to a tile
-enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_FVP = 2, MODE_BC = 3 };
+enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_FVP = 2, MODE_BC = 3, MODE_PPO = 4 };
+constexpr int PPO_LP = 4;                             // MODE_PPO's loss sums per block (the other modes: 2)
 static_assert(O_LS % 4 == 0 && NP >= NWT, "theta is copied to LDS as float4s");
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -59,8 +68,9 @@ static_assert(sizeof(PgShared) <= 160 * 1024, "PgShared must fit a CU's LDS");
 // operand reads past a buffer's rows (padded unit tiles) must stay inside the struct: the furthest is W3's row 127 as an A operand
 static_assert(O_W3 + 127 * AC + AC <= NWT + ZR * SBP, "padded W3 rows read into z");
 
-// what only MODE_BC reads: idx [n] rows of ob / ac (null: rows 0 .. n - 1), the noise's seed / counter, and whether to run the reverse pass
-struct BcArgs { const int* idx; unsigned long long seed, counter; int stochastic, grad; };
+// what only MODE_BC / MODE_PPO read: idx [n] rows of the inputs (null: rows 0 .. n - 1), the noise's seed / counter (BC), whether to run the
+// reverse pass, and PPO's clip range eps
+struct BcArgs { const int* idx; unsigned long long seed, counter; int stochastic, grad; float clip; };
 
 __device__ inline v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
@@ -68,6 +78,8 @@ __device__ inline v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_
 // old_logstd [28], old_mean [n, 28] — with write_old != 0 the kernel treats old == new and WRITES old_mean (src/trpo.py:247 assign_old_eq_new).
 // MODE_FVP: v = the direction (NP, in global memory).  partial: [gridDim.x][NPAD] f32 gradients; lpart: [gridDim.x][2] f64 (sum of ratio * atarg, sum of KL).
 // MODE_BC: ob [N, 56] / ac [N, 28] are the expert's, rows gathered by bc.idx; write_old = 1; inv_n = 1 / (28 n); lpart = {sum of r^2, 0}.
+// MODE_PPO: ob [N, 56], ac / old_mean [N, 28], atarg [N] (normalised), rows gathered by bc.idx; write_old = 0; inv_n = 1 / n;
+// lpart: [gridDim.x][PPO_LP] (see the top of the file).
 template <int MODE>
 __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int stride, int n, const float* __restrict__ ac, const float* __restrict__ atarg,
                                             float* __restrict__ old_mean, const float* __restrict__ old_logstd, int write_old,
@@ -102,7 +114,7 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
   v16f gW1[2], gW2[4], gW3;
 #pragma unroll
   for (int r = 0; r < 16; r++) { gW1[0][r] = 0.0f; gW1[1][r] = 0.0f; gW2[0][r] = 0.0f; gW2[1][r] = 0.0f; gW2[2][r] = 0.0f; gW2[3][r] = 0.0f; gW3[r] = 0.0f; }
-  double lsum0 = 0.0, lsum1 = 0.0;
+  double lsum0 = 0.0, lsum1 = 0.0, lsum2 = 0.0;
   const int ntiles = (n + SB - 1) / SB;
   // A tile's inputs are contiguous in memory (32 rows of ob / ac / old_mean): every thread fetches its share of the NEXT tile while the block
   // works on this one, and hands it to LDS (transposed) at the top of the loop.
@@ -124,6 +136,23 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
         const int i = tid + 256 * j, r = s0n + i / AC;
         acx[j] = (i < SB * AC && r < n) ? ac[(size_t)(bc.idx ? bc.idx[r] : r) * AC + i % AC] : 0.0f;
       }
+      return;
+    }
+    if constexpr (MODE == MODE_PPO) {                         // gathered rows of ob, ac, old_mean and atarg
+#pragma unroll
+      for (int j = 0; j < NZ; j++) {
+        const int i = tid + 256 * j, r = s0n + i / OB;
+        obx[j] = r < n ? ob[(size_t)(bc.idx ? bc.idx[r] : r) * OB + i % OB] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < NA; j++) {
+        const int i = tid + 256 * j, r = s0n + i / AC;
+        const bool ok = i < SB * AC && r < n;
+        const size_t row = ok ? (size_t)(bc.idx ? bc.idx[r] : r) : 0;
+        acx[j] = ok ? ac[row * AC + i % AC] : 0.0f;
+        omx[j] = ok ? old_mean[row * AC + i % AC] : 0.0f;
+      }
+      if (tid < SB) atx = s0n + tid < n ? atarg[bc.idx ? bc.idx[s0n + tid] : s0n + tid] : 0.0f;
       return;
     }
 #pragma unroll
@@ -289,7 +318,24 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
         for (int j = 0; j < NA; j++) { const int i = tid + 256 * j; if (i < SB * AC && s0g + i / AC < n) old_mean[(size_t)s0g * AC + i] = S.mo[i % AC][i / AC]; }
       }
       __syncthreads();
-      if (tid < SB) {
+      if constexpr (MODE == MODE_PPO) {
+        if (tid < SB) {
+          float d = 0.0f, kl = 0.0f;
+#pragma unroll
+          for (int g8 = 0; g8 < 8; g8++) { d += S.redp[g8][tid][0]; kl += S.redp[g8][tid][1]; }
+          const bool ok = s0g + tid < n;
+          const float ratio = __expf(d), A = S.at[tid];
+          const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, 1.0f - bc.clip), 1.0f + bc.clip) * A;
+          const bool first = s1 <= s2;                        // the branch of min() the gradient flows through
+          S.red[tid][0] = (ok && first) ? -ratio * A : 0.0f;  // ratio x d pol_surr / d ratio (times n): the reverse pass below
+          double b0 = ok ? -(double)(first ? s1 : s2) : 0.0, b1 = ok ? (double)kl : 0.0;
+          double b2 = (ok && fabsf(ratio - 1.0f) > bc.clip) ? 1.0 : 0.0;
+#pragma unroll
+          for (int o = 16; o >= 1; o >>= 1) { b0 += __shfl_xor(b0, o, 32); b1 += __shfl_xor(b1, o, 32); b2 += __shfl_xor(b2, o, 32); }
+          lsum0 += b0; lsum1 += b1; lsum2 += b2;
+        }
+        if (!bc.grad) continue;
+      } else if (tid < SB) {
         float d = 0.0f, kl = 0.0f;
 #pragma unroll
         for (int g8 = 0; g8 < 8; g8++) { d += S.redp[g8][tid][0]; kl += S.redp[g8][tid][1]; }
@@ -363,9 +409,17 @@ __global__ __launch_bounds__(256) void k_pg(const float* __restrict__ ob, int st
       for (int mt = 0; mt < 2; mt++) gW1[mt] = mfma32(S.z[32 * mt + li][2 * t + hf], b, gW1[mt]);
     }
   }
-  if (tid == 0) { lpart[2 * blockIdx.x] = lsum0; lpart[2 * blockIdx.x + 1] = lsum1; }
+  if constexpr (MODE == MODE_PPO) {
+    if (tid == 0) {
+      double ent = 0.0;                                       // DiagGaussianPd.entropy: state-independent
+      for (int a = 0; a < AC; a++) ent += (double)S.ls[a];
+      ent += AC * 1.4189385332046727;                         // 0.5 log(2 pi e) per action
+      double* lp = lpart + (size_t)PPO_LP * blockIdx.x;
+      lp[0] = lsum0; lp[1] = lsum1; lp[2] = lsum2; lp[3] = ent;
+    }
+  } else if (tid == 0) { lpart[2 * blockIdx.x] = lsum0; lpart[2 * blockIdx.x + 1] = lsum1; }
   if (MODE == MODE_LOSS) return;
-  if constexpr (MODE == MODE_BC) { if (!bc.grad) return; }
+  if constexpr (MODE == MODE_BC || MODE == MODE_PPO) { if (!bc.grad) return; }
   float* out = partial + (size_t)blockIdx.x * NPAD;
   const int col = u0 + li;
 #pragma unroll
@@ -419,6 +473,47 @@ __global__ __launch_bounds__(256) void k_bc_adam(const float* __restrict__ parti
   }
   if (p >= NP) return;
   const float g = column_sum<8>(partial, NPAD, p, 0, nblk);
+  const float mm = beta1 * m[p] + (1.0f - beta1) * g;
+  const float vv = beta2 * v[p] + (1.0f - beta2) * g * g;
+  m[p] = mm; v[p] = vv;
+  theta[p] += (-a) * mm / (sqrtf(vv) + eps);
+}
+
+// One PPO minibatch's reduction of both halves, and either the flat gradient (out_grad != null: dm_ppo_lossgrad) or the MpiAdam step on both
+// halves (dm_ppo_fit; one step count t for both, a = stepsize sqrt(1 - beta2^t) / (1 - beta1^t)).  Blocks 0 .. PPO_PG_BLOCKS - 1 take the policy's
+// NP parameters, the rest the value net's dmv::NP; theta / m / v / out_grad are [NP + dmv::NP] (the value half at offset NP).  Each parameter's
+// partials are summed in block order (column_sum), so a fit step equals dm_ppo_lossgrad's gradient + the host's Adam rule.  The entropy
+// penalty's gradient, -entcoeff, is added on logstd.  Thread 0 of block 0 writes out_loss [6] = {pol_surr, pol_entpen, vf_loss, kl, ent,
+// clipfrac} from the blocks' loss sums (in block order); theta == null and out_grad == null: the losses alone.
+constexpr int PPO_PG_BLOCKS = (NP + 255) / 256, PPO_STEP_BLOCKS = PPO_PG_BLOCKS + (dmv::NP + 255) / 256;
+__global__ __launch_bounds__(256) void k_ppo_step(const float* __restrict__ pg_partial, const double* __restrict__ pg_lpart, int pg_nblk,
+                                                  const float* __restrict__ vf_partial, const double* __restrict__ vf_lpart, int vf_nblk, double inv_n,
+                                                  float entcoeff, float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v, float a,
+                                                  float beta1, float beta2, float eps, float* __restrict__ out_grad, double* __restrict__ out_loss) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b == 0 && tid == 0) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, sv = 0.0;
+    for (int k = 0; k < pg_nblk; k++) { s0 += pg_lpart[PPO_LP * k]; s1 += pg_lpart[PPO_LP * k + 1]; s2 += pg_lpart[PPO_LP * k + 2]; }
+    for (int k = 0; k < vf_nblk; k++) sv += vf_lpart[k];
+    const double ent = pg_lpart[3];
+    out_loss[0] = s0 * inv_n; out_loss[1] = -(double)entcoeff * ent; out_loss[2] = sv * inv_n;
+    out_loss[3] = s1 * inv_n; out_loss[4] = ent; out_loss[5] = s2 * inv_n;
+  }
+  if (!theta && !out_grad) return;
+  int p;
+  float g;
+  if (b < PPO_PG_BLOCKS) {
+    p = b * 256 + tid;
+    if (p >= NP) return;
+    g = column_sum<8>(pg_partial, NPAD, p, 0, pg_nblk);
+    if (p >= O_LS) g += -entcoeff;
+  } else {
+    const int q = (b - PPO_PG_BLOCKS) * 256 + tid;
+    if (q >= dmv::NP) return;
+    g = column_sum<8>(vf_partial, dmv::NPAD, q, 0, vf_nblk);
+    p = NP + q;
+  }
+  if (out_grad) { out_grad[p] = g; return; }
   const float mm = beta1 * m[p] + (1.0f - beta1) * g;
   const float vv = beta2 * v[p] + (1.0f - beta2) * g * g;
   m[p] = mm; v[p] = vv;

@@ -104,6 +104,56 @@ __global__ __launch_bounds__(256) void k_vf_grad(const float* __restrict__ ob, c
   mlp_backward(S, partial + (size_t)blockIdx.x * NPAD);
 }
 
+// ---- PPO's value half: k_vf_grad on rows gathered by idx, with the loss -------------------------------------------------------------
+// loss = mean over the n rows of (vpred - ret)^2 (ppo1's vf_loss); rows idx[0 .. n) of ob_all / ret_all (null idx: rows 0 .. n - 1).
+// lpart[blockIdx.x] = the block's sum of squared errors, in float64 (a butterfly over each tile's 32 samples).  GRAD: one tile per block
+// (grid = the tiles), its partial gradient to partial + blockIdx.x * NPAD as k_vf_grad writes it; !GRAD: any grid, a block walks the tiles
+// blockIdx.x, + gridDim.x, ... and writes the loss alone.
+template <bool GRAD>
+__global__ __launch_bounds__(256) void k_vf_grad_rows(const float* __restrict__ ob_all, const float* __restrict__ ret_all, const int* __restrict__ idx,
+                                                      int n, const float* __restrict__ theta, const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                      float* __restrict__ partial, double* __restrict__ lpart) {
+  __shared__ VfShared S;
+  const int tid = threadIdx.x, ntiles = (n + SB - 1) / SB;
+  constexpr int NZ = SB * OB / 256;
+  double lsum = 0.0;
+  auto run_tile = [&](int tile) {
+    const int s0 = tile * SB;
+    float x[NZ], mu[NZ], sd[NZ];
+#pragma unroll
+    for (int j = 0; j < NZ; j++) {
+      const int i = tid + 256 * j, sm = i / OB, k = i % OB, r = s0 + sm;
+      x[j] = r < n ? ob_all[(size_t)(idx ? idx[r] : r) * OB + k] : 0.0f; mu[j] = mean[k]; sd[j] = stdv[k];
+    }
+    mlp_stage(S, theta, [&] {
+#pragma unroll
+      for (int j = 0; j < NZ; j++) {
+        const int i = tid + 256 * j, sm = i / OB, k = i % OB;
+        S.z[k][sm] = (s0 + sm < n) ? fminf(fmaxf((x[j] - mu[j]) / sd[j], -5.0f), 5.0f) : 0.0f;
+      }
+    });
+    mlp_forward(S, [&](int sm, float v) {                     // threads 0 .. 31: one sample each
+      const int r = s0 + sm;
+      const float e = r < n ? v - ret_all[idx ? idx[r] : r] : 0.0f;
+      S.dy[sm] = 2.0f * e / (float)n;
+      double q = (double)e * (double)e;
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o, 32);
+      lsum += q;
+    });
+  };
+  if constexpr (GRAD) {
+    run_tile(blockIdx.x);
+    mlp_backward(S, partial + (size_t)blockIdx.x * NPAD);
+  } else {
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+      run_tile(tile);
+      __syncthreads();                                        // this tile's readers are done before the next one zeroes the pads
+    }
+  }
+  if (tid == 0) lpart[blockIdx.x] = lsum;
+}
+
 // ---- gradient reduction + MpiAdam step (src/mpi_adam.py:21-35): the summation tree of quarter_sum (mlp_tile.h) ---------------------
 constexpr int ADAM_PARAMS = QCOLS;
 __global__ __launch_bounds__(256) void k_vf_adam(const float* __restrict__ partial, int nblk, float* __restrict__ theta, float* __restrict__ m,

@@ -268,7 +268,7 @@ class ExpertDataset:
 
 def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4, timesteps_per_batch=1024, max_iters=0, max_timesteps=0,
           max_seconds=0, entcoeff=0.0, max_kl=0.01, cg_iters=10, cg_damping=0.1, gamma=0.995, lam=0.97, vf_iters=5, vf_stepsize=1e-3,
-          callback=None, log=print, group=None, log_dir=None, fused=None, seed=0, **learner_kwargs):
+          callback=None, log=print, group=None, log_dir=None, fused=None, seed=0, algo="trpo", ppo_kwargs=None, **learner_kwargs):
     """`learn()` of src/gail.py:112-343 (hyper-parameters as its `train()` passes them) over a DPVecEnv (autoreset="init") and an MlpPolicy.
     One iteration: g_step times a segment rewarded by `reward_giver` and a TRPO update on it (trpo.TrpoLearner), then the D update on the
     LAST segment's (ob, ac): one `expert.get_next_batch(len(ob))` whose result is dropped, then for each of the d_step minibatches of
@@ -276,12 +276,22 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
     size, the adversary's filter updated with both, the loss gradient all-mean'd into MpiAdam(d_stepsize).
     Episode statistics come from the last segment as in the reference (:345-357): EpRewMean averages D's returns, EpTrueRewMean the env's;
     TimestepsSoFar adds the lengths of the episodes that ended (:361).  Stops after max_iters iterations, max_timesteps or max_seconds.
-    With `log_dir`, rank 0 writes progress.csv and monitor.csv (the env's returns of every finished episode) as trpo.learn does."""
+    With `log_dir`, rank 0 writes progress.csv and monitor.csv (the env's returns of every finished episode) as trpo.learn does.
+    algo="ppo" (the reference's --algo, src/gail.py:394): the G updates are ppo.PpoLearner's, with gamma, lam, entcoeff, seed and `ppo_kwargs`
+    (its linear schedule over max_timesteps when that is the stopping rule, else a constant one); the TRPO arguments are then unused."""
     import torch.distributed as dist
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     from .rollout import can_fuse, traj_segment_generator
-    learner = TrpoLearner(pi, max_kl=max_kl, cg_iters=cg_iters, cg_damping=cg_damping, gamma=gamma, lam=lam, entcoeff=entcoeff,
-                          vf_iters=vf_iters, vf_stepsize=vf_stepsize, group=group, seed=seed, **learner_kwargs)
+    if algo == "trpo":
+        learner = TrpoLearner(pi, max_kl=max_kl, cg_iters=cg_iters, cg_damping=cg_damping, gamma=gamma, lam=lam, entcoeff=entcoeff,
+                              vf_iters=vf_iters, vf_stepsize=vf_stepsize, group=group, seed=seed, **learner_kwargs)
+    elif algo == "ppo":
+        from .ppo import PpoLearner
+        kw = dict(schedule="linear" if max_timesteps else "constant", max_timesteps=max_timesteps)
+        kw.update(ppo_kwargs or {})
+        learner = PpoLearner(pi, gamma=gamma, lam=lam, entcoeff=entcoeff, group=group, seed=seed, **kw)
+    else:
+        raise ValueError("algo must be 'trpo' or 'ppo'")
     d_adam = MpiAdam(reward_giver.get_trainable_variables(), group=group)
     d_adam.sync()
     use_fused = can_fuse(pi, env) if fused is None else bool(fused)
@@ -319,6 +329,7 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
         segs = []
         for _ in range(g_step):
             seg = next(seg_gen)
+            learner.timesteps_so_far = timesteps_so_far                 # (PPO's schedule)
             stats = learner.update(seg)
             segs.append(seg)
         # ---- update D (:328-343) ----

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 6
+#define DM_ABI_VERSION 7
 
 /* fixed sizes of the DeepMimic humanoid (dp_env_v3.xml:21-156): the kernels are specialised to this tree */
 #define DM_NBODY 14
@@ -368,6 +368,40 @@ int dm_bc_lossgrad(const float* ob_all, const float* ac_all, const int32_t* idx,
 int dm_bc_fit(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
               const float* step_scale_host, double beta1, double beta2, double eps, const float* rms_mean, const float* rms_std, int32_t stochastic,
               uint64_t seed, uint64_t counter0, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream);
+
+/* PPO's clipped-surrogate update (OpenAI baselines' ppo1 `pposgd_simple.learn`, whose policy file the reference trains: src/mlp_policy_trpo.py;
+ * the reference's --algo ppo, src/gail.py:394) for the 56-100-100-28 policy and the 56-100-100-1 value net of src/mlp_policy_trpo.py together.
+ * theta (and adam_m / adam_v): [dm_pg_param_count() + dm_vf_param_count()] float32 = the policy's dm_pg_* flat order, then the value net's
+ * dm_vf_* order (vffc1/w, vffc1/b, vffc2/w, vffc2/b, vffinal/w, vffinal/b), 16-byte aligned.  The segment's rows: ob_all [N, 56],
+ * ac_all [N, 28], atarg_all [N] (already normalised: (adv - mean) / std), old_mean_all [N, 28] (the old policy's means, e.g. written by
+ * dm_pg_losses with write_old = 1), ret_all [N] (tdlamret), old_logstd [28]; all float32.  Rows are gathered by idx, which is NOT checked:
+ * every entry must lie in 0 .. N - 1 (a null idx takes rows 0 .. n - 1, resp. 0 .. bs - 1 every minibatch).  rms_mean / rms_std [56]: the
+ * obs filter, read and never updated (ppo1 updates it once per segment, before the epochs: dm_rms_update).  With ratio = exp(logp_new -
+ * logp_old) and A = atarg, a minibatch's losses (out_loss, DM_PPO_NLOSS float64 each) are
+ *     pol_surr = -mean(min(ratio A, clip(ratio, 1 - clip, 1 + clip) A)),  pol_entpen = -entcoeff * ent,  vf_loss = mean((vpred - ret)^2),
+ *     kl = mean KL(old || new),  ent = entropy of the policy (state-independent),  clipfrac = fraction of rows with |ratio - 1| > clip;
+ * the gradient is that of pol_surr + pol_entpen + vf_loss, d pol_surr / d ratio = -A / n where ratio A <= clip(ratio) A, else 0.
+ * Every pointer but step_scale_host / clip_host is a DEVICE pointer on one device; the work is enqueued on `hip_stream`; no device visible
+ * -> DM_ENODEVICE.  Sums are taken in a fixed order: two calls with the same inputs give bitwise-identical results.
+ *   dm_ppo_scratch_bytes  scratch both calls need for a minibatch of bs rows (0 for bs < 1).  A losses-only dm_ppo_lossgrad (out_grad null)
+ *                         of any n needs no more than dm_ppo_scratch_bytes(1).
+ *   dm_ppo_lossgrad       Replaces: `lossandgrad(ob, ac, atarg, tdlamret, cur_lrmult)` of one minibatch (and, with out_grad null,
+ *                         `compute_losses`): out_loss [DM_PPO_NLOSS] and, unless out_grad is null, out_grad [dm_pg_param_count() +
+ *                         dm_vf_param_count()] float32 = the flat gradient of both nets.  The multi-process path: MpiAdam all-means it.
+ *   dm_ppo_fit            Replaces: `iters` minibatches of `lossandgrad` + `adam.update(g, optim_stepsize * cur_lrmult)` (MpiAdam(epsilon =
+ *                         adam_epsilon) over both nets, one process): minibatch i takes rows idx[i * bs .. (i + 1) * bs), the clip range
+ *                         clip_host[i] and the Adam scale step_scale_host[i] (both on the HOST; a_t = stepsize sqrt(1 - beta2^t) / (1 - beta1^t)),
+ *                         and steps theta, adam_m, adam_v in place; out_loss [iters, DM_PPO_NLOSS] = each minibatch's losses before its step.
+ *                         Three launches per minibatch (policy gradient, value gradient, reduction + step); nothing comes back to the host. */
+#define DM_PPO_NLOSS 6
+size_t dm_ppo_scratch_bytes(int32_t bs);
+int dm_ppo_lossgrad(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
+                    const float* ret_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean, const float* rms_std,
+                    double clip, double entcoeff, float* out_grad, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dm_ppo_fit(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
+               const float* ret_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
+               const float* step_scale_host, const float* clip_host, double beta1, double beta2, double eps, double entcoeff,
+               const float* rms_mean, const float* rms_std, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream);
 
 /* Diagnostics of DM_OPT_PACKED (four environments per wavefront, csrc/slot_kernel.h): env-steps so far that exceeded a capacity of that
  * path (DM_PACKED_*: rows, contacts / contact pairs, pairs past the bounding spheres, box staging slots; or a PGS step the cost test would

@@ -10,6 +10,7 @@
 <save without .npz>.adversary.npz.
 --pretrained clones the expert first (src/gail.py:490-495, behavior_clone.learn: --BC-max-iter Adam iterations of 128 transitions) and GAIL
 starts from that policy; --bc-save writes the cloned policy (x.npz or a checkpoint prefix) for train_trpo.py --task evaluate.
+--algo ppo updates the policy with PPO (deepmimic_mujoco_amd.ppo) instead of TRPO.
 """
 import argparse
 import json
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--policy-entcoeff", type=float, default=0.0)
     ap.add_argument("--d-stepsize", type=float, default=3e-4)
     ap.add_argument("--max-kl", type=float, default=0.01)
+    ap.add_argument("--algo", default="trpo", choices=["trpo", "ppo"], help="the policy's learner (the reference's --algo); ppo: ppo1's defaults")
     ap.add_argument("--task", default="train", choices=["train", "evaluate", "sample"])
     ap.add_argument("--load-model-path", default=None, help="evaluate / sample: a tf.train.Saver checkpoint prefix or an .npz")
     ap.add_argument("--number-trajs", type=int, default=10)
@@ -83,7 +85,7 @@ def main():
     reward_giver = TransitionClassifier(hidden_size=args.adversary_hidden_size, entcoeff=args.adversary_entcoeff, device=dev, seed=args.seed)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     hist = learn(env, pi, reward_giver, expert, g_step=args.g_step, d_step=args.d_step, d_stepsize=args.d_stepsize, timesteps_per_batch=args.horizon,
-                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, **stop)
+                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, algo=args.algo, **stop)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump({"args": vars(args), "history": hist}, open(args.out, "w"))
