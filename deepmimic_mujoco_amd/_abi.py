@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 NBODY, NJNT, NQ, NV, NU, NGEOM, NOBS, MAXEFC = 14, 29, 35, 34, 28, 16, 56, 64
 DEBUG_DOUBLES = 34 * 34 + 34 * 3 + 42 + 3 + MAXEFC * (34 + 6)
 PTR_HOST, PTR_DEVICE = 0, 1
@@ -54,6 +54,17 @@ class ModelDesc(C.Structure):
     ]
 
 
+class RenderDesc(C.Structure):
+    """include/dmenv.h dm_render_desc (built by render.make_desc)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("track_com", C.c_int32),
+        ("cam_pos", C.c_double * 3), ("cam_mat", C.c_double * 9), ("fovy", C.c_double),
+        ("geom_rgb", (C.c_double * 3) * NGEOM), ("floor_rgb1", C.c_double * 3), ("floor_rgb2", C.c_double * 3), ("floor_square", C.c_double),
+        ("sky_top", C.c_double * 3), ("sky_bottom", C.c_double * 3), ("light_dir", C.c_double * 3),
+        ("ambient", C.c_double), ("headlight", C.c_double), ("diffuse", C.c_double),
+    ]
+
+
 def make_model_desc(cm):
     """Fill a ModelDesc from a `model.CompiledModel`; returns (desc, keepalive list of arrays)."""
     keep = []
@@ -95,7 +106,7 @@ LIB_PATH = os.environ.get("DMENV_LIB") or os.path.join(_HERE, "csrc", "libdmenv.
 EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_destroy", "dm_batch_create",
            "dm_batch_destroy", "dm_batch_set_stream", "dm_batch_set_option", "dm_batch_set_state", "dm_batch_reset",
            "dm_batch_step", "dm_batch_get_obs", "dm_batch_get", "dm_batch_set", "dm_batch_debug_forward",
-           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_last_error", "dm_abi_version", "dm_real_bits",
+           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_last_error", "dm_abi_version", "dm_real_bits",
            "dm_device_count"]
 _LIB = None
 
@@ -166,6 +177,7 @@ def load(dtype=64):
     L.dm_ppo_lossgrad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, C.c_size_t, vp]
     L.dm_ppo_fit.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double,
                              C.c_double, C.c_double, vp, vp, vp, vp, C.c_size_t, vp]
+    L.dm_batch_render.argtypes = [vp, vp, vp, i32, C.POINTER(RenderDesc), vp, vp, vp, vp, i32]
     L.dm_episode_scan.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]
     if L.dm_abi_version() != ABI_VERSION:
         raise DmenvError("libdmenv.so ABI version %d != %d" % (L.dm_abi_version(), ABI_VERSION))

@@ -23,6 +23,7 @@ class Batch(object):
         self._L = L
         self.n = int(n_envs)
         self.device = int(device)
+        self.compiled_model = compiled_model
         md, self._keep = A.make_model_desc(compiled_model)
         self._model = C.c_void_p(); self._mocap = C.c_void_p(); self._h = C.c_void_p()
         A.check(L.dm_model_create(C.byref(md), C.byref(self._model)), L)
@@ -63,7 +64,7 @@ class Batch(object):
             return None, A.PTR_HOST, None
         if _is_torch(x):
             import torch
-            want = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}[dtype]
+            want = {np.float64: torch.float64, np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}[dtype]
             if x.dtype != want or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
                 raise ValueError("tensor must be contiguous %s of shape %s" % (want, shape))
             if x.device.type != "cuda" or (x.device.index or 0) != self.device:
@@ -275,6 +276,70 @@ class Batch(object):
         p, kind, _ = self._ptr(out, np.float64, (self.n, A.NOBS), out=True)
         A.check(self._L.dm_batch_get_obs(self._h, p, kind), self._L)
         return out
+
+    def render(self, width, height, camera="side", qpos=None, env_ids=None, depth=False, segmentation=False, out=None, visual=None,
+               rgb=True, geom_xform=False):
+        """Images of environment states through dm_batch_render.  camera: a model camera's name or a
+        render.FreeCamera; qpos [n,35]: render these poses instead of the batch's state (env_ids must then be None); env_ids [n]:
+        a subset of the batch's environments (default: all).  Returns a dict with "rgb" uint8 [n,H,W,3] and, when asked,
+        "depth" float32 [n,H,W], "segmentation" int32 [n,H,W], "geom_xform" float64 [n,16,12].  out: a dict of buffers under
+        the same keys; like `step`, numpy arrays (host) or torch tensors on the batch's device (stream-ordered, no host wait)."""
+        from . import render as R
+        want = [k for k, on in (("rgb", rgb), ("depth", depth), ("segmentation", segmentation), ("geom_xform", geom_xform)) if on]
+        if not want:
+            raise ValueError("nothing to render")
+        if qpos is not None and env_ids is not None:
+            raise ValueError("qpos and env_ids exclude each other")
+        if qpos is not None:
+            n = int(qpos.shape[0])
+        elif env_ids is not None:
+            n = int(len(env_ids))
+        else:
+            n = self.n
+        W, H = int(width), int(height)
+        spec = {"rgb": (np.uint8, (n, H, W, 3)), "depth": (np.float32, (n, H, W)), "segmentation": (np.int32, (n, H, W)),
+                "geom_xform": (np.float64, (n, A.NGEOM, 12))}
+        out = dict(out or {})
+        device = any(_is_torch(v) for v in list(out.values()) + [qpos, env_ids])
+        for k in want:
+            if k not in out:
+                if device:
+                    import torch
+                    out[k] = torch.empty(spec[k][1], dtype={np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32,
+                                                            np.float64: torch.float64}[spec[k][0]], device="cuda:%d" % self.device)
+                else:
+                    out[k] = np.empty(spec[k][1], dtype=spec[k][0])
+        if device:
+            import torch
+            if qpos is not None and not _is_torch(qpos):
+                qpos = torch.as_tensor(np.ascontiguousarray(qpos, dtype=np.float64), device="cuda:%d" % self.device)
+            if env_ids is not None and not _is_torch(env_ids):
+                env_ids = torch.as_tensor(np.ascontiguousarray(env_ids, dtype=np.int32), device="cuda:%d" % self.device)
+        ptrs, kinds, keep = {}, set(), []
+        for k in ("rgb", "depth", "segmentation", "geom_xform"):
+            if k in want:
+                p, kind, ka = self._ptr(out[k], spec[k][0], spec[k][1], out=True)
+                ptrs[k] = p; kinds.add(kind); keep.append(ka)
+            else:
+                ptrs[k] = None
+        qp, kq, ka = self._ptr(qpos, np.float64, (n, A.NQ)); keep.append(ka)
+        ip, ki, ka = self._ptr(env_ids, np.int32, (n,)); keep.append(ka)
+        if qpos is not None:
+            kinds.add(kq)
+        if env_ids is not None:
+            kinds.add(ki)
+        if len(kinds) != 1:
+            raise ValueError("render buffers must be all numpy arrays or all device tensors")
+        key = (W, H, camera, id(visual)) if isinstance(camera, str) else None      # (model cameras: resolved once per size and visual table)
+        cache = self.__dict__.setdefault("_render_descs", {})
+        desc = cache[key][0] if key in cache else None
+        if desc is None:
+            desc = R.make_desc(self.compiled_model, W, H, camera, visual)
+            if key is not None:
+                cache[key] = (desc, visual)          # (holding `visual` keeps its id from being reused)
+        A.check(self._L.dm_batch_render(self._h, qp, ip, n, C.byref(desc), ptrs["rgb"], ptrs["depth"], ptrs["segmentation"],
+                                        ptrs["geom_xform"], kinds.pop()), self._L)
+        return {k: out[k] for k in want}
 
     def set_state(self, qpos, qvel, frame_idx=None, mask=None):
         n = self.n

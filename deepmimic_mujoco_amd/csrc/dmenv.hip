@@ -20,6 +20,7 @@
 #include "model_host.h"
 
 using namespace dm;
+#include "render_kernel.h"     // (written against namespace dm, like the kernels below)
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
               DM_PACKED_MAXCAND == SLOT_MAXCAND, "include/dmenv.h documents the packed path's capacities: keep it in step with slot_kernel.h");
 // ============================================ kernels ======================================================
@@ -247,6 +248,8 @@ struct dm_batch {
   bool timing = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; float last_ms = 0.f; bool ev_pending = false;
   // pipelined sub-batches (DM_OPT_PIPELINE): the env range is cut into `pipe` contiguous parts, each stepped on its own stream
   int pipe = 1; hipStream_t ps[DM_MAX_PIPELINE] = {}; hipEvent_t ev_in = nullptr, ev_done[DM_MAX_PIPELINE] = {}; bool pipe_pending = false;
+  // dm_batch_render: view records and the staging of host arrays, grown on demand
+  unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
 };
 // make the batch's stream wait for every sub-batch launch still in flight (no host wait)
 static int pipe_join(dm_batch* b) {
@@ -310,7 +313,7 @@ extern "C" void dm_batch_destroy(dm_batch* b) {
   if (b->ev_in) hipEventDestroy(b->ev_in);
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
@@ -804,6 +807,84 @@ extern "C" int dm_batch_debug_forward(dm_batch* b, int32_t env, double* out_host
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out_host, b->d_debug, DM_DEBUG_DOUBLES * 8, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
+  return DM_OK;
+}
+
+// ------------------------------------------------------------------ rendering (render_kernel.h)
+extern "C" int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, const dm_render_desc* d, uint8_t* rgb,
+                               float* depth, int32_t* seg, double* geom_xform, int32_t kind) {
+  if (!b || !d) return fail(DM_EINVAL, "dm_batch_render: null argument");
+  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_render: bad ptr_kind");
+  if (n <= 0) return fail(DM_EINVAL, "dm_batch_render: n must be positive");
+  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_render: env_ids must be NULL when qpos is given");
+  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_render: n exceeds the batch size");
+  const int W = d->width, H = d->height;
+  if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(DM_EINVAL, "dm_batch_render: width and height must be 1..4096");
+  const size_t npix = (size_t)n * W * H;
+  if (npix >= (size_t)1 << 31) return fail(DM_EINVAL, "dm_batch_render: n * width * height must stay below 2^31");
+  if (!(d->fovy > 0 && d->fovy < 180)) return fail(DM_EINVAL, "dm_batch_render: fovy must lie in (0, 180) degrees");
+  if (!rgb && !depth && !seg && !geom_xform) return fail(DM_EINVAL, "dm_batch_render: no output requested");
+  const double ln = std::sqrt(d->light_dir[0] * d->light_dir[0] + d->light_dir[1] * d->light_dir[1] + d->light_dir[2] * d->light_dir[2]);
+  if (!(ln > 0)) return fail(DM_EINVAL, "dm_batch_render: light_dir must be nonzero");
+  if (!(d->floor_square > 0)) return fail(DM_EINVAL, "dm_batch_render: floor_square must be positive");
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  const bool host = kind == DM_PTR_HOST;
+  // scratch: records | qpos | env ids | (host outputs) rgb | depth | seg | xform
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  const size_t o_rec = take((size_t)n * sizeof(dmr::ViewRec));
+  const size_t o_q = host && qpos ? take((size_t)n * NQ * sizeof(double)) : 0;
+  const size_t o_id = host && env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
+  const size_t o_rgb = host && rgb ? take(npix * 3) : 0;
+  const size_t o_dep = host && depth ? take(npix * sizeof(float)) : 0;
+  const size_t o_seg = host && seg ? take(npix * sizeof(int32_t)) : 0;
+  const size_t o_xf = host && geom_xform ? take((size_t)n * NG * 12 * sizeof(double)) : 0;
+  if (off > b->rbuf_bytes) {
+    HIPCHK(hipStreamSynchronize(b->stream));       // (the old buffer may still be read by an earlier render)
+    if (b->d_rbuf) { HIPCHK(hipFree(b->d_rbuf)); b->d_rbuf = nullptr; b->rbuf_bytes = 0; }
+    if (hipMalloc((void**)&b->d_rbuf, off) != hipSuccess) { (void)hipGetLastError(); return fail(DM_ENOMEM, "dm_batch_render: hipMalloc failed"); }
+    b->rbuf_bytes = off;
+  }
+  unsigned char* base = b->d_rbuf;
+  // env ids are checked on the host (device ids are read back first)
+  if (env_ids) {
+    std::vector<int32_t> ids((size_t)n);
+    if (host) std::memcpy(ids.data(), env_ids, (size_t)n * sizeof(int32_t));
+    else { HIPCHK(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
+    for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= b->n) return fail(DM_EINVAL, "dm_batch_render: env id out of range");
+  }
+  const double* q = qpos;
+  const int32_t* ids = env_ids;
+  if (host && qpos) { HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q); }
+  if (host && env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
+  unsigned char* drgb = host && rgb ? base + o_rgb : rgb;
+  float* ddep = host && depth ? (float*)(base + o_dep) : depth;
+  int32_t* dseg = host && seg ? (int32_t*)(base + o_seg) : seg;
+  double* dxf = host && geom_xform ? (double*)(base + o_xf) : geom_xform;
+  dmr::ViewRec* rec = (dmr::ViewRec*)(base + o_rec);
+  dmr::Camera cam{};
+  for (int k = 0; k < 3; k++) cam.pos[k] = d->cam_pos[k];
+  for (int k = 0; k < 9; k++) cam.mat[k] = d->cam_mat[k];
+  cam.track_com = d->track_com != 0;
+  hipLaunchKernelGGL(k_render_pose, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, q, (const int*)ids, cam, rec, dxf);
+  HIPCHK(hipGetLastError());
+  if (drgb || ddep || dseg) {
+    const dmr::Params P = dmr::make_params(*d);
+    const int tiles_x = (W + 15) / 16, tiles = tiles_x * ((H + 15) / 16);
+    for (int v0 = 0; v0 < n; v0 += 65535) {
+      const int nv = n - v0 < 65535 ? n - v0 : 65535;
+      hipLaunchKernelGGL(k_render_rays, dim3(tiles, nv), dim3(256), 0, b->stream, (const dmr::ViewRec*)rec, P, tiles_x, v0, drgb, ddep, (int*)dseg);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (host) {
+    if (rgb) HIPCHK(hipMemcpyAsync(rgb, drgb, npix * 3, hipMemcpyDeviceToHost, b->stream));
+    if (depth) HIPCHK(hipMemcpyAsync(depth, ddep, npix * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    if (seg) HIPCHK(hipMemcpyAsync(seg, dseg, npix * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    if (geom_xform) HIPCHK(hipMemcpyAsync(geom_xform, dxf, (size_t)n * NG * 12 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
   return DM_OK;
 }
 

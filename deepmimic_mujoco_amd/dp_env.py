@@ -26,8 +26,8 @@ import numpy as np
 from . import _abi as A
 from .batch import Batch
 from .config import Config
-from .humanoid import humanoid_spec
-from .mjcf import load_mjcf
+from .humanoid import humanoid_spec, humanoid_visual
+from .mjcf import load_mjcf, load_visual
 from .mocap import MocapDM
 from .model import CompiledModel
 from .spaces import Box
@@ -44,6 +44,19 @@ def _load_model(xml_path=None, explicit=True):
     if xml_path and explicit:
         raise FileNotFoundError("model file %r does not exist" % (xml_path,))
     return CompiledModel(humanoid_spec())
+
+
+def _load_visual(xml_path=None):
+    """the rendering description that goes with `_load_model(xml_path)`"""
+    import os
+    if xml_path and os.path.isfile(xml_path):
+        return load_visual(xml_path)
+    return humanoid_visual()
+
+
+def _camera(camera_name):
+    from .render import DEFAULT_CAMERA
+    return DEFAULT_CAMERA if camera_name is None else camera_name
 
 
 class _Opt(object):
@@ -95,13 +108,14 @@ class _SimView(object):
 
 
 class DPEnv(object):
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array", "depth_array"]}
     reward_range = (-float("inf"), float("inf"))
     spec = None
 
     def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None):
         self.mocap = MocapDM()
         self._cm = _load_model(xml_path if xml_path is not None else Config.xml_path, explicit=xml_path is not None)
+        self._visual = _load_visual(xml_path if xml_path is not None else Config.xml_path)
         self.model = _ModelView(self._cm)
         self._device = device
         self._batch_factory = batch_factory or (lambda cm, cfg, vel, n, dt: Batch(cm, cfg, vel, n, device=device, mocap_dt=dt))
@@ -146,8 +160,16 @@ class DPEnv(object):
         if self._batch is not None:
             self._batch.close(); self._batch = None
 
-    def render(self, mode="human"):
-        raise NotImplementedError("rendering is outside the accelerated path")
+    def render(self, mode="human", width=500, height=500, camera_name=None):
+        """gym MujocoEnv.render: "rgb_array" -> uint8 [height, width, 3], "depth_array" -> float32 [height, width] (distance
+        along the optical axis, metres; +inf where nothing is hit), ray-cast by dm_batch_render from a model camera
+        (camera_name: "side" (default) or "back", dp_env_v3.xml:23-24) or a render.FreeCamera.  There is no display: "human"
+        raises NotImplementedError."""
+        if mode not in self.metadata["render.modes"]:
+            raise NotImplementedError("render mode %r: no display here; modes are %s" % (mode, self.metadata["render.modes"]))
+        depth = mode == "depth_array"
+        r = self._batch.render(width, height, _camera(camera_name), depth=depth, rgb=not depth, visual=self._visual)
+        return r["depth"][0] if depth else r["rgb"][0]
 
     def viewer_setup(self):
         pass
@@ -330,6 +352,7 @@ class DPVecEnv(object):
         self.mocap_dt = self.mocap.dt
         self.mocap_data_len = len(self.mocap.data)
         self._cm = _load_model(xml_path)
+        self._visual = _load_visual(xml_path)
         self.model = _ModelView(self._cm)
         flags = (0 if contacts else A.FLAG_NO_CONTACT) | (0 if limits else A.FLAG_NO_LIMIT)
         per_frame = max(1, int(float(self.mocap_dt) / float(self._cm.timestep)))
@@ -418,6 +441,19 @@ class DPVecEnv(object):
     def step(self, actions, out=None):
         self.step_async(actions)
         return self.step_wait(out)
+
+    metadata = {"render.modes": ["rgb_array"]}
+
+    def get_images(self, width=128, height=128, camera_name=None):
+        """baselines VecEnv.get_images: uint8 [N, height, width, 3], one image per environment (dm_batch_render)"""
+        return self._batch.render(width, height, _camera(camera_name), visual=self._visual)["rgb"]
+
+    def render(self, mode="rgb_array", width=128, height=128, camera_name=None):
+        """baselines VecEnv.render: the environments' images tiled into one (render.tile_images); "human" raises"""
+        if mode != "rgb_array":
+            raise NotImplementedError("render mode %r: no display here; the mode is 'rgb_array'" % (mode,))
+        from .render import tile_images
+        return tile_images(self.get_images(width, height, camera_name))
 
     def close(self):
         self._batch.close()

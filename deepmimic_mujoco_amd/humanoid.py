@@ -90,3 +90,23 @@ def humanoid_spec():
         base = j["name"][:-2] if j["name"][-2:] in ("_x", "_y", "_z") else j["name"]
         motors.append(dict(name=j["name"], joint=ji, gear=float(gears[base]), ctrlrange=(-0.5, 0.5)))
     return dict(option=opt, bodies=bodies, joints=joints, geoms=geoms, motors=motors, excludes=excludes)
+
+
+# MuJoCo 2.0 visual defaults the XML does not override (EXTERNAL: MuJoCo XML reference, `visual/headlight`, `visual/global`)
+DEFAULT_HEADLIGHT = dict(ambient=0.1, diffuse=0.4)
+DEFAULT_FOVY = 45.0
+
+
+def humanoid_visual():
+    """What dp_env_v3.xml says about how the model looks (`mjcf.load_visual` reads the same from the XML): its two cameras,
+    the directional light, the default geom colour, the floor's checker material and the gradient skybox.  render.make_desc
+    turns it into the descriptor of dm_batch_render."""
+    return dict(
+        cameras=[dict(name="back", body=1, pos=(-3.0, 0.0, 1.0), xyaxes=(0.0, -1.0, 0.0, 1.0, 0.0, 2.0), mode="trackcom", fovy=DEFAULT_FOVY),  # :23
+                 dict(name="side", body=1, pos=(0.0, -3.0, 1.0), xyaxes=(1.0, 0.0, 0.0, 0.0, 1.0, 2.0), mode="trackcom", fovy=DEFAULT_FOVY)],  # :24
+        light=dict(dir=(0.0, 0.0, -1.3), diffuse=(1.0, 1.0, 1.0), directional=True),                                    # :20
+        geom_rgba=(0.7, 0.5, 0.3, 1.0),                                                                                  # :5
+        floor=dict(geom=0, builtin="checker", rgb1=(0.1, 0.2, 0.3), rgb2=(0.2, 0.3, 0.4), texrepeat=(1.0, 1.0), texuniform=True),  # :14-15, :19
+        skybox=dict(builtin="gradient", rgb1=(0.4, 0.5, 0.6), rgb2=(0.0, 0.0, 0.0)),                                    # :12
+        headlight=dict(DEFAULT_HEADLIGHT),
+    )

@@ -226,3 +226,69 @@ def to_mjcf(spec):
     out.append("  </actuator>")
     out.append("</mujoco>")
     return "\n".join(out)
+
+
+def load_visual(path_or_string):
+    """The rendering description of an MJCF document, in the format of `humanoid.humanoid_visual()`: its cameras (name, the
+    index of the body they sit in, counted as `load_mjcf` counts bodies, pos, xyaxes, mode, fovy), the first directional light,
+    the default geom rgba, the floor plane's checker texture (through its material) and the skybox.  `load_mjcf` is unaffected."""
+    from .humanoid import DEFAULT_FOVY, DEFAULT_HEADLIGHT
+    if path_or_string.lstrip().startswith("<"):
+        root = ET.fromstring(path_or_string)
+    else:
+        root = ET.parse(path_or_string).getroot()
+    if root.tag != "mujoco":
+        raise ValueError("not an MJCF document")
+    rgba = (0.5, 0.5, 0.5, 1.0)                      # MuJoCo's default geom colour
+    for d in root.findall("default"):
+        g = d.find("geom")
+        if g is not None and g.get("rgba"):
+            rgba = _floats(g.get("rgba"), 4)
+    headlight, fovy = dict(DEFAULT_HEADLIGHT), DEFAULT_FOVY
+    vis = root.find("visual")
+    if vis is not None:
+        h = vis.find("headlight")
+        if h is not None:
+            for k in ("ambient", "diffuse"):
+                if h.get(k):
+                    headlight[k] = _floats(h.get(k), 3)[0]
+        gl = vis.find("global")
+        if gl is not None and gl.get("fovy"):
+            fovy = float(gl.get("fovy"))
+    textures, materials = {}, {}
+    skybox = None
+    for asset in root.findall("asset"):
+        for t in asset.findall("texture"):
+            rec = dict(builtin=t.get("builtin", "none"), rgb1=_floats(t.get("rgb1", "0.8 0.8 0.8"), 3), rgb2=_floats(t.get("rgb2", "0.5 0.5 0.5"), 3))
+            if t.get("type") == "skybox":
+                skybox = rec
+            elif t.get("name"):
+                textures[t.get("name")] = rec
+        for m in asset.findall("material"):
+            materials[m.get("name")] = m
+    cameras, light, floor = [], None, None
+    count = [0]
+
+    def walk(elem, body):
+        nonlocal light, floor
+        for e in elem:
+            if e.tag == "body":
+                count[0] += 1
+                walk(e, count[0])
+            elif e.tag == "camera":
+                cameras.append(dict(name=e.get("name"), body=body, pos=_floats(e.get("pos", "0 0 0"), 3),
+                                    xyaxes=_floats(e.get("xyaxes", "1 0 0 0 1 0"), 6), mode=e.get("mode", "fixed"),
+                                    fovy=float(e.get("fovy", fovy))))
+            elif e.tag == "light" and light is None and _bool(e.get("directional", "false")):
+                light = dict(dir=_floats(e.get("dir", "0 0 -1"), 3), diffuse=_floats(e.get("diffuse", "0.7 0.7 0.7"), 3), directional=True)
+            elif e.tag == "geom" and floor is None and e.get("type") == "plane" and e.get("material") in materials:
+                m = materials[e.get("material")]
+                tex = textures.get(m.get("texture"))
+                if tex is not None and tex["builtin"] == "checker":
+                    floor = dict(geom=0, builtin="checker", rgb1=tex["rgb1"], rgb2=tex["rgb2"],
+                                 texrepeat=_floats(m.get("texrepeat", "1 1"), 2), texuniform=_bool(m.get("texuniform", "false")))
+
+    wb = root.find("worldbody")
+    if wb is not None:
+        walk(wb, 0)
+    return dict(cameras=cameras, light=light, geom_rgba=rgba, floor=floor, skybox=skybox, headlight=headlight)

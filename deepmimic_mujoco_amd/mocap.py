@@ -147,4 +147,4 @@ class MocapDM(object):
         self.data_vel = vel
 
     def play(self, mocap_filepath):
-        raise NotImplementedError("rendering is outside the accelerated path (SURVEY.md section 2, row 24)")
+        raise NotImplementedError("there is no on-screen viewer; tools/play_mocap.py renders the clip's frames to a GIF (dm_batch_render)")

@@ -764,15 +764,21 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
     return history
 
 
-def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print, save_sample=None):
+def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print, save_sample=None, frames=None, render_size=(500, 500),
+           render_camera="side"):
     """`runner()` + `traj_1_generator()` of src/trpo.py:356-436 (`--task evaluate`), one trajectory per env of the batch at once: from
     `env.reset(); env.reset_model_init()` each env runs `pi.act(stochastic, ob)` -> `env.step(ac)` until its first `done` or until
     `timesteps_per_batch + 1` steps.  Returns (average length, average return) as the reference prints them, plus the per-trajectory
     arrays.  `pi` comes from `MlpPolicy.from_tf_checkpoint(path)` (= U.load_state) or `from_npz`.
     save_sample: a path — the trajectories are also written there as `--save_sample` does (:385-388): obs / acs (N, L, ...) when every
     trajectory has the same length, else object arrays of N (L_i, ...) arrays, lens, rets; and the same returns as `ep_rets`, the key the
-    GAIL expert reader (src/utils/mujoco_dset.py) reads.  gail.ExpertDataset accepts the file."""
+    GAIL expert reader (src/utils/mujoco_dset.py) reads.  gail.ExpertDataset accepts the file.
+    frames: a render.FrameWriter — trajectory 0 is rendered (dm_batch_render, `render_camera`, render_size = (width, height)) from its
+    first state and after every step it survives: what the reference's `env.render()` after each step (:421) shows."""
     n = env.num_envs
+
+    def snap():
+        frames.add(env.batch.render(render_size[0], render_size[1], render_camera, env_ids=np.zeros(1, dtype=np.int32))["rgb"][0])
     dev = pi.device
     with torch.no_grad():
         ob = torch.zeros((n, 56), dtype=torch.float64, device=dev)
@@ -780,6 +786,8 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         ep_len = torch.zeros(n, dtype=torch.int64, device=dev); ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
         obs_hist, acs_hist = [], []
+        if frames is not None:
+            snap()
         for t in range(int(timesteps_per_batch) + 1):
             ac, _ = pi.act(stochastic_policy, ob)
             if save_sample:
@@ -789,6 +797,8 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
             rew = torch.as_tensor(res[1], dtype=torch.float64, device=dev); done = torch.as_tensor(res[2], device=dev).to(torch.bool)
             ep_ret += torch.where(alive, rew, torch.zeros_like(rew)); ep_len += alive.to(torch.int64)
             alive &= ~done
+            if frames is not None and bool(alive[0]):
+                snap()
             if not bool(alive.any()):
                 break
     lens, rets = ep_len.cpu().numpy(), ep_ret.cpu().numpy()

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 7
+#define DM_ABI_VERSION 8
 
 /* fixed sizes of the DeepMimic humanoid (dp_env_v3.xml:21-156): the kernels are specialised to this tree */
 #define DM_NBODY 14
@@ -225,6 +225,36 @@ int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t bytes, int32
  *   per row r < DM_MAXEFC: J[34] , then pos, margin, R, aref, b, force   (DM_DEBUG_DOUBLES in total) */
 #define DM_DEBUG_DOUBLES (34 * 34 + 34 * 3 + 42 + 3 + DM_MAXEFC * (34 + 6))
 int dm_batch_debug_forward(dm_batch* b, int32_t env, double* out_host);
+
+/* Replaces: mujoco-py `sim.render(w, h, camera_name=, depth=)` / `MjViewer.render` behind gym `MujocoEnv.render`
+ * (src/trpo.py:421, src/mujoco/mocap_v2.py:161-178): ray-cast images of n environment states.
+ * The scene is the model's 16 geoms at the frames forward kinematics gives (the floor plane z = 0, visible from above, finite at
+ * |x|, |y| <= its size; spheres, capsules, boxes), each view alone.  Pinhole camera, vertical `fovy` in degrees; cam_mat is
+ * row-major like MuJoCo's cam_xmat: its columns are the camera's x (right), y (up) and z (backward) axes, and it looks along -z.
+ * With track_com, cam_pos is an offset from the root's subtree centre of mass at each view's qpos.  Pixel (r, c), row 0 at the top:
+ *   u = (2 (c + 0.5) / W - 1) tan(fovy / 2) W / H,   v = (1 - 2 (r + 0.5) / H) tan(fovy / 2),   d = normalize(u x + v y - z).
+ * Shading: c = clamp(albedo (ambient + headlight max(0, -n.d) + diffuse vis max(0, -n.l)), 0, 1), byte = floor(255 c + 0.5), with
+ * l = normalize(light_dir) and vis = 0 where a ray from the hit point (offset 1e-4 along n) towards -l meets a body geom.  The floor's
+ * albedo is a checker of squares of `floor_square` metres (floor_rgb1 where floor(x / sq) + floor(y / sq) is even); a pixel that
+ * hits nothing takes the unlit skybox sky_bottom + (1 + d_z) / 2 (sky_top - sky_bottom).  geom_rgb[0] is unused. */
+typedef struct {
+  int32_t width, height;            /* 1 .. 4096 each */
+  int32_t track_com;                /* cam_pos is an offset from the humanoid's centre of mass */
+  double cam_pos[3], cam_mat[9], fovy;
+  double geom_rgb[DM_NGEOM][3], floor_rgb1[3], floor_rgb2[3], floor_square;
+  double sky_top[3], sky_bottom[3], light_dir[3], ambient, headlight, diffuse;
+} dm_render_desc;
+/* qpos == NULL: the batch's current states of env_ids[0..n) (env_ids NULL: envs 0..n-1, n <= the batch size).  qpos [n,35] non-NULL:
+ * those poses, rendered with the batch's model on its stream (mocap playback, recorded trajectories); env_ids must then be NULL.
+ * Outputs (each may be NULL, at least one given): rgb [n,H,W,3] uint8, depth [n,H,W] float32 (distance along the optical axis, +inf
+ * where nothing is hit), seg [n,H,W] int32 (geom id: 0 the floor, 1..15 body geoms, -1 nothing), geom_xform [n,16,12] float64 (each
+ * geom's world position, then its row-major rotation).  ptr_kind applies to every array, qpos and env_ids included: host outputs
+ * are written when the call returns; device outputs are valid once the caller's stream has joined, like a step's (device env_ids
+ * are read back to the host to be checked).  Queued steps run and pipelined sub-batches join first, so an image shows the latest
+ * step; no simulation state changes.  DM_EINVAL: n <= 0, n beyond the batch without qpos, an env id out of range, a size outside
+ * 1..4096, n W H >= 2^31, fovy outside (0, 180), no output. */
+int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, const dm_render_desc* d, uint8_t* rgb,
+                    float* depth, int32_t* seg, double* geom_xform, int32_t ptr_kind);
 
 /* kernel timing of the last dm_batch_step launch, measured with HIP events on the batch's stream (ms) */
 int dm_batch_last_step_ms(dm_batch* b, float* ms);

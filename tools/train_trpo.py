@@ -39,6 +39,11 @@ def main():
     ap.add_argument("--stochastic-policy", action="store_true")
     ap.add_argument("--save-sample", default=None, help="evaluate: also write the trajectories to this .npz (obs, acs, lens, rets and ep_rets: "
                                                         "the reference's `--save_sample` file, readable by its GAIL expert reader and tools/train_gail.py)")
+    ap.add_argument("--render-out", default=None, help="evaluate: write trajectory 0 frame by frame (what the reference's env.render() shows) to this "
+                                                       ".gif (an .npy of frames where PIL is missing), ray-cast by dm_batch_render")
+    ap.add_argument("--camera", default="side", choices=["side", "back"], help="--render-out: the model camera (dp_env_v3.xml:23-24)")
+    ap.add_argument("--width", type=int, default=320, help="--render-out: image width")
+    ap.add_argument("--height", type=int, default=240, help="--render-out: image height")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--log-dir", default=None, help="write progress.csv and monitor.csv in the reference's formats")
@@ -69,7 +74,14 @@ def main():
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
         env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, autoreset="init", seed=args.seed, frame_skip=fs)
-        runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=args.save_sample)
+        writer = None
+        if args.render_out:
+            from deepmimic_mujoco_amd.render import FrameWriter
+            writer = FrameWriter(args.render_out, fps=1.0 / (env.frame_skip * float(env._cm.timestep)))
+        runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=args.save_sample, frames=writer,
+               render_size=(args.width, args.height), render_camera=args.camera)
+        if writer is not None:
+            print("wrote %d frames of trajectory 0 to %s" % (len(writer.frames), writer.close()))
         return
     P = max(1, args.pipeline)
     if args.unfused:
