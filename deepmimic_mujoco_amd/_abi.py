@@ -15,6 +15,8 @@ PTR_HOST, PTR_DEVICE = 0, 1
 FLAG_NO_CONTACT, FLAG_NO_LIMIT = 1, 2
 OPT_REWARD_MODE, OPT_AUTORESET, OPT_ACTION_MODE, OPT_SEED, OPT_DIAGNOSTICS, OPT_PIPELINE, OPT_PACKED, OPT_ENV_OFFSET = 1, 2, 3, 4, 5, 6, 7, 100
 OPT_STEP_QUEUE = 8
+# DM_OPT_ACTION_MODE values (include/dmenv.h): 3 and 4 make the action a PD target pose under a stable PD controller evaluated per substep
+ACTION_RAW, ACTION_P_CONTROL, ACTION_PD, ACTION_SPD_TARGET, ACTION_SPD_MOCAP = 0, 1, 2, 3, 4
 MAX_PIPELINE = 8
 MAX_STEP_QUEUE = 256
 # per-environment capacities of the OPT_PACKED path (include/dmenv.h DM_PACKED_*)

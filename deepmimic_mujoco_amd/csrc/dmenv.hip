@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64, DM_STEP_WAVES) void k_step_narrow(const DevMode
   if ((int)blockIdx.x >= count) return;
   int env;
   dispatch_env<1>(B, first, count, (int)blockIdx.x, dmw::lane(), blockIdx.x == 0, &env);
-  env_step<Real, NARROW_ROWS>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
+  env_step_impl<Real, NARROW_ROWS, false, false>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
 }
 // the same step followed, in the same wave, by the policy's step on the observation it produced (dm_batch_step_act)
 __global__ __launch_bounds__(64, DM_STEP_WAVES) void k_step_act(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const Ext* __restrict__ action,
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(64, DM_STEP_WAVES) void k_step_act(const DevModel<R
   if ((int)blockIdx.x >= count) return;
   int env;
   dispatch_env<1>(B, first, count, (int)blockIdx.x, dmw::lane(), blockIdx.x == 0, &env);
-  env_step<Real, NARROW_ROWS>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
+  env_step_impl<Real, NARROW_ROWS, false, false>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
   // s.qpos / s.qvel hold the state the observation was written from (the fresh episode's after an auto-reset); the row-descriptor
   // region is free
   static_assert(sizeof(s.u) >= 464 * sizeof(float), "policy scratch");
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void k_step(const DevModel<Real>* __restrict__ 
   __shared__ StepScratch<Real> x;
   const int env = blockIdx.x;
   if (env >= B.n_envs) return;
-  env_step<Real, MAXEFC>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
+  env_step_impl<Real, MAXEFC, false, false>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
 }
 
 // the batch descriptor into device memory, stream-ordered before the horizon launch that reads it there
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64, DM_STEP_WAVES) void k_step_redo(const DevModel<
   if (blockIdx.x == 0 && threadIdx.x == 0 && n > 0) atomicAdd(B.redo_why, n);       // running total (dm_batch_redo_total)
   for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) {
     const int env = B.redo_list[first + i];
-    env_step<Real, NARROW_ROWS>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
+    env_step_impl<Real, NARROW_ROWS, false, false>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps);
     if (pa.P) { dmw::sync(); dmp::policy_wave(pa, env, dmw::lane(), &s.qpos[7], &s.qvel[6], reinterpret_cast<float*>(&s.u)); }
     dmw::sync_mem();
   }
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64) void k_step_prof(const DevModel<Real>* __restri
   __shared__ StepScratch<Real> x;
   const int env = blockIdx.x;
   if (env >= B.n_envs) return;
-  env_step<Real, MAXEFC, true>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps, prof);
+  env_step_impl<Real, MAXEFC, true, false>(*Mp, B, s, x, env, dmw::lane(), action, obs, reward, done, n_substeps, prof);
 }
 
 __global__ __launch_bounds__(64) void k_set_state(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const Ext* __restrict__ qpos,
@@ -410,7 +410,7 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
       if (v >= 3 && !b->d_imit) return fail(DM_EINVAL, "reward modes 3 and 4 need dm_mocap_set_imitation() before dm_batch_create()");
       b->B.reward_mode = (int)v; break;
     case DM_OPT_AUTORESET: if (v < 0 || v > 2) return fail(DM_EINVAL, "autoreset must be 0..2"); b->B.autoreset = (int)v; break;
-    case DM_OPT_ACTION_MODE: if (v < 0 || v > 2) return fail(DM_EINVAL, "action mode must be 0..2"); b->B.action_mode = (int)v; break;
+    case DM_OPT_ACTION_MODE: if (v < 0 || v > 4) return fail(DM_EINVAL, "action mode must be 0..4"); b->B.action_mode = (int)v; break;
     case DM_OPT_SEED: b->B.seed = (unsigned long long)v; break;
     case DM_OPT_DIAGNOSTICS: b->B.diag = v != 0; break;
     case DM_OPT_PIPELINE: {
@@ -497,8 +497,9 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // SIMD (8 192 envs on an MI355X; at 4 096 envs 17.3 M env-steps/s against 12.2 M for the one-env steps and 11.4 M for the packed ones).
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
+  // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && b->B.action_mode <= 2 && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -618,6 +619,16 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   const bool packed_step = b->packed && b->B.reward_mode <= 4 && b->two_tier;      // this call runs on the packed kernels (profiled or not)
   const bool use_packed = packed_step && !b->prof;
   const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
+  // the kernels of this call: action modes 3 and 4 have their own instantiations (kernels_spd.hip, kernels_packed_spd.hip), launched exactly like the others
+  const bool spd = b->B.action_mode >= 3;
+  const auto kn_packed = spd ? (b->packed_ext ? k_step_packed_ext_spd : k_step_packed_spd) : (b->packed_ext ? k_step_packed_ext : k_step_packed);
+  const auto kn_packed_act = spd ? (b->packed_ext ? k_step_packed_act_ext_spd : k_step_packed_act_spd) : (b->packed_ext ? k_step_packed_act_ext : k_step_packed_act);
+  const auto kn_packed_prof = spd ? k_step_packed_prof_spd : k_step_packed_prof;
+  const auto kn_redo = spd ? k_step_redo_spd : k_step_redo;
+  const auto kn_narrow = spd ? k_step_narrow_spd : k_step_narrow;
+  const auto kn_act = spd ? k_step_act_spd : k_step_act;
+  const auto kn_single = spd ? k_step_spd : k_step;
+  const auto kn_prof = spd ? k_step_prof_spd : k_step_prof;
   if (packed_step) {
     const int mode = piped ? 1 : 0;
     if (mode != b->redo_mode) {      // (rare: the first packed step, or a host-pointer step between pipelined ones; every earlier launch is ordered before this stream here)
@@ -631,9 +642,9 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   if (b->prof && packed_step) {
     HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
     int* rc = b->B.redo_count + b->redo_phase; int* rn = b->B.redo_count + (1 - b->redo_phase);
-    hipLaunchKernelGGL(k_step_packed_prof, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, b->d_prof);
-    if (b->has_rows) hipLaunchKernelGGL(k_step_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, nopol);
-  } else if (b->prof) hipLaunchKernelGGL(k_step_prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, b->d_prof);
+    hipLaunchKernelGGL(kn_packed_prof, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, b->d_prof);
+    if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, nopol);
+  } else if (b->prof) hipLaunchKernelGGL(kn_prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, b->d_prof);
   else if (piped) {
     // Sub-batch h's launch of THIS call depends on its own launch of the previous call (stream order on ps[h]) and on the
     // caller's inputs (ev_in), not on the other sub-batches: while the last, cheap workgroups of one sub-batch drain, the
@@ -649,12 +660,12 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       if (b->timing && h == 0) HIPCHK(hipEventRecord(b->ev0, b->ps[0]));     // timing: sub-batch 0's kernel on ITS stream
       if (use_packed) {
         int* rc = b->B.redo_count + 2 * h + b->redo_phase; int* rn = b->B.redo_count + 2 * h + (1 - b->redo_phase);
-        if (pol) hipLaunchKernelGGL(b->packed_ext ? k_step_packed_act_ext : k_step_packed_act, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc, *pol);
-        else hipLaunchKernelGGL(b->packed_ext ? k_step_packed_ext : k_step_packed, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc);
-        if (b->has_rows) hipLaunchKernelGGL(k_step_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pol ? *pol : nopol);
+        if (pol) hipLaunchKernelGGL(kn_packed_act, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc, *pol);
+        else hipLaunchKernelGGL(kn_packed, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc);
+        if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pol ? *pol : nopol);
       }
-      else if (pol) hipLaunchKernelGGL(k_step_act, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, *pol);
-      else hipLaunchKernelGGL(k_step_narrow, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo);
+      else if (pol) hipLaunchKernelGGL(kn_act, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, *pol);
+      else hipLaunchKernelGGL(kn_narrow, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo);
       if (b->timing && h == 0) { HIPCHK(hipEventRecord(b->ev1, b->ps[0])); b->ev_pending = true; }
       HIPCHK(hipEventRecord(b->ev_done[h], b->ps[h]));
     }
@@ -670,13 +681,13 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of counters is clean — pair 0's
       //  two are cleared here once if a pipelined step used them before)
       int* rc = b->B.redo_count + b->redo_phase; int* rn = b->B.redo_count + (1 - b->redo_phase);
-      if (pol) hipLaunchKernelGGL(b->packed_ext ? k_step_packed_act_ext : k_step_packed_act, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, *pol);
-      else hipLaunchKernelGGL(b->packed_ext ? k_step_packed_ext : k_step_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc);
-      if (b->has_rows) hipLaunchKernelGGL(k_step_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, pol ? *pol : nopol);
+      if (pol) hipLaunchKernelGGL(kn_packed_act, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, *pol);
+      else hipLaunchKernelGGL(kn_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc);
+      if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, pol ? *pol : nopol);
     }
-    else if (pol) hipLaunchKernelGGL(k_step_act, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, *pol);
-    else hipLaunchKernelGGL(k_step_narrow, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n);
-  } else hipLaunchKernelGGL(k_step, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub);
+    else if (pol) hipLaunchKernelGGL(kn_act, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, *pol);
+    else hipLaunchKernelGGL(kn_narrow, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n);
+  } else hipLaunchKernelGGL(kn_single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub);
   HIPCHK(hipGetLastError());
   for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
   if (packed_step) b->redo_phase ^= 1;

@@ -658,7 +658,8 @@ struct EliminateFrom {
   }
 };
 
-template <class R>
+// SPD (action modes 3 and 4, env_step.h spd_control): the factor of M + h diag(kd) instead — only the diagonal moves, the sparsity and the schedule stay.
+template <class R, bool SPD = false>
 DM_DEV void stage_mass_matrix(const DevModel<R>& M, Shared<R>& s, int lane_in, const LaneTopo& lt, const DebugOut* dbg) {
   const int lane = dmw::launder(lane_in);
   // the elimination schedule's per-lane words, all requested here: their latency hides behind the assembly of M
@@ -669,6 +670,8 @@ DM_DEV void stage_mass_matrix(const DevModel<R>& M, Shared<R>& s, int lane_in, c
     R f[6];
     sinert_mul(f, s.ub.i.crb[TOPO.dof_body[lane]], s.cdof[lane]);
     for (int r = 0; r < 6; r++) s.u.fdof[lane][r] = f[r];
+    if constexpr (SPD) s.dinv[lane] = M.dof_armature[lane] + M.timestep * M.kd[lane];
+    else
     s.dinv[lane] = M.dof_armature[lane];     // staged once (coalesced) — s.dinv is dead until the end of the factorisation;
   }                                          // a per-entry `M.dof_armature[i]` would be a divergent global load in every pass
   dmw::sync();

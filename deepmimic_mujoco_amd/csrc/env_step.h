@@ -450,12 +450,52 @@ DM_DEV void place_kin(Shared<R>& s, const R* reg, int lane) {
   for (int c = 0; c < KIN_PER_LANE; c++) { const int i = lane + 64 * c; if (i < KIN_A) a[i] = reg[c]; else if (i < KIN_DOUBLES) b[i - KIN_A] = reg[c]; }
 }
 
+// ---- stable PD control (action modes 3 "spd-target" and 4 "spd-mocap"; cImpPDController::CalcControlForces, code.md:147-179) -----------------
+// The action is a target pose: qbar = action (mode 3) or mocap frame + action (mode 4), vbar = 0 or the mocap frame's rates.  At the start of
+// EVERY simulation substep, from the state (q, v) the substep starts at, with h = the model's timestep:
+//   p = kp (qbar - q - h v),  d = kd (vbar - v),  c = qfrc_bias - qfrc_passive,  a = (M + h diag(kd))^-1 (p + d - c),  tau = p + d - h kd a
+//   ctrl = tau / gear (kept unclamped in B.ctrl),  actuator force = gear clamp(ctrl, ctrlrange);  held through the substep's four RK4 evaluations.
+// Built from the stages of a forward evaluation: kinematics (skipped where the env's parked kinematics are those of this state), the mass-matrix
+// stage with h kd on the diagonal (same tree-sparse L^T D L), the bias stage with no actuation (it leaves -c in s.ua.f.tau), one lane-parallel
+// solve.  None of them touches the kinematics' results, so the substep's first RK4 evaluation — the same state — starts from them (forward's `kin`).
+// qbar / vbar: the target of dof `lane` (lanes 6..33).  Ends with a full hand-off: the reward epilogue reads B.ctrl back.
+template <class R>
+DM_DEV void spd_control(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int env, int lane, const LaneTopo& lt, R qbar, R vbar, bool kin) {
+  const R h = M.timestep;
+  if (lane < NV) s.act[lane] = 0;
+  if (!kin) stage_kinematics(M, s, lane, lt);
+  else dmw::sync();
+  stage_mass_matrix<R, true>(M, s, lane, lt, (const DebugOut*)0);
+  stage_bias(M, s, lane, lt);
+  const bool hinge = lane >= 6 && lane < NV;
+  R p = 0, d = 0, kd = 0;
+  if (hinge) {
+    const R q = s.qpos[lane + 1], v = s.qvel[lane];
+    kd = M.kd[lane];
+    p = M.kp[lane] * (qbar - q - h * v);
+    d = kd * (vbar - v);
+  }
+  R x = lane_solve_LT(s, lane, lane < NV ? p + d + s.ua.f.tau[lane] : R(0));
+  if (lane < NV) x *= s.dinv[lane];
+  dmw::sync();
+  const R a = lane_solve_L(s, lane, x);
+  if (hinge) {
+    const R g = M.gear[lane];
+    const R c = (p + d - h * kd * a) / g;
+    B.ctrl[(size_t)env * NU + (lane - 6)] = c;   // data.ctrl keeps the unclamped value (the last substep's: DM_F_CTRL, the control cost of reward modes 2 and 4)
+    s.act[lane] = g * clampr(c, M.ctrl_lo[lane], M.ctrl_hi[lane]);
+  }
+  dmw::sync_mem();
+}
+
 // DPEnv.step for one environment
 // ROWS = columns of A = J M^-1 J^T + R that this instantiation keeps in registers; an evaluation with more constraint rows
 // (up to MAXEFC) keeps the remaining columns in the env's global-memory strip s.aovf (see stage_constraint).
-template <class R, int ROWS = MAXEFC, bool PROF = false>
-DM_DEV bool env_step(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, StepScratch<R>& x, int env, int lane,
-                     const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0) {
+// SPD: the instantiation for action modes 3 and 4 (spd_control above) — the action is a target pose and the control is evaluated per substep.  The
+// kernels of modes 0..2 instantiate SPD = false, whose code is what it was before the modes existed.
+template <class R, int ROWS, bool PROF, bool SPD>
+DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, StepScratch<R>& x, int env, int lane,
+                          const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0) {
   long long prof[PROF_SLOTS];
   for (int k = 0; k < PROF_SLOTS; k++) prof[k] = 0;
   long long tstart = 0;
@@ -465,10 +505,25 @@ DM_DEV bool env_step(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, Step
   const bool kin0 = B.kin && dmw::uniform((int)B.kin_ok[env]) != 0;
   R kreg[KIN_PER_LANE];
   if (kin0) fetch_kin(kreg, B.kin + (size_t)env * KIN_DOUBLES, lane);
+  R qbar = 0, vbar = 0;                  // SPD: the target of dof `lane` (the frame cursor as it stands at the start of the env step)
+  if constexpr (SPD) {
+    load_env(M, B, s, env, lane, (const double*)0);
+    if (lane >= 6 && lane < NV) {
+      const int u = lane - 6;
+      if (action) qbar = (R)action[(size_t)env * NU + u];
+      if (B.action_mode == 4) {
+        const int idx = B.frame_idx[env];
+        qbar += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
+        vbar = B.mocap_vel[(size_t)idx * NV + 6 + u];
+      }
+    }
+  } else
   load_env(M, B, s, env, lane, action);
   if (kin0) { place_kin(s, kreg, lane); dmw::sync(); }
-  for (int k = 0; k < n_substeps; k++)   // do_simulation(action, n)
-    if (!rk4_step<R, ROWS, PROF>(M, s, x, lane, lt, prof, k == 0 && kin0)) { if (lane == 0) order_ticket(B, env, s.nefc, s.solver_iter); return false; }
+  for (int k = 0; k < n_substeps; k++) {   // do_simulation(action, n)
+    if constexpr (SPD) spd_control(M, B, s, env, lane, lt, qbar, vbar, k == 0 && kin0);
+    if (!rk4_step<R, ROWS, PROF>(M, s, x, lane, lt, prof, SPD || (k == 0 && kin0))) { if (lane == 0) order_ticket(B, env, s.nefc, s.solver_iter); return false; }
+  }
   bool kin_saved = false;
   const R z = com_z(M, s);
   bool dn = (z < R(0.7)) || (z > R(2.0));
@@ -533,6 +588,14 @@ DM_DEV bool env_step(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, Step
     for (int k = 0; k < PROF_SLOTS; k++) prof_out[(size_t)env * PROF_SLOTS + k] = prof[k];
   }
   return true;
+}
+// The step by the batch's action mode: the wave testbench and the kernels of modes 3 and 4 come through here or name their instantiation; the
+// kernels of modes 0..2 call env_step_impl<.., false> directly and carry no controller code.
+template <class R, int ROWS = MAXEFC, bool PROF = false>
+DM_DEV bool env_step(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, StepScratch<R>& x, int env, int lane,
+                     const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0) {
+  if (B.action_mode >= 3) return env_step_impl<R, ROWS, PROF, true>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out);
+  return env_step_impl<R, ROWS, PROF, false>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out);
 }
 
 }  // namespace dm

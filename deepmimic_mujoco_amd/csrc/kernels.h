@@ -1,6 +1,8 @@
 // kernels.h — what the three translation units of libdmenv.so share: the build's arithmetic type and the prototypes of the packed step kernels.
 //   dmenv.hip           one-env step kernels, reset / state / ordering / learner kernels, the C ABI (host side)
 //   kernels_rollout.hip the horizon launch (k_rollout_packed + the step bodies it calls): the packed options and the load-store vectoriser off
+//   kernels_spd.hip / kernels_packed_spd.hip   the one-env and the packed step kernels of action modes 3 and 4 (stable PD control per substep), units
+//                       of their own with the options of dmenv.hip / kernels_packed.hip: the kernels of modes 0..2 carry no controller code
 //   kernels_packed.hip  the four-environments-per-wavefront per-step kernels (slot_kernel.h / slot_step.h): compiled with their own backend options
 //                       (csrc/build.py PACKED_FLAGS — one wave per SIMD with the whole register file wants a scheduler that goes for
 //                       instruction-level parallelism, the two-waves-per-SIMD one-env kernels do not: profiles/r04_ab_kernel_variants.md)
@@ -56,3 +58,24 @@ __global__ void k_rollout_packed(const dm::DevModel<Real>* __restrict__ Mp, cons
                                  int count, int T, dmp::PolicyArgs pa, long long* __restrict__ wave_clk);
 __global__ void k_step_packed_prof(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
                                    unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, long long* __restrict__ prof);
+// ---- kernels_packed_spd.hip, kernels_spd.hip: the same launches in action modes 3 and 4 -----------------------------------------------------
+__global__ void k_step_packed_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                              unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count);
+__global__ void k_step_packed_act_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                  unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dmp::PolicyArgs pa);
+__global__ void k_step_packed_ext_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                  unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count);
+__global__ void k_step_packed_act_ext_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                      unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dmp::PolicyArgs pa);
+__global__ void k_step_packed_prof_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                   unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, long long* __restrict__ prof);
+__global__ void k_step_narrow_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                  unsigned char* __restrict__ done, int n_substeps, int first, int count);
+__global__ void k_step_act_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                               unsigned char* __restrict__ done, int n_substeps, int first, int count, dmp::PolicyArgs pa);
+__global__ void k_step_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                           unsigned char* __restrict__ done, int n_substeps);
+__global__ void k_step_redo_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                unsigned char* __restrict__ done, int n_substeps, int first, const int* __restrict__ redo_count, int* __restrict__ redo_count_next, dmp::PolicyArgs pa);
+__global__ void k_step_prof_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                unsigned char* __restrict__ done, int n_substeps, long long* prof);

@@ -439,7 +439,8 @@ struct SlotEliminateFrom {
 static_assert(elim_group_size(4, 0) % SW == 0 && elim_group_size(3, 2) % SW == 0 && elim_group_size(1, 0) % SW == 0, "lane groups are whole slots");
 // (pair codes of a lane cover t = (lane & 15) + 16 j, j < 6, i.e. t < 96: elim_codes_ok)
 
-template <class R, bool PROF = false>
+// SPD (action modes 3 and 4, slot_step.h slot_spd_control): the factor of M + h diag(kd) instead.
+template <class R, bool PROF = false, bool SPD = false>
 DM_DEV void slot_mass_matrix(const DevModel<R>& M, SlotShared<R>& s, const SlotTables& tb, int sl_in, const LaneTopo& lt, const DebugOut* dbg, long long* prof = 0) {
   const int sl = DM_SLOT_LANE_AT(2, sl_in);
   long long pt0 = 0, pt1 = 0;
@@ -457,7 +458,8 @@ DM_DEV void slot_mass_matrix(const DevModel<R>& M, SlotShared<R>& s, const SlotT
     const int d = sl + SW * c;
     if (d < NV) {
       for (int r = 0; r < 6; r++) s.r1.fdof[d][r] = f[c][r];
-      s.qd.o.dinv[d] = M.dof_armature[d];
+      if constexpr (SPD) s.qd.o.dinv[d] = M.dof_armature[d] + M.timestep * M.kd[d];
+      else s.qd.o.dinv[d] = M.dof_armature[d];
     }
   }
   int ijc[ENT_PASSES];                      // (i << 8) | j of this lane's entries, fetched ahead of the hand-off: the loop below then has no dependent look-up

@@ -115,6 +115,61 @@ DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>
   dmw::sync_mem();
 }
 
+// ---- stable PD control of the slot's environment (action modes 3 and 4; env_step.h spd_control has the rule).  A pass of its own over the
+// stages at the start of every substep: kinematics, bias without actuation (-c in s.tau), the mass-matrix stage with h kd on the diagonal,
+// one register solve (every lane of the slot carries the vector, as in slot_smooth_solve).  The factor overwrites the inertias here (r2), so
+// the substep's first RK4 evaluation forms its own kinematics again.  qbar / vbar: dof-distributed targets (dofs 6..33).
+template <class R>
+DM_DEV void slot_spd_control(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, const SlotTables& tb, int env, int sl, const LaneTopo& lt, bool live,
+                             const DofVec<R>& qbar, const DofVec<R>& vbar) {
+  const R h = M.timestep;
+#pragma unroll
+  for (int c = 0; c < DOF_PASSES; c++) { const int d = sl + SW * c; if (d < NV) s.act[d] = 0; }
+  dmw::sync();
+  R xip[3];
+  slot_kinematics(M, s, sl, lt, xip);
+  slot_bias(M, s, tb, sl, lt);
+  slot_mass_matrix<R, false, true>(M, s, tb, sl, lt, (const DebugOut*)0);
+  R pd[DOF_PASSES], kd[DOF_PASSES];
+#pragma unroll
+  for (int c = 0; c < DOF_PASSES; c++) {
+    const int d = sl + SW * c;
+    pd[c] = 0; kd[c] = 0;
+    if (d >= 6 && d < NV) {
+      const R q = s.qpos[d + 1], v = s.qvel[d];
+      kd[c] = M.kd[d];
+      pd[c] = M.kp[d] * (qbar.r[c] - q - h * v) + kd[c] * (vbar.r[c] - v);
+      s.tau[d] += pd[c];
+    }
+  }
+  dmw::sync();
+  {
+    R x[1][NV];
+#pragma unroll
+    for (int d = 0; d < NV; d++) x[0][d] = s.tau[d];
+    slot_solve_LT<1>(x, s.r2.qLD);
+#pragma unroll
+    for (int d = 0; d < NV; d++) { x[0][d] *= s.qd.o.dinv[d]; dmw::pin_value(x[0][d]); }
+    solve_L(x[0], s.r2.qLD);
+    if (sl == 0) {
+#pragma unroll
+      for (int d = 0; d < NV; d++) s.qd.o.qacc[d] = x[0][d];
+    }
+  }
+  dmw::sync();
+#pragma unroll
+  for (int c = 0; c < DOF_PASSES; c++) {
+    const int d = sl + SW * c;
+    if (d >= 6 && d < NV) {
+      const R g = M.gear[d];
+      const R ct = (pd[c] - h * kd[c] * s.qd.o.qacc[d]) / g;
+      if (live) B.ctrl[(size_t)env * NU + (d - 6)] = ct;
+      s.act[d] = g * clampr(ct, M.ctrl_lo[d], M.ctrl_hi[d]);
+    }
+  }
+  dmw::sync_mem();
+}
+
 template <class R>
 DM_DEV void slot_store_state(const Batch<R>& B, SlotShared<R>& s, int env, int sl, bool live) {
   if (!live) return;
@@ -249,20 +304,42 @@ DM_DEV R slot_imitation_reward(const DevModel<R>& M, const Batch<R>& B, SlotShar
 // CARRY (horizon launches only) + kin_carry (wave-uniform): the slots' LDS is what this wave's previous step left, so a slot's `kin_ok` flag
 // means what it says and the first evaluation may skip its position stage (slot_forward): one kinematics pass in five less with the 5-term
 // reward, bit-identical results.  Without kin_carry (the first step of a launch, the step after an in-wave re-step) the flags are cleared first.
-template <class R, bool PROF = false, bool CARRY = false, int MAXR = 2 * SW>
-DM_DEV bool slot_env_step(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, SlotTables& tb, int env, int sl, int lane, bool live,
-                          const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int* redo_count, int* redo_list,
-                          long long* prof_out = 0, bool kin_carry = false) {
+// SPD: the instantiation for action modes 3 and 4 (slot_spd_control); the kernels of modes 0..2 — the horizon launch among them — instantiate SPD = false.
+template <class R, bool PROF, bool CARRY, int MAXR, bool SPD>
+DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, SlotTables& tb, int env, int sl, int lane, bool live,
+                               const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int* redo_count, int* redo_list,
+                               long long* prof_out = 0, bool kin_carry = false) {
   long long prof[32];
   for (int k = 0; k < 32; k++) prof[k] = 0;
   long long tstart = 0;
   if (PROF) tstart = dmw::clk();
   const LaneTopo lt = lane_topo(sl);
   if constexpr (CARRY) { if (!kin_carry && sl == 0) s.kin_ok() = R(0); }       // (ordered before the first read by slot_load_env's hand-off)
+  DofVec<R> qbar, vbar;                  // SPD: dof-distributed targets (the frame cursor as it stands at the start of the env step)
+  if constexpr (SPD) {
+    slot_load_env(M, B, s, env, sl, live, (const double*)0);
+#pragma unroll
+    for (int c = 0; c < DOF_PASSES; c++) {
+      const int d = sl + SW * c;
+      qbar.r[c] = 0; vbar.r[c] = 0;
+      if (d >= 6 && d < NV) {
+        const int u = d - 6;
+        if (action) qbar.r[c] = (R)action[(size_t)env * NU + u];
+        if (B.action_mode == 4) {
+          const int idx = B.frame_idx[env];
+          qbar.r[c] += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
+          vbar.r[c] = B.mocap_vel[(size_t)idx * NV + 6 + u];
+        }
+      }
+    }
+  } else
   slot_load_env(M, B, s, env, sl, live, action);
   R xip[3];
   int why = 0;
-  for (int k = 0; k < n_substeps; k++) slot_rk4_step<R, PROF, CARRY, MAXR>(M, s, tb, sl, lane, lt, xip, why, prof);
+  for (int k = 0; k < n_substeps; k++) {
+    if constexpr (SPD) slot_spd_control(M, B, s, tb, env, sl, lt, live, qbar, vbar);
+    slot_rk4_step<R, PROF, CARRY, MAXR>(M, s, tb, sl, lane, lt, xip, why, prof);
+  }
   const bool ovf = dmw::row_ballot(why != 0, lane) != 0u;
   if (dmw::ballot(ovf) != 0ull) {                     // rare: list the environment, tally the reasons (diagnostics)
     unsigned bits = 0;
@@ -353,6 +430,14 @@ DM_DEV bool slot_env_step(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>
   }
   return live;                                  // the slot's environment was stepped and stored by this wave
 }
+// The step by the batch's action mode (the wave testbench; see env_step.h env_step).  Device kernels name their instantiation.
+template <class R, bool PROF = false, bool CARRY = false, int MAXR = 2 * SW>
+DM_DEV bool slot_env_step(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, SlotTables& tb, int env, int sl, int lane, bool live,
+                          const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int* redo_count, int* redo_list,
+                          long long* prof_out = 0, bool kin_carry = false) {
+  if (B.action_mode >= 3) return slot_env_step_impl<R, PROF, CARRY, MAXR, true>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry);
+  return slot_env_step_impl<R, PROF, CARRY, MAXR, false>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry);
+}
 
 // ---- a whole horizon without leaving the wave (dm_batch_rollout) ---------------------------------------------------------------------
 // T consecutive DPEnv.steps (src/dp_env_v3.py:106-132) of the wave's four environments; between two steps an optional policy step on the
@@ -397,7 +482,7 @@ DM_DEV_CALL64 void restep_one_env(const DevModel<R>* M, const Batch<R>* B, Share
   DM_CALL_SLOT_TOUCH(0);
   using dmw::uniform_ptr; using dmw::in_lds; using dmw::in_global; using dmw::in_constant;
   const Batch<R> Bv = *in_constant(B);                  // (the struct's pointers are generic too: a copy whose members are told to be global)
-  env_step<R, NR>(*in_constant(M), global_members(Bv), *in_lds(uniform_ptr(s)), *in_lds(uniform_ptr(x)), dmw::uniform(env), lane, in_global(uniform_ptr(action)),
+  env_step_impl<R, NR, false, false>(*in_constant(M), global_members(Bv), *in_lds(uniform_ptr(s)), *in_lds(uniform_ptr(x)), dmw::uniform(env), lane, in_global(uniform_ptr(action)),
                   in_global(uniform_ptr(obs)), in_global(uniform_ptr(reward)), in_global(uniform_ptr(done)), dmw::uniform(n_substeps));
 }
 // (the packed step as a call too: its body is then compiled exactly as in k_step_packed — inlined into the horizon loop the register
@@ -412,7 +497,7 @@ DM_DEV_CALL64 int slot_env_step_call(const DevModel<R>* M, const Batch<R>* B, Sl
   const Batch<R> Bv = *in_constant(B);
   SlotShared<R>& sr = *in_lds(s);
   DM_CALL_SLOT_TOUCH(env);
-  const bool stored = slot_env_step<R, false, true, MAXR>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
+  const bool stored = slot_env_step_impl<R, false, true, MAXR, false>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
                                                           in_global(uniform_ptr(obs)), in_global(uniform_ptr(reward)), in_global(uniform_ptr(done)), dmw::uniform(n_substeps), (int*)0, (int*)0,
                                                           (long long*)0, dmw::uniform(kin_carry) != 0);
   return (stored ? 1 : 0) | (sr.nefc << 8);
@@ -425,7 +510,7 @@ DM_DEV_CALL64 int slot_env_step_call_prof(const DevModel<R>* M, const Batch<R>* 
   using dmw::uniform_ptr; using dmw::in_lds; using dmw::in_global; using dmw::in_constant;
   const Batch<R> Bv = *in_constant(B);
   SlotShared<R>& sr = *in_lds(s);
-  const bool stored = slot_env_step<R, true, true, MAXR>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
+  const bool stored = slot_env_step_impl<R, true, true, MAXR, false>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
                                                          in_global(uniform_ptr(obs)), in_global(uniform_ptr(reward)), in_global(uniform_ptr(done)), dmw::uniform(n_substeps), (int*)0, (int*)0,
                                                          in_global(uniform_ptr(prof_out)), dmw::uniform(kin_carry) != 0);
   return (stored ? 1 : 0) | (sr.nefc << 8);

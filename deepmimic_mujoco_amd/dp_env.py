@@ -59,6 +59,21 @@ def _camera(camera_name):
     return DEFAULT_CAMERA if camera_name is None else camera_name
 
 
+# DM_OPT_ACTION_MODE by name.  "raw": motor commands; "p-control" / "pd": a feedback term around the mocap frame, evaluated once per env step, added to
+# a motor command; "spd-target": the action is a target pose (28 absolute hinge angles, rad) tracked by a stable PD controller that is evaluated at the
+# start of every simulation substep (DeepMimic's action); "spd-mocap": the same controller around mocap frame + action (include/dmenv.h has the rule).
+ACTION_MODES = {"raw": 0, "p-control": 1, "pd": 2, "spd-target": 3, "spd-mocap": 4}
+
+
+def _action_space(cm, action_mode):
+    """Box of the action: the actuators' ctrlrange; for "spd-target" the hinges' jnt_range (informative: targets are not clamped)."""
+    if action_mode == "spd-target":
+        jr = cm.jnt_range[cm.actuator_jntid]
+        return Box(low=jr[:, 0], high=jr[:, 1], dtype=np.float32)
+    cr = cm.actuator_ctrlrange
+    return Box(low=cr[:, 0], high=cr[:, 1], dtype=np.float32)
+
+
 class _Opt(object):
     def __init__(self, timestep):
         self.timestep = timestep
@@ -112,8 +127,12 @@ class DPEnv(object):
     reward_range = (-float("inf"), float("inf"))
     spec = None
 
-    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None):
+    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None, action_mode="raw"):
+        """action_mode: one of ACTION_MODES ("raw" is the reference's behaviour; "spd-target" / "spd-mocap" make the action a PD target pose)."""
         self.mocap = MocapDM()
+        self._action_mode = action_mode
+        if action_mode not in ACTION_MODES:
+            raise ValueError("action_mode must be one of %s" % sorted(ACTION_MODES))
         self._cm = _load_model(xml_path if xml_path is not None else Config.xml_path, explicit=xml_path is not None)
         self._visual = _load_visual(xml_path if xml_path is not None else Config.xml_path)
         self.model = _ModelView(self._cm)
@@ -138,8 +157,7 @@ class DPEnv(object):
         self.data = self.sim.data
         observation, _r, done, _i = self.step(np.zeros(self._cm.nu))   # the base class's warm-up step
         assert not done
-        cr = self._cm.actuator_ctrlrange
-        self.action_space = Box(low=cr[:, 0], high=cr[:, 1], dtype=np.float32)
+        self.action_space = _action_space(self._cm, action_mode)
         self.observation_space = Box(low=-np.inf, high=np.inf, shape=(observation.size,), dtype=np.float32)
         self.seed()
 
@@ -187,6 +205,8 @@ class DPEnv(object):
             self._batch.close()
         self._batch = self._batch_factory(self._cm, self.mocap.data_config, self.mocap.data_vel, 1, float(self.mocap_dt))
         self._batch.set_option(A.OPT_REWARD_MODE, self._reward_mode)
+        if self._action_mode != "raw":
+            self._batch.set_option(A.OPT_ACTION_MODE, ACTION_MODES[self._action_mode])
         if hasattr(self, "sim"):
             self.sim = _SimView(self); self.data = self.sim.data
 
@@ -345,6 +365,9 @@ class DPVecEnv(object):
         the one-env kernel when a competent policy keeps most environments on both feet (32+ rows).  Smaller batches: one env per wave —
         except for models without contacts and limits (BASELINE configs[1]): all waves cost the same there and four per wave is 1.5x
         faster at any size.
+        action_mode: one of ACTION_MODES.  "spd-target" / "spd-mocap": the action is a PD target pose, tracked by a stable PD controller evaluated at every
+        simulation substep (include/dmenv.h DM_OPT_ACTION_MODE); `action_space` is then the hinges' joint range ("spd-target") — informative, not enforced.
+        These two modes run on the per-step kernels: horizon launches and the step queue fall back to step launches with identical results.
         step_queue: DM_OPT_STEP_QUEUE depth (0 = off): queue `batch.step` calls and run them as one horizon launch (see below)."""
         self.num_envs = int(num_envs)
         self.mocap = MocapDM()
@@ -379,7 +402,10 @@ class DPVecEnv(object):
         b = self._batch
         b.set_option(A.OPT_REWARD_MODE, REWARD_MODES[reward])
         b.set_option(A.OPT_AUTORESET, {"none": 0, None: 0, "rsi": 1, "init": 2}[autoreset])
-        b.set_option(A.OPT_ACTION_MODE, {"raw": 0, "p-control": 1, "pd": 2}[action_mode])
+        if action_mode not in ACTION_MODES:
+            raise ValueError("action_mode must be one of %s" % sorted(ACTION_MODES))
+        b.set_option(A.OPT_ACTION_MODE, ACTION_MODES[action_mode])
+        self.action_mode = action_mode
         b.set_option(A.OPT_SEED, int(seed))
         b.set_option(A.OPT_ENV_OFFSET, int(env_offset))
         b.set_option(A.OPT_DIAGNOSTICS, 1 if diagnostics else 0)
@@ -399,8 +425,7 @@ class DPVecEnv(object):
             if not self.packed:
                 b.set_option(A.OPT_PACKED, 1)
             b.set_option(A.OPT_STEP_QUEUE, int(step_queue))
-        cr = self._cm.actuator_ctrlrange
-        self.action_space = Box(low=cr[:, 0], high=cr[:, 1], dtype=np.float32)
+        self.action_space = _action_space(self._cm, action_mode)
         self.observation_space = Box(low=-np.inf, high=np.inf, shape=(A.NOBS,), dtype=np.float32)
         self._pending = None
 

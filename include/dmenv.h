@@ -114,7 +114,19 @@ enum {
                                hinge triples; modes 3 and 4 need dm_mocap_set_imitation() */
   DM_OPT_AUTORESET = 2,   /* 0 off (default), 1 RSI on done, 2 noisy-init on done (DummyVecEnv convention) */
   DM_OPT_ACTION_MODE = 3, /* 0 raw ctrl (dp_env_v3.py:112, default), 1 P-control 0.8*(mocap_cfg - q) + action (env_torque_test.py:20),
-                             2 PD kp*(mocap_cfg - q) + kd*(mocap_vel - v) + action (setting_states.py:207-226, gains mocap_util.py:22-24) */
+                             2 PD kp*(mocap_cfg - q) + kd*(mocap_vel - v) + action (setting_states.py:207-226, gains mocap_util.py:22-24).
+                             Modes 1 and 2 add their feedback term, evaluated ONCE per env step, to an action that is a motor command.
+                             3 "spd-target": the action is a TARGET POSE qbar = action (28 absolute hinge angles, rad), target rate vbar = 0 —
+                             DeepMimic's action.  4 "spd-mocap": qbar = mocap_cfg[frame_idx][7:] + action, vbar = mocap_vel[frame_idx][6:]
+                             (frame_idx as at the start of the env step) — the stable form of mode 2.  In both a stable (implicit) PD controller
+                             (cImpPDController::CalcControlForces, code.md:147-179) turns the target into ctrl at the start of EVERY simulation
+                             substep, from the state (q, v) that substep starts at, and holds it through the substep; h = the timestep:
+                               p = kp (qbar - q - h v),  d = kd (vbar - v)   (hinge dofs; kp, kd as in mode 2; 0 on the root dofs)
+                               c = qfrc_bias - qfrc_passive,  a = (M + h diag(kd))^-1 (p + d - c)   (full 34 x 34 M; contacts ignored)
+                               tau = p + d - h kd a,  ctrl = tau / gear;  actuator force = gear * clamp(ctrl, ctrlrange)
+                             The target is not clamped.  DM_F_CTRL (and the control cost of reward modes 2 and 4) is the last substep's
+                             unclamped ctrl.  Modes 3 and 4 run on the per-step kernels, one-env and DM_OPT_PACKED, with or without the
+                             fused policy step; dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches for them (see there). */
   DM_OPT_SEED = 4,
   DM_OPT_DIAGNOSTICS = 5, /* 1 (default): every step also stores sim.data.xipos and the contact (geom1, geom2) list (DM_F_XIPOS,
                              DM_F_CONTACT_GEOMS: 848 B per env-step); 0: state, obs, reward, done and the row / contact counts only —
@@ -154,7 +166,8 @@ enum {
                              a view into them, a queued call's observations handed in as actions: a closed loop — first runs what is
                              queued, i.e. degenerates to one launch per call.  Results are bit-identical to unqueued DM_OPT_PACKED
                              steps.  Queuing applies where dm_batch_rollout uses one launch per horizon (DM_OPT_PACKED on, reward modes
-                             0..3, constraint rows, at most two packed waves per SIMD); elsewhere calls launch at once as without it.
+                             0..3, action modes 0..2, constraint rows, at most two packed waves per SIMD); elsewhere — action modes 3 and
+                             4 among it: nothing is queued, dm_batch_queue_stats stays 0 — calls launch at once as without it.
                              dm_batch_destroy() DROPS what is still queued (the buffers belong to the caller and may be gone). */
 };
 /* per-environment capacities of the DM_OPT_PACKED path (= csrc/slot_kernel.h SLOT_MAXROWS, SLOT_MAXLIMROWS, SLOT_MAXCON, SLOT_MAXFRAME, SLOT_MAXCAND) */
@@ -295,7 +308,8 @@ int dm_batch_step_act(dm_batch* b, const double* action, double* obs, double* re
  * horizon is ONE launch: every wavefront steps its four environments T times at its own pace, so the horizon lasts as long as the slowest
  * wave's sum over T steps instead of the sum of every step's slowest wave (4 096 envs: 17.3 M env-steps/s against 12.2 M through
  * dm_batch_step); an environment that exceeds the packed path's capacities in some step is re-stepped inside its wave by the one-env code.
- * Otherwise T step launches are issued. */
+ * Otherwise — always in action modes 3 and 4, whose controller lives in the per-step kernels — T step launches are issued: the results are those
+ * of T dm_batch_step / dm_batch_step_act calls, bit for bit. */
 int dm_batch_rollout(dm_batch* b, double* action, double* obs, double* reward, uint8_t* done, int32_t T, int32_t n_substeps,
                      const float* weights, float* vpred, int32_t stochastic, uint64_t seed, uint64_t counter);
 

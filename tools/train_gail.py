@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--num-timesteps", type=int, default=0, help="stop after this many timesteps of finished episodes (the reference's --num_timesteps)")
     ap.add_argument("--motion", default="walk")
+    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
+                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
     ap.add_argument("--reward", default="alive", help="the env's own reward (logged as EpTrueRewMean)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON")
@@ -65,13 +67,13 @@ def main():
         assert args.load_model_path, "--task %s needs --load-model-path" % args.task
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=0, reward=args.reward, autoreset="init", seed=args.seed)
+        env = DPVecEnv(args.number_trajs, motion=args.motion, device=0, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed)
         save = args.save_sample or ("sample.npz" if args.task == "sample" else None)
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=save)
         return
     assert args.expert_path, "--task train needs --expert-path"
     expert = ExpertDataset(args.expert_path, traj_limitation=args.traj_limitation, seed=args.seed, device=dev)
-    env = DPVecEnv(args.envs, motion=args.motion, device=0, reward=args.reward, autoreset="init", seed=args.seed)
+    env = DPVecEnv(args.envs, motion=args.motion, device=0, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed)
     pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed)
     if args.pretrained:                                     # src/gail.py:490-495
         t0 = time.time()

@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--no-native", action="store_true", help="the update through torch autograd instead of the dm_ppo_* kernels")
     ap.add_argument("--motion", default="walk")
     ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
+    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
+                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
     ap.add_argument("--autoreset", default="init", help="init (the reference's protocol) | rsi (DeepMimic reference-state initialisation)")
     ap.add_argument("--frame-skip", default=None, help="sim steps per env step, or 'mocap' (default: 1)")
     ap.add_argument("--seed", type=int, default=0)
@@ -73,10 +75,10 @@ def main():
         assert args.load_model_path, "--task evaluate needs --load-model-path"
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, autoreset="init", seed=args.seed, frame_skip=fs)
+        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed, frame_skip=fs)
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy)
         return
-    env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+    env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                    env_offset=rank * args.envs, frame_skip=fs)
     pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)

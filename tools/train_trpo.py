@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--max-kl", type=float, default=0.01)
     ap.add_argument("--motion", default="walk")
     ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
+    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
+                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
     ap.add_argument("--autoreset", default="init", help="init (the reference's trpo.py protocol) | rsi (DeepMimic reference-state initialisation)")
     ap.add_argument("--frame-skip", default=None, help="sim steps per env step, or 'mocap' (default: 1; 'mocap' with --reward imitation)")
     ap.add_argument("--pipeline", type=int, default=2, help="sub-batches whose step launches overlap across consecutive steps (DM_OPT_PIPELINE; with "
@@ -73,7 +75,7 @@ def main():
         assert args.load_model_path, "--task evaluate needs --load-model-path"
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, autoreset="init", seed=args.seed, frame_skip=fs)
+        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed, frame_skip=fs)
         writer = None
         if args.render_out:
             from deepmimic_mujoco_amd.render import FrameWriter
@@ -86,12 +88,12 @@ def main():
     P = max(1, args.pipeline)
     if args.unfused:
         cuts = [args.envs * h // P for h in range(P + 1)]
-        envs = [DPVecEnv(cuts[h + 1] - cuts[h], motion=args.motion, device=lr, reward=args.reward, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+        envs = [DPVecEnv(cuts[h + 1] - cuts[h], motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                          env_offset=rank * args.envs + cuts[h], frame_skip=fs) for h in range(P)]
         env = envs if P > 1 else envs[0]
     else:
         from deepmimic_mujoco_amd import _abi as A
-        env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+        env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                        env_offset=rank * args.envs, frame_skip=fs)
         env.batch.set_option(A.OPT_PIPELINE, min(P, A.MAX_PIPELINE))
     pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
