@@ -341,6 +341,41 @@ class Batch(object):
                                         ptrs["geom_xform"], kinds.pop()), self._L)
         return {k: out[k] for k in want}
 
+    def state_features(self, out=None, env_ids=None, qpos=None, qvel=None, phase=None):
+        """DeepMimic's state features through dm_batch_state_features (one launch; state_features.py has the layout): [n, 171]
+        float64.  Default: the batch's current state of every environment, or of `env_ids` [n]; with qpos [n,35], qvel [n,34] and
+        phase [n] (all three, env_ids must then be None): those states instead (mocap frames, recorded trajectories).  Like `step`,
+        the arrays are numpy arrays (host) or torch tensors on the batch's device (stream-ordered; no host wait, except that device
+        `env_ids` are first copied back and range-checked on the host, which waits for the stream).  Reads the batch, changes
+        nothing in it."""
+        explicit = [x is not None for x in (qpos, qvel, phase)]
+        if any(explicit) and not all(explicit):
+            raise ValueError("an explicit state needs qpos, qvel and phase")
+        if explicit[0] and env_ids is not None:
+            raise ValueError("an explicit state and env_ids exclude each other")
+        n = int(qpos.shape[0]) if explicit[0] else (int(len(env_ids)) if env_ids is not None else self.n)
+        ins = [qpos, qvel, phase, env_ids]
+        device = any(_is_torch(x) for x in ins + [out])
+        if out is None:
+            if device:
+                import torch
+                out = torch.empty((n, A.NSTATE), dtype=torch.float64, device="cuda:%d" % self.device)
+            else:
+                out = np.empty((n, A.NSTATE))
+        if device:
+            import torch
+            for i, dt in enumerate((np.float64, np.float64, np.float64, np.int32)):
+                if ins[i] is not None and not _is_torch(ins[i]):
+                    ins[i] = torch.as_tensor(np.ascontiguousarray(ins[i], dtype=dt), device="cuda:%d" % self.device)
+        op, kind, _ko = self._ptr(out, np.float64, (n, A.NSTATE), out=True)
+        qp, k1, _k1 = self._ptr(ins[0], np.float64, (n, A.NQ)); vp, k2, _k2 = self._ptr(ins[1], np.float64, (n, A.NV))
+        pp, k3, _k3 = self._ptr(ins[2], np.float64, (n,)); ip, k4, _k4 = self._ptr(ins[3], np.int32, (n,))
+        kinds = {kind} | ({k1, k2, k3} if explicit[0] else set()) | ({k4} if env_ids is not None else set())
+        if len(kinds) != 1:
+            raise ValueError("state_features buffers must be all numpy arrays or all device tensors")
+        A.check(self._L.dm_batch_state_features(self._h, qp, vp, pp, ip, n, op, kind), self._L)
+        return out
+
     def set_state(self, qpos, qvel, frame_idx=None, mask=None):
         n = self.n
         qp, k, _a = self._ptr(qpos, np.float64, (n, A.NQ)); vp, k2, _b = self._ptr(qvel, np.float64, (n, A.NV))

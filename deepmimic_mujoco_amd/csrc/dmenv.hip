@@ -21,6 +21,7 @@
 
 using namespace dm;
 #include "render_kernel.h"     // (written against namespace dm, like the kernels below)
+#include "state_kernel.h"
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
               DM_PACKED_MAXCAND == SLOT_MAXCAND, "include/dmenv.h documents the packed path's capacities: keep it in step with slot_kernel.h");
 // ============================================ kernels ======================================================
@@ -248,7 +249,7 @@ struct dm_batch {
   bool timing = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; float last_ms = 0.f; bool ev_pending = false;
   // pipelined sub-batches (DM_OPT_PIPELINE): the env range is cut into `pipe` contiguous parts, each stepped on its own stream
   int pipe = 1; hipStream_t ps[DM_MAX_PIPELINE] = {}; hipEvent_t ev_in = nullptr, ev_done[DM_MAX_PIPELINE] = {}; bool pipe_pending = false;
-  // dm_batch_render: view records and the staging of host arrays, grown on demand
+  // dm_batch_render: view records and the staging of host arrays, grown on demand (dm_batch_state_features stages host arrays in it too)
   unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
 };
 // make the batch's stream wait for every sub-batch launch still in flight (no host wait)
@@ -894,6 +895,59 @@ extern "C" int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* e
     if (depth) HIPCHK(hipMemcpyAsync(depth, ddep, npix * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     if (seg) HIPCHK(hipMemcpyAsync(seg, dseg, npix * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
     if (geom_xform) HIPCHK(hipMemcpyAsync(geom_xform, dxf, (size_t)n * NG * 12 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return DM_OK;
+}
+
+// ------------------------------------------------------------------ DeepMimic's state features (state_kernel.h)
+static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
+extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
+                                       double* out, int32_t kind) {
+  if (!b || !out) return fail(DM_EINVAL, "dm_batch_state_features: null argument");
+  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_state_features: bad ptr_kind");
+  if (n <= 0) return fail(DM_EINVAL, "dm_batch_state_features: n must be positive");
+  if ((qpos || qvel || phase) && !(qpos && qvel && phase)) return fail(DM_EINVAL, "dm_batch_state_features: an explicit state needs qpos, qvel and phase");
+  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_state_features: env_ids must be NULL when a state is given");
+  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_state_features: n exceeds the batch size");
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  const bool host = kind == DM_PTR_HOST;
+  // env ids are checked on the host (device ids are read back first)
+  if (env_ids) {
+    std::vector<int32_t> ids((size_t)n);
+    if (host) std::memcpy(ids.data(), env_ids, (size_t)n * sizeof(int32_t));
+    else { HIPCHK(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
+    for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= b->n) return fail(DM_EINVAL, "dm_batch_state_features: env id out of range");
+  }
+  const double *q = qpos, *qv = qvel, *ph = phase;
+  const int32_t* ids = env_ids;
+  double* o = out;
+  if (host) {      // staging: qpos | qvel | phase | env ids | out
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const size_t o_q = qpos ? take((size_t)n * NQ * sizeof(double)) : 0, o_v = qpos ? take((size_t)n * NV * sizeof(double)) : 0;
+    const size_t o_p = qpos ? take((size_t)n * sizeof(double)) : 0, o_id = env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
+    const size_t o_out = take((size_t)n * DM_NSTATE * sizeof(double));
+    if (off > b->rbuf_bytes) {
+      HIPCHK(hipStreamSynchronize(b->stream));       // (the old buffer may still be read by an earlier call)
+      if (b->d_rbuf) { HIPCHK(hipFree(b->d_rbuf)); b->d_rbuf = nullptr; b->rbuf_bytes = 0; }
+      if (hipMalloc((void**)&b->d_rbuf, off) != hipSuccess) { (void)hipGetLastError(); return fail(DM_ENOMEM, "dm_batch_state_features: hipMalloc failed"); }
+      b->rbuf_bytes = off;
+    }
+    unsigned char* base = b->d_rbuf;
+    if (qpos) {
+      HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q);
+      HIPCHK(hipMemcpyAsync(base + o_v, qvel, (size_t)n * NV * sizeof(double), hipMemcpyHostToDevice, b->stream)); qv = (const double*)(base + o_v);
+      HIPCHK(hipMemcpyAsync(base + o_p, phase, (size_t)n * sizeof(double), hipMemcpyHostToDevice, b->stream)); ph = (const double*)(base + o_p);
+    }
+    if (env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
+    o = (double*)(base + o_out);
+  }
+  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, q, qv, ph, (const int*)ids, (Ext*)o);
+  HIPCHK(hipGetLastError());
+  if (host) {
+    HIPCHK(hipMemcpyAsync(out, o, (size_t)n * DM_NSTATE * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
   }
   return DM_OK;

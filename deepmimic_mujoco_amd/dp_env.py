@@ -31,6 +31,7 @@ from .mjcf import load_mjcf, load_visual
 from .mocap import MocapDM
 from .model import CompiledModel
 from .spaces import Box
+from .state_features import obs_width
 
 REWARD_MODES = {"alive": 0, "v3-config": 1, "v2-pose": 2, "imitation": 3, "v1-quat": 4}
 
@@ -127,9 +128,14 @@ class DPEnv(object):
     reward_range = (-float("inf"), float("inf"))
     spec = None
 
-    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None, action_mode="raw"):
-        """action_mode: one of ACTION_MODES ("raw" is the reference's behaviour; "spd-target" / "spd-mocap" make the action a PD target pose)."""
+    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None, action_mode="raw", obs_mode="dp_env_v3"):
+        """action_mode: one of ACTION_MODES ("raw" is the reference's behaviour; "spd-target" / "spd-mocap" make the action a PD target pose).
+        obs_mode: "dp_env_v3" (default: the reference's 56 numbers) or "deepmimic": `reset`, `step`, `_get_obs` and `reset_model*` return DeepMimic's
+        171 state features (state_features.py) of the batch's state; their phase comes from the batch's cursor fields, which this class then writes from
+        `idx_curr` / `idx_init` before every features call — for reward "alive" too, whose cursor never advances: its phase is the RSI draw."""
         self.mocap = MocapDM()
+        obs_width(obs_mode)
+        self.obs_mode = obs_mode
         self._action_mode = action_mode
         if action_mode not in ACTION_MODES:
             raise ValueError("action_mode must be one of %s" % sorted(ACTION_MODES))
@@ -211,7 +217,13 @@ class DPEnv(object):
             self.sim = _SimView(self); self.data = self.sim.data
 
     def _get_obs(self):
+        if self.obs_mode == "deepmimic":
+            return self._features()[0].copy()
         return self._batch.get_obs()[0].copy()
+
+    def _features(self):
+        self._sync_frame_idx()                          # the phase is read from the batch's cursor (reward "alive" never writes it otherwise)
+        return self._batch.state_features()
 
     def reference_state_init(self):
         self.idx_init = random.randint(0, self.mocap_data_len - 1)
@@ -251,6 +263,8 @@ class DPEnv(object):
         obs, rew, done = self.do_simulation(action, 1)
         if self._reward_mode != 0:
             self.idx_curr = int(self._batch.get(A.F_FRAME_IDX)[0])
+        if self.obs_mode == "deepmimic":
+            obs = self._features()                        # of the state the step left, one more launch
         return obs[0].copy(), float(rew[0]), bool(done[0]), dict()
 
     def is_done(self):
@@ -347,7 +361,7 @@ class DPVecEnv(object):
 
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
-                 step_queue=0):
+                 step_queue=0, obs_mode="dp_env_v3"):
         """reward="imitation": the 5-term reward of code.md:1017-1143 (imitation.py) against the frame after the current one.
         frame_skip: sim steps per env step (src/dp_env_v3.py:108-112 hard-codes 1); "mocap" = floor(mocap_dt / timestep), the
         commented intent of :107-110, so that one env step spans one mocap frame.  Default (None): 1, except "mocap" for the
@@ -368,8 +382,16 @@ class DPVecEnv(object):
         action_mode: one of ACTION_MODES.  "spd-target" / "spd-mocap": the action is a PD target pose, tracked by a stable PD controller evaluated at every
         simulation substep (include/dmenv.h DM_OPT_ACTION_MODE); `action_space` is then the hinges' joint range ("spd-target") — informative, not enforced.
         These two modes run on the per-step kernels: horizon launches and the step queue fall back to step launches with identical results.
-        step_queue: DM_OPT_STEP_QUEUE depth (0 = off): queue `batch.step` calls and run them as one horizon launch (see below)."""
+        step_queue: DM_OPT_STEP_QUEUE depth (0 = off): queue `batch.step` calls and run them as one horizon launch (see below).
+        obs_mode: "dp_env_v3" (default: the 56 numbers the step launch writes; nothing else is launched) or "deepmimic": `reset`, `step` and `step_wait` return
+        [N, 171] DeepMimic state features (state_features.py) and `observation_space` has shape (171,).  A step is then the step launch into an internal
+        56-wide buffer plus one features launch on the same stream, which reads the state after the step: with `autoreset`, a done environment's row is
+        the fresh episode's features — the convention of the 56-wide observation.  The features call runs queued steps first, so with `step_queue`
+        every `step` is executed at once, as in the closed loop."""
         self.num_envs = int(num_envs)
+        self.obs_mode = obs_mode
+        self._obs_width = obs_width(obs_mode)
+        self._ob56 = None
         self.mocap = MocapDM()
         self.mocap.load_mocap(motion)
         self.mocap_dt = self.mocap.dt
@@ -426,7 +448,7 @@ class DPVecEnv(object):
                 b.set_option(A.OPT_PACKED, 1)
             b.set_option(A.OPT_STEP_QUEUE, int(step_queue))
         self.action_space = _action_space(self._cm, action_mode)
-        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(A.NOBS,), dtype=np.float32)
+        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self._obs_width,), dtype=np.float32)
         self._pending = None
 
     @property
@@ -443,13 +465,40 @@ class DPVecEnv(object):
 
     def reset(self, mode="rsi", out=None):
         self._batch.reset(mode={"rsi": 0, "init": 1, "qpos0": 2}[mode], hard=1)
+        if self.obs_mode == "deepmimic":
+            return self._batch.state_features(out)
         return self._batch.get_obs(out)
+
+    def _step_features(self, actions, out):
+        """a step in obs_mode "deepmimic": the step launch writes its 56 numbers into an internal buffer, the features launch the [N, 171] rows"""
+        b = self._batch
+        if out is None:
+            _o56, rew, done = b.step(actions, self.frame_skip)
+            obs = None
+            if type(rew).__module__.startswith("torch"):
+                import torch
+                obs = torch.empty((self.num_envs, self._obs_width), dtype=torch.float64, device=rew.device)
+        else:
+            obs, rew, done = out
+            o56 = self._ob56
+            if o56 is None or type(o56) is not type(rew) or getattr(o56, "device", None) != getattr(rew, "device", None):
+                if type(rew).__module__.startswith("torch"):
+                    import torch
+                    o56 = torch.empty((self.num_envs, A.NOBS), dtype=torch.float64, device=rew.device)
+                else:
+                    o56 = np.empty((self.num_envs, A.NOBS))
+                self._ob56 = o56
+            b.step(actions, self.frame_skip, (o56, rew, done))
+        return b.state_features(obs), rew, done
 
     def step_async(self, actions):
         self._pending = actions
 
     def step_wait(self, out=None):
-        obs, rew, done = self._batch.step(self._pending, self.frame_skip, out)
+        if self.obs_mode == "deepmimic":
+            obs, rew, done = self._step_features(self._pending, out)
+        else:
+            obs, rew, done = self._batch.step(self._pending, self.frame_skip, out)
         self._pending = None
         if getattr(self._batch, "_queue_refs", None) is not None:
             self._batch.join()      # OPT_STEP_QUEUE: the call was only queued, and what this method returns is read in stream order

@@ -28,6 +28,9 @@ class RolloutBlock(object):
 
     def append(self, obs, action, reward, done, vpred=None):
         row = self.buf[self.t]
+        if obs.shape[-1] != 56:
+            raise ValueError("the rollout block's row is 87 wide (56 obs | 28 act | reward | done | vpred): observations of width %d (obs_mode "
+                             "'deepmimic') are not gathered" % obs.shape[-1])
         row[:, :56] = obs; row[:, 56:84] = action; row[:, 84] = reward; row[:, 85] = done
         if vpred is not None:
             row[:, 86] = vpred
@@ -93,7 +96,7 @@ def can_fuse(pi, env, device=None):
     import torch
     device = torch.device(pi.device if device is None else device)
     return (device.type == "cuda" and getattr(pi, "native", False) and hasattr(getattr(env, "batch", None), "step_act")
-            and getattr(env.batch, "can_step_act", True) and getattr(pi, "ob_dim", 0) == 56 and getattr(pi, "ac_dim", 0) == 28 and getattr(pi, "hid_size", 0) == 100)
+            and getattr(env.batch, "can_step_act", True) and getattr(env, "obs_mode", "dp_env_v3") == "dp_env_v3" and getattr(pi, "ob_dim", 0) == 56 and getattr(pi, "ac_dim", 0) == 28 and getattr(pi, "hid_size", 0) == 100)
 
 
 class _PendingEpisodes:
@@ -187,7 +190,10 @@ class SegmentCollector(object):
         device = torch.device(pi.device if device is None else device)
         self.device = device
         f32, f64 = torch.float32, torch.float64
-        self.ob64 = torch.zeros((T + 1, n, 56), dtype=f64, device=device)         # row t: observation the policy sees at step t
+        self.ob_width = int(env.observation_space.shape[0]) if getattr(env, "obs_mode", "dp_env_v3") != "dp_env_v3" else 56
+        self.ob64 = torch.zeros((T + 1, n, self.ob_width), dtype=f64, device=device)   # row t: observation the policy sees at step t
+        # obs_mode "deepmimic": the step launch writes its 56 numbers here, then dm_batch_state_features fills the segment's row from the state it left
+        self.ob56 = torch.zeros((n, 56), dtype=f64, device=device) if self.ob_width != 56 else None
         self.ac64 = torch.zeros((T + 1, n, 28), dtype=f64, device=device)         # row T: the action already drawn for ob64[T] (fused path)
         self.rew64 = torch.zeros((T, n), dtype=f64, device=device)
         self.done8 = torch.zeros((T, n), dtype=torch.uint8, device=device)
@@ -261,7 +267,11 @@ class SegmentCollector(object):
                 return
             for t in range(T):
                 pi.act(self.stochastic, ob64[t], out=ac64[t], vpred_out=vpreds[t])                       # :49
-                env.batch.step(as_buf(ac64[t]), fs, (as_buf(ob64[t + 1]), as_buf(rew64[t]), as_buf(done8[t])))   # :66, one launch
+                if self.ob56 is None:
+                    env.batch.step(as_buf(ac64[t]), fs, (as_buf(ob64[t + 1]), as_buf(rew64[t]), as_buf(done8[t])))   # :66, one launch
+                else:
+                    env.batch.step(as_buf(ac64[t]), fs, (as_buf(self.ob56), as_buf(rew64[t]), as_buf(done8[t])))
+                    env.batch.state_features(as_buf(ob64[t + 1]))
             vpreds[T] = pi.forward(ob64[T])[1]                                      # value of the observation after the segment (:49-52);
         # the action for it is sampled at the top of the next segment, i.e. from the policy as updated in between
 
@@ -503,13 +513,17 @@ class DoubleBufferedGather:
     copied to pinned host memory (stream-ordered), the gather runs between host buffers (async, gloo's own threads) and the
     result stays on the host in `gathered_host[k]` — the path the world-2 tests and single-GPU multi-rank runs use."""
 
-    def __init__(self, horizon, n_local, device="cpu", world=None, collective=None):
-        """collective: run the multi-rank code path (two blocks, the all-gather into `gathered`) — default: when the process group has more
+    def __init__(self, horizon, n_local, device="cpu", world=None, collective=None, ob_width=56):
+        """ob_width: the width of the observations the caller will write into the rows; the 87-wide row holds 56 (obs_mode "dp_env_v3") and nothing else.
+        collective: run the multi-rank code path (two blocks, the all-gather into `gathered`) — default: when the process group has more
         than one rank; True forces it for a group of ONE rank, which executes the same RCCL calls where only one GPU is visible."""
         import torch
         import torch.distributed as dist
         if world is None:
             world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+        if int(ob_width) != 56:
+            raise ValueError("the gathered rollout row is 87 wide (56 obs | 28 act | reward | done | vpred): observations of width %d (obs_mode "
+                             "'deepmimic') are not gathered" % int(ob_width))
         self.T, self.n, self.world = int(horizon), int(n_local), int(world)
         self.collective = (self.world > 1) if collective is None else bool(collective)
         nb = 2 if self.collective else 1

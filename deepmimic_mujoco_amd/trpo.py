@@ -781,7 +781,10 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
         frames.add(env.batch.render(render_size[0], render_size[1], render_camera, env_ids=np.zeros(1, dtype=np.int32))["rgb"][0])
     dev = pi.device
     with torch.no_grad():
-        ob = torch.zeros((n, 56), dtype=torch.float64, device=dev)
+        space = getattr(env, "observation_space", None)
+        if space is not None and int(space.shape[0]) != pi.ob_dim:
+            raise ValueError("the policy takes observations of width %d, the environment gives %d (obs_mode)" % (pi.ob_dim, int(space.shape[0])))
+        ob = torch.zeros((n, pi.ob_dim), dtype=torch.float64, device=dev)
         env.reset("init", out=ob if ob.is_cuda else ob.numpy())
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         ep_len = torch.zeros(n, dtype=torch.int64, device=dev); ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 8
+#define DM_ABI_VERSION 9
 
 /* fixed sizes of the DeepMimic humanoid (dp_env_v3.xml:21-156): the kernels are specialised to this tree */
 #define DM_NBODY 14
@@ -32,6 +32,7 @@ extern "C" {
 #define DM_NU 28
 #define DM_NGEOM 16
 #define DM_NOBS 56
+#define DM_NSTATE 171 /* DeepMimic's state features (dm_batch_state_features): 1 + 1 + 13 * 7 + 13 * 6 */
 #define DM_MAXPAIR 128
 #define DM_MAXEFC 64   /* lanes of the per-env wavefront = stride of the per-row arrays */
 #define DM_MAXROWS 63  /* constraint rows per environment held on chip (one lane each; the 64th lane carries the smooth force);
@@ -268,6 +269,34 @@ typedef struct {
  * 1..4096, n W H >= 2^31, fovy outside (0, 180), no output. */
 int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, const dm_render_desc* d, uint8_t* rgb,
                     float* depth, int32_t* seg, double* geom_xform, int32_t ptr_kind);
+
+/* DeepMimic's state features of n humanoid states (cCtController::BuildStatePose / BuildStateVel, code.md:307-489):
+ * the observation the imitation task was designed around — where dm_batch_step's 56 numbers (hinge angles and rates) carry neither the
+ * root's height or orientation, nor the bodies' positions, nor the position in the clip.  out [n, DM_NSTATE] float64, one row per state.
+ * Coordinates are the model's (z up, x forward); bodies are model bodies b = 1..13 in model order (the root first), k = b - 1:
+ *   [0]                 phase in [0, 1)
+ *   [1]                 root height: z of the root body's frame origin (xpos[1][2] = qpos[2])
+ *   [2 + 7k .. +3]      Rz(-hd) (xipos_b - xpos_root): the body's centre of mass relative to the root's frame origin, in the heading frame
+ *                       (the root's own entry is its centre-of-mass offset, not a special case)
+ *   [2 + 7k + 3 .. +4]  q_z(-hd) (x) xquat_b as (w, x, y, z), negated as a whole when w < 0 (code.md:406-412)
+ *   [93 + 6k .. +3]     Rz(-hd) v_b, v_b the world velocity of the point xipos_b
+ *   [93 + 6k + 3 .. +3] Rz(-hd) w_b, w_b the body's world angular velocity
+ * Heading: hd = atan2(f_y, f_x) with f the root's x axis in the world (the root quaternion is normalised first) — the heading of the
+ * imitation reward's end-effector features.  qvel[0:3] is the world velocity of the root's frame origin, qvel[3:6] the root's angular
+ * velocity in its own frame (MuJoCo's free joint).  Upstream's defaults otherwise: no flip_stance, mRecordWorldRootPos / Rot off.
+ * The sign rule is discontinuous where the heading-frame quaternion's w crosses 0.
+ * qpos == NULL: the batch's current states of env_ids[0..n) (env_ids NULL: envs 0..n-1, n <= the batch size); the phase comes from the
+ * batch's cursor fields: frame_idx / n_frames in reward modes 0, 1 and 3 (mode 0 never advances the cursor: the phase stays the RSI
+ * draw), ((frame_idx + frame_init) mod n_frames) / n_frames in modes 2 and 4.  In mode 4 that is the STEP cursor: it is the mocap frame
+ * only when one env step spans one mocap frame.  qpos [n,35] non-NULL: explicit states — qvel [n,34] and phase [n] must be given too, and
+ * env_ids must be NULL (mocap frames, recorded trajectories).
+ * One launch on the batch's stream; ptr_kind applies to every array.  Device arrays are stream-ordered with no host wait, except env_ids:
+ * device env_ids are read back and range-checked on the host first (one copy and a wait for the stream), as dm_batch_render does.  Queued steps run and pipelined sub-batches join first, so the
+ * features are those of the latest step (after an auto-reset: of the fresh episode's state, like a step's observation).  Read-only: the
+ * call reads qpos, qvel, the two cursor fields and the reward mode and changes no batch state.  DM_EINVAL: n <= 0, n beyond the batch
+ * without qpos, an env id out of range, a partial explicit state, env_ids with an explicit state, a bad ptr_kind. */
+int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
+                            double* out, int32_t ptr_kind);
 
 /* kernel timing of the last dm_batch_step launch, measured with HIP events on the batch's stream (ms) */
 int dm_batch_last_step_ms(dm_batch* b, float* ms);

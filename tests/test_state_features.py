@@ -1,0 +1,189 @@
+"""DeepMimic's state features without a GPU: the float64 restatement (tests/state_numpy.py) against analysis, csrc/state_features.h
+built for the host against that restatement, and the ABI.  The host build is fed `CompiledModel.kinematics`' frame origins, centres of
+mass and dof axes; that code keeps rotation matrices only, so the body quaternions it is fed are the restatement's own (checked against
+those matrices in test_restatement_agrees_with_the_package_kinematics): of the quaternion block the host test checks the heading
+product and the sign rule, not the composition down the tree — that is the kernel's kinematics, checked on the GPU against the same
+restatement (tests/test_gpu_state.py)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from deepmimic_mujoco_amd import _abi as A
+from tests import helpers as H
+from tests import state_numpy as SN
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CLIPS = ("walk", "spinkick", "dance_b")
+
+
+def bar_states():
+    """the inputs of the bar tests: every frame of the three clips with its data_vel, then varied_states(256, seed=3)"""
+    qs, vs = [], []
+    for clip in CLIPS:
+        mc = H.mocap(clip)
+        qs.append(mc.data_config); vs.append(mc.data_vel)
+    _idx, q, v, _ws, _ctrl = H.varied_states(256, seed=3)
+    qs.append(q); vs.append(v)
+    q = np.concatenate(qs); v = np.concatenate(vs)
+    phase = (np.arange(len(q)) % 97) / 97.0
+    return q, v, phase
+
+
+def quat_z(a):
+    return np.array([np.cos(0.5 * a), 0, 0, np.sin(0.5 * a)])
+
+
+def rot_z(a):
+    return np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1.0]])
+
+
+def integrate(q, v, eps):
+    """qpos after eps seconds at constant qvel: MuJoCo's free joint (world linear, body-local angular velocity), then the hinges"""
+    out = q.copy()
+    out[0:3] += eps * v[0:3]
+    th = eps * np.linalg.norm(v[3:6])
+    dq = np.array([1.0, 0, 0, 0]) if th == 0 else np.concatenate([[np.cos(0.5 * th)], np.sin(0.5 * th) * v[3:6] / np.linalg.norm(v[3:6])])
+    rq = q[3:7] / np.linalg.norm(q[3:7])
+    out[3:7] = SN.qmul(rq, dq)
+    out[7:] += eps * v[6:]
+    return out
+
+
+# ---- the restatement against analysis ---------------------------------------------------------------------------------------------
+def test_restated_velocities_are_the_derivative_of_the_kinematics():
+    cm = H.compiled_model()
+    _idx, qs, vs, _ws, _ctrl = H.varied_states(24, seed=5)
+    eps = 1e-6
+    for q, v in zip(qs, vs):
+        vb, _wb = SN.body_velocities(cm, q, v)
+        xp = cm.kinematics(integrate(q, v, eps))[2]
+        xm = cm.kinematics(integrate(q, v, -eps))[2]
+        np.testing.assert_allclose(vb[1:], ((xp - xm) / (2 * eps))[1:], atol=1e-6, rtol=0)
+
+
+def test_restatement_agrees_with_the_package_kinematics():
+    cm = H.compiled_model()
+    _idx, qs, _vs, _ws, _ctrl = H.varied_states(16, seed=7)
+    for q in qs:
+        xpos, xquat, xipos, axes, anchors = SN.kinematics(cm, q)
+        cx, cmat, cxi, caxes, canch, _rot = cm.kinematics(q)
+        np.testing.assert_allclose(xpos, cx, atol=1e-12); np.testing.assert_allclose(xipos, cxi, atol=1e-12)
+        np.testing.assert_allclose(axes, caxes, atol=1e-12); np.testing.assert_allclose(anchors[3:], canch[3:], atol=1e-12)
+        for b in range(1, cm.nbody):
+            np.testing.assert_allclose(np.stack([SN.qrot(xquat[b], e) for e in np.eye(3)], 1), cmat[b], atol=1e-12)
+
+
+def test_features_ignore_a_root_shift_and_a_rotation_about_the_vertical():
+    cm = H.compiled_model()
+    _idx, qs, vs, _ws, _ctrl = H.varied_states(16, seed=9)
+    keep = np.arange(SN.NSTATE) != SN.O_HEIGHT
+    for i, (q, v) in enumerate(zip(qs, vs)):
+        f0 = SN.features(cm, q, v, 0.25)
+        assert f0[SN.O_HEIGHT] == q[2] and f0[SN.O_PHASE] == 0.25
+        q1 = q.copy(); q1[0] += 3.7; q1[1] -= 12.2
+        np.testing.assert_allclose(SN.features(cm, q1, v, 0.25)[keep], f0[keep], atol=1e-12, rtol=0)
+        a = 0.4 + 0.9 * i
+        q2 = q.copy(); v2 = v.copy()
+        q2[0:3] = rot_z(a) @ q[0:3]; q2[3:7] = SN.qmul(quat_z(a), q[3:7]); v2[0:3] = rot_z(a) @ v[0:3]
+        np.testing.assert_allclose(SN.features(cm, q2, v2, 0.25), f0, atol=1e-12, rtol=0)
+
+
+def test_rest_pose_has_rest_rotations_and_no_velocity():
+    cm = H.compiled_model()
+    f = SN.features(cm, cm.qpos0, np.zeros(cm.nv), 0.0)
+    for k in range(SN.NBODY):
+        np.testing.assert_allclose(f[SN.QUAT_IDX[k]], [1.0, 0, 0, 0], atol=1e-15)     # (the model's bodies carry no rest rotation)
+        np.testing.assert_allclose(f[SN.O_POS + 7 * k:SN.O_POS + 7 * k + 3], cm.kinematics(cm.qpos0)[2][k + 1] - cm.qpos0[0:3], atol=1e-15)
+    assert not f[SN.O_VEL:].any() and f[SN.O_HEIGHT] == cm.qpos0[2]
+
+
+def test_restated_phase_rule():
+    assert SN.phase_of(0, 7, 3, 20) == 7 / 20.0 and SN.phase_of(1, 19, 5, 20) == 19 / 20.0 and SN.phase_of(3, 0, 9, 20) == 0.0
+    assert SN.phase_of(2, 7, 3, 20) == 10 / 20.0 and SN.phase_of(2, 18, 5, 20) == 3 / 20.0
+    assert SN.phase_of(4, 45, 3, 20) == 8 / 20.0 and SN.phase_of(4, 0, 19, 20) == 19 / 20.0
+
+
+def test_bar_inputs_stay_clear_of_the_quaternion_sign_flip():
+    cm = H.compiled_model()
+    q, v, phase = bar_states()
+    ref = SN.batch_features(cm, q, v, phase)
+    w = np.abs(ref[:, SN.QUAT_IDX[:, 0]])
+    assert (w < SN.W_SMALL).sum() <= 1e-3 * w.size
+    assert w.min() > 1e-3                          # (1.4e-3 on the varied states, 3.4e-3 on the clips)
+
+
+# ---- the package's layout and phase rule ------------------------------------------------------------------------------------------
+def test_package_layout_and_phase_of():
+    from deepmimic_mujoco_amd import state_features as SF
+    assert (SF.NSTATE, SF.O_PHASE, SF.O_HEIGHT, SF.O_POS, SF.O_VEL) == (SN.NSTATE, SN.O_PHASE, SN.O_HEIGHT, SN.O_POS, SN.O_VEL) == (171, 0, 1, 2, 93)
+    rng = np.random.RandomState(0)
+    for mode in range(5):
+        n = 20 + 7 * mode
+        idx = rng.randint(0, n if mode in (0, 1, 3) else 5 * n, size=32); init = rng.randint(0, n, size=32)
+        want = np.array([SN.phase_of(mode, i, j, n) for i, j in zip(idx, init)])
+        np.testing.assert_array_equal(SF.phase_of(mode, idx, init, n), want)
+        assert SF.phase_of(mode, int(idx[0]), int(init[0]), n) == want[0]
+    assert SF.phase_of("v2-pose", 18, 5, 20) == 3 / 20.0 and SF.phase_of("imitation", 18, 5, 20) == 18 / 20.0
+    assert SF.obs_width("dp_env_v3") == 56 and SF.obs_width("deepmimic") == 171
+    with pytest.raises(ValueError):
+        SF.obs_width("deep-mimic")
+
+
+# ---- csrc/state_features.h on the host --------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def state_host(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler to build tests/state_host.cpp")
+    out = str(tmp_path_factory.mktemp("state_host") / "state_host")
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), os.path.join(ROOT, "tests", "state_host.cpp"), "-o", out])
+    return out
+
+
+def host_features(exe, cm, q, v, phase, tmp_path, f32=False):
+    """csrc/state_features.h on cm.kinematics' frame origins, centres of mass and dof axes (+ the restatement's body quaternions:
+    the model code keeps rotation matrices only)"""
+    vals = [float(len(q))]
+    for i in range(len(q)):
+        xpos, _xmat, xipos, axes, _anchors, _rot = cm.kinematics(q[i])
+        xquat = SN.kinematics(cm, q[i])[1]
+        vals += list(xpos.reshape(-1)) + list(xquat.reshape(-1)) + list(xipos.reshape(-1)) + list(axes.reshape(-1)) + list(v[i]) + [phase[i]]
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    np.asarray(vals, dtype=np.float64).tofile(fin)
+    subprocess.check_call([exe, fin, fout] + (["32"] if f32 else []))
+    return np.fromfile(fout, dtype=np.float64).reshape(len(q), SN.NSTATE)
+
+
+def test_state_features_h_on_the_host_matches_the_restatement(state_host, tmp_path):
+    cm = H.compiled_model()
+    q, v, phase = bar_states()
+    ref = SN.batch_features(cm, q, v, phase)
+    got = host_features(state_host, cm, q, v, phase, tmp_path)
+    fails, e_pose, e_vel, loose = SN.compare(got, ref, 1e-12, 1e-12)
+    print("host float64: worst pose error %.3e, worst velocity error %.3e, %d pairs compared up to sign" % (e_pose, e_vel * 1e-12, loose))
+    assert loose <= 1e-3 * len(q) * SN.NBODY
+    assert not fails, fails[:10]
+
+
+def test_state_features_h_in_float_stays_inside_the_float32_bars(state_host, tmp_path):
+    """the header's arithmetic in float on float64 kinematics: the part of the float32 library's error that is this file's"""
+    cm = H.compiled_model()
+    q, v, phase = bar_states()
+    ref = SN.batch_features(cm, q, v, phase)
+    got = host_features(state_host, cm, q, v, phase, tmp_path, f32=True)
+    fails, e_pose, e_vel, loose = SN.compare(got, ref, 1e-5, 1e-5 * np.maximum(1.0, np.abs(v).sum(1)))
+    print("host float32: worst pose error %.3e, worst velocity error %.3f of its bar" % (e_pose, e_vel))
+    assert not fails, fails[:10]
+
+
+# ---- the ABI ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [64, 32])
+def test_both_libraries_export_the_entry_point(dtype):
+    L = A.load(dtype)
+    assert L.dm_abi_version() == 9 == A.ABI_VERSION and A.NSTATE == 171
+    assert "dm_batch_state_features" in A.EXPORTS and hasattr(L, "dm_batch_state_features")
+    hdr = open(os.path.join(ROOT, "include", "dmenv.h")).read()
+    assert "#define DM_ABI_VERSION 9" in hdr and "#define DM_NSTATE 171" in hdr and "int dm_batch_state_features(" in hdr

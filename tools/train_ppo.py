@@ -44,6 +44,10 @@ def main():
     ap.add_argument("--no-native", action="store_true", help="the update through torch autograd instead of the dm_ppo_* kernels")
     ap.add_argument("--motion", default="walk")
     ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
+    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
+                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
+                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
+                         "env; at 171 the learners run on their torch paths")
     ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
                     help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
     ap.add_argument("--autoreset", default="init", help="init (the reference's protocol) | rsi (DeepMimic reference-state initialisation)")
@@ -75,12 +79,12 @@ def main():
         assert args.load_model_path, "--task evaluate needs --load-model-path"
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed, frame_skip=fs)
+        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed, frame_skip=fs)
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy)
         return
-    env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+    env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                    env_offset=rank * args.envs, frame_skip=fs)
-    pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
+    pi = MlpPolicy(ob_dim=env.observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     schedule = args.schedule or ("linear" if "max_timesteps" in stop else "constant")
     hist = learn(env, pi, timesteps_per_batch=args.horizon, clip_param=args.clip_param, entcoeff=args.entcoeff, optim_epochs=args.optim_epochs,

@@ -28,6 +28,10 @@ def main():
     ap.add_argument("--max-kl", type=float, default=0.01)
     ap.add_argument("--motion", default="walk")
     ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
+    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
+                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
+                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
+                         "env; at 171 the learners run on their torch paths")
     ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
                     help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
     ap.add_argument("--autoreset", default="init", help="init (the reference's trpo.py protocol) | rsi (DeepMimic reference-state initialisation)")
@@ -75,7 +79,7 @@ def main():
         assert args.load_model_path, "--task evaluate needs --load-model-path"
         pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
         pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset="init", seed=args.seed, frame_skip=fs)
+        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed, frame_skip=fs)
         writer = None
         if args.render_out:
             from deepmimic_mujoco_amd.render import FrameWriter
@@ -88,15 +92,15 @@ def main():
     P = max(1, args.pipeline)
     if args.unfused:
         cuts = [args.envs * h // P for h in range(P + 1)]
-        envs = [DPVecEnv(cuts[h + 1] - cuts[h], motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+        envs = [DPVecEnv(cuts[h + 1] - cuts[h], motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                          env_offset=rank * args.envs + cuts[h], frame_skip=fs) for h in range(P)]
         env = envs if P > 1 else envs[0]
     else:
         from deepmimic_mujoco_amd import _abi as A
-        env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
+        env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
                        env_offset=rank * args.envs, frame_skip=fs)
         env.batch.set_option(A.OPT_PIPELINE, min(P, A.MAX_PIPELINE))
-    pi = MlpPolicy(device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
+    pi = MlpPolicy(ob_dim=(envs[0] if args.unfused else env).observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     hist = learn(env, pi, timesteps_per_batch=args.horizon, max_seconds=args.seconds if not args.iters else 0, max_iters=args.iters,
                  vf_batch_size=args.vf_batch, vf_stepsize=args.vf_stepsize, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir,
                  fused=False if args.unfused else None, pg_native=False if args.no_pg_native else None)
