@@ -6,14 +6,15 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
-SOURCES = ["dmenv.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "packed_body.h", "kernels.h", "env_kernel.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h"]
+SOURCES = ["dmenv.hip", "views.hip", "learner.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "packed_body.h", "host_common.h", "batch_host.h", "kernels.h", "env_kernel.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h"]
 OUT = os.path.join(HERE, "libdmenv.so")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-shift-count-negative", "-Wno-implicit-const-int-float-conversion"]
-# Two translation units, each with the backend options its kernels want (round 4, A/B in profiles/r04_ab_kernel_variants.md):
+# Seven translation units (kernels.h lists them), each with the backend options its kernels want (round 4, A/B in profiles/r04_ab_kernel_variants.md):
 #   kernels_packed.hip — four environments per wavefront: ONE wave per SIMD with the whole register file.  The default scheduling strategy (max-occupancy: keep
 #                        register pressure low) buys nothing there; scheduling for instruction-level parallelism hides more of a lone wave's LDS / f64 latencies
 #                        (+1.0 .. +1.6 % env-steps/s), register-class priority in the greedy allocator +0.4 %.
-#   dmenv.hip          — the one-env step kernels (two waves per SIMD at 256 registers: 2 % SLOWER under max-ilp), everything else, the C ABI: defaults.
+#   dmenv.hip          — the one-env step kernels (two waves per SIMD at 256 registers: 2 % SLOWER under max-ilp), the reset / state / view kernels, the batch half of
+#                        the C ABI: defaults.  views.hip (render / state features, host side) and learner.hip (the learner kernels and their entry points): defaults too.
 # Neither option touches floating-point semantics: results are bit-identical.
 #                        -enable-ipra (round 6): inter-procedural register allocation — the horizon launch's called step bodies (internal functions, slot_step.h
 #                        DM_CALL_SLOT) are compiled without callee-saved registers: no 337-register save / restore per call, +3.7 % (profiles/r06_ab_kernel_variants.md §4).
@@ -27,7 +28,7 @@ ROLLOUT_FLAGS = PACKED_FLAGS + ["-mllvm", "-amdgpu-load-store-vectorizer=false",
 if os.environ.get("DM_ROLLOUT_FLAGS") is not None:
     ROLLOUT_FLAGS = os.environ["DM_ROLLOUT_FLAGS"].split()
 #   kernels_spd.hip / kernels_packed_spd.hip — the step kernels of action modes 3 and 4, with the options of the units whose kernels they mirror.
-UNITS = [("dmenv.hip", []), ("kernels_packed.hip", PACKED_FLAGS), ("kernels_rollout.hip", ROLLOUT_FLAGS), ("kernels_spd.hip", []), ("kernels_packed_spd.hip", PACKED_FLAGS)]
+UNITS = [("dmenv.hip", []), ("views.hip", []), ("learner.hip", []), ("kernels_packed.hip", PACKED_FLAGS), ("kernels_rollout.hip", ROLLOUT_FLAGS), ("kernels_spd.hip", []), ("kernels_packed_spd.hip", PACKED_FLAGS)]
 
 
 def hipcc():

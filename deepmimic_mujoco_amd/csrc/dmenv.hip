@@ -1,11 +1,8 @@
-// dmenv.hip — libdmenv.so: HIP kernels (gfx950) + the C ABI of include/dmenv.h.
-//
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -I../../include dmenv.hip -o libdmenv.so
+// dmenv.hip — libdmenv.so: the one-env step kernels of action modes 0..2, the reset / state / ordering kernels, and the batch half of the C ABI of
+// include/dmenv.h: models, mocap tables and batches, options, state, step / rollout / queue, profiling and timing.  (views.hip: render and state
+// features, whose kernels are compiled here; learner.hip: the learner half; kernels.h lists the units.)
 // There is no CPU execution path in this library: every entry point that computes runs a HIP kernel.
-#include <cstddef>
-#include <hip/hip_runtime.h>
-
-#include <cmath>
+#define DM_NO_LAUNCH_KERNELS
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,15 +10,15 @@
 #include <string>
 #include <vector>
 
-#include "kernels.h"
-#include "vf_kernel.h"
-#include "pg_kernel.h"
-#include "disc_kernel.h"
+#include "batch_host.h"
 #include "model_host.h"
 
 using namespace dm;
-#include "render_kernel.h"     // (written against namespace dm, like the kernels below)
+// the kernels of views.hip's entry points (written against namespace dm, like the kernels below) stay in this unit, beside the step kernels whose
+// kinematics they share: in a unit of their own k_state_features and k_render_pose came out as different code objects (profiles/host_split.md)
+#include "render_kernel.h"
 #include "state_kernel.h"
+static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
               DM_PACKED_MAXCAND == SLOT_MAXCAND, "include/dmenv.h documents the packed path's capacities: keep it in step with slot_kernel.h");
 // ============================================ kernels ======================================================
@@ -212,60 +209,10 @@ __global__ __launch_bounds__(64) void k_debug_forward(const DevModel<Real>* __re
 }
 
 // ============================================ host side ====================================================
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(DM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+thread_local std::string g_err;
 
 struct dm_model { DevModel<Real> h; };
 struct dm_mocap { std::vector<double> cfg, vel, imit_table, imit_params; int n_frames; double dt; };
-struct dm_batch {
-  int n = 0, device = 0;
-  hipStream_t stream = nullptr; bool own_stream = false;
-  DevModel<Real>* d_model = nullptr;
-  Batch<Real> B{};
-  Batch<Real>* d_B = nullptr;   // a copy of B in device memory for the horizon launch (refreshed before each: its code is reached through calls, which take a pointer)
-  Real *d_cfg = nullptr, *d_vel = nullptr, *d_imit = nullptr; int* d_order = nullptr;
-  // self-ordering per-step launches (env_step.h dispatch_env): per pipelined part three phases of 64 bucket counters, and three phases of bucket
-  // lists ([phase][bucket][n], a part's entries at its first env); ord_phase = the phase the part's last launch counted into, valid once one did
-  int* d_ord_cnt = nullptr; int* d_ord_list = nullptr; int ord_phase[DM_MAX_PIPELINE] = {}; bool ord_valid[DM_MAX_PIPELINE] = {};
-  // staging for DM_PTR_HOST callers
-  Ext *d_action = nullptr, *d_obs = nullptr, *d_reward = nullptr; unsigned char *d_done = nullptr, *d_mask = nullptr;
-  // host-pointer steps: obs | reward | done are ONE device block (d_obs points at its start) mirrored in pinned host memory, so a
-  // step costs one H2D (action, from the pinned mirror) and one D2H instead of one pageable copy per array
-  unsigned char* h_out = nullptr; Ext* h_action = nullptr; size_t out_bytes = 0;
-  Ext* d_cvt = nullptr;   // float32 build: float64 staging for field reads / writes through host pointers
-  Ext *d_qpos_in = nullptr, *d_qvel_in = nullptr; int* d_fidx_in = nullptr;
-  double* d_debug = nullptr;
-  long long* d_prof = nullptr; bool prof = false;
-  int redo_phase = 0;    // which of a sub-batch's two redo counters the next packed launch counts into
-  int redo_mode = -1;    // 1 / 0: the last packed step was / was not pipelined (the counter pairs are re-zeroed when that changes)
-  // DM_OPT_STEP_QUEUE: dm_batch_step calls with device pointers are queued (nothing is launched) and executed together — one horizon launch,
-  // every wave at its own pace — when the queue is full or any other entry point of the batch is called (dm_batch_join, ...)
-  int queue_cap = 0; std::vector<StepRow> q; int q_nsub = 1; StepRow* d_rows = nullptr; int rows_cap = 0; long long queue_flushes = 0, queue_steps = 0;
-  int horizon_mode = -1; // option 106: dm_batch_rollout on the packed path as ONE launch per horizon (1), as step launches (0), by batch size (-1, default)
-  bool packed = false;   // option 105: four environments per wavefront (k_step_packed) where that kernel covers the configuration
-  bool packed_ext = false;   // DM_OPT_PACKED = 2: per-step packed launches with the three-set code (k_step_packed_ext: 40 rows per env, ~8 % slower otherwise)
-  bool two_tier = true, reorder = true, has_rows = true; int resident_waves = 2048;   // CUs x 8 single-wave workgroups (LDS-limited)
-  bool timing = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; float last_ms = 0.f; bool ev_pending = false;
-  // pipelined sub-batches (DM_OPT_PIPELINE): the env range is cut into `pipe` contiguous parts, each stepped on its own stream
-  int pipe = 1; hipStream_t ps[DM_MAX_PIPELINE] = {}; hipEvent_t ev_in = nullptr, ev_done[DM_MAX_PIPELINE] = {}; bool pipe_pending = false;
-  // dm_batch_render: view records and the staging of host arrays, grown on demand (dm_batch_state_features stages host arrays in it too)
-  unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
-};
-// make the batch's stream wait for every sub-batch launch still in flight (no host wait)
-static int pipe_join(dm_batch* b) {
-  if (!b->pipe_pending) return DM_OK;
-  for (int h = 0; h < b->pipe; h++) if (hipStreamWaitEvent(b->stream, b->ev_done[h], 0) != hipSuccess) return DM_EHIP;
-  b->pipe_pending = false;
-  return DM_OK;
-}
-
-static int flush_queue(dm_batch* b);
-// what every entry point other than a queued dm_batch_step does first: run the queued steps, then make the batch's stream wait for the sub-batch launches
-static int settle(dm_batch* b) {
-  if (!b->q.empty()) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
-  return pipe_join(b);
-}
 
 extern "C" const char* dm_last_error(void) { return g_err.c_str(); }
 extern "C" int dm_abi_version(void) { return DM_ABI_VERSION; }
@@ -452,14 +399,6 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
   return DM_OK;
 }
 
-static int stage_in(dm_batch* b, void* dst, const void* src, size_t bytes, int kind, const void** use) {
-  if (!src) { *use = nullptr; return DM_OK; }
-  if (kind == DM_PTR_DEVICE) { *use = src; return DM_OK; }
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b->stream));
-  *use = dst;
-  return DM_OK;
-}
-
 extern "C" int dm_batch_set_state(dm_batch* b, const double* qpos, const double* qvel, const int32_t* fidx, const uint8_t* mask, int32_t kind) {
   if (!b || !qpos || !qvel) return fail(DM_EINVAL, "dm_batch_set_state: null argument");
   HIPCHK(hipSetDevice(b->device));
@@ -533,7 +472,7 @@ static int launch_horizon(dm_batch* b, int T, int nsub, const dmp::PolicyArgs& p
   HIPCHK(hipGetLastError());
   return DM_OK;
 }
-static int flush_queue(dm_batch* b) {
+int flush_queue(dm_batch* b) {
   const int T = (int)b->q.size();
   if (T == 0) return DM_OK;
   HIPCHK(hipSetDevice(b->device));
@@ -575,6 +514,32 @@ static int ord_bind(dm_batch* b, Batch<Real>& Bh, int h, int lo, hipStream_t st)
 }
 static void ord_commit(dm_batch* b, int h) { b->ord_phase[h] = (b->ord_phase[h] + 1) % 3; b->ord_valid[h] = true; }
 
+// the bytes of a dm_batch_step call's buffers overlap the bytes of ANY buffer of a queued call, in whatever role: the same tensors step after step, a view that
+// starts elsewhere in one of them, a queued call's observations handed in as this call's action
+static bool overlaps_queued(const dm_batch* b, const double* action, const double* obs, const double* reward, const uint8_t* done) {
+  const size_t n = (size_t)b->n;
+  const char* p[4] = {(const char*)action, (const char*)obs, (const char*)reward, (const char*)done};
+  const size_t len[4] = {n * NU * sizeof(Ext), n * NOBS * sizeof(Ext), n * sizeof(Ext), n};
+  for (const StepRow& r : b->q) {
+    const char* qp[4] = {(const char*)r.action, (const char*)r.obs, (const char*)r.reward, (const char*)r.done};
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) if (p[i] < qp[j] + len[j] && qp[j] < p[i] + len[i]) return true;
+  }
+  return false;
+}
+
+// the kernels of a step call: action modes 3 and 4 have their own instantiations (kernels_spd.hip, kernels_packed_spd.hip), DM_OPT_PACKED = 2 the packed
+// kernels with the three-set code; every one is launched exactly like its counterpart
+struct StepKernels {
+  decltype(&k_step_packed) packed; decltype(&k_step_packed_act) packed_act; decltype(&k_step_packed_prof) packed_prof;
+  decltype(&k_step_redo) redo; decltype(&k_step_narrow) narrow; decltype(&k_step_act) act; decltype(&k_step) single; decltype(&k_step_prof) prof;
+};
+static StepKernels step_kernels(bool spd, bool ext) {
+  if (spd) return {ext ? k_step_packed_ext_spd : k_step_packed_spd, ext ? k_step_packed_act_ext_spd : k_step_packed_act_spd, k_step_packed_prof_spd,
+                   k_step_redo_spd, k_step_narrow_spd, k_step_act_spd, k_step_spd, k_step_prof_spd};
+  return {ext ? k_step_packed_ext : k_step_packed, ext ? k_step_packed_act_ext : k_step_packed_act, k_step_packed_prof,
+          k_step_redo, k_step_narrow, k_step_act, k_step, k_step_prof};
+}
+
 static int step_impl(dm_batch* b, const double* action, double* obs, double* reward, uint8_t* done, int32_t nsub, int32_t kind, const dmp::PolicyArgs* pol) {
   if (!b || !action || !obs || !reward || !done || nsub < 1) return fail(DM_EINVAL, "dm_batch_step: bad argument");
   if (pol && (kind != DM_PTR_DEVICE || b->prof || !b->two_tier)) return fail(DM_EINVAL, "dm_batch_step_act: device pointers, the two-tier kernel and no profiling");
@@ -583,27 +548,13 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     // DM_OPT_STEP_QUEUE: remember the call; the queued steps run as ONE horizon launch (flush_queue).  A call that names a buffer an
     // earlier queued call names (the same action / output tensors step after step) runs that earlier call first: a caller that reuses
     // buffers has, by the pipelined contract, joined in between and sees plain step-by-step behaviour.
-    // "names a buffer" = its bytes overlap the bytes of ANY buffer of a queued call, in whatever role: the same tensors step after step, a view that
-    // starts elsewhere in one of them, a queued call's observations handed in as this call's action.
-    bool reuse = nsub != b->q_nsub && !b->q.empty();
-    {
-      const size_t n = (size_t)b->n;
-      const char* p[4] = {(const char*)action, (const char*)obs, (const char*)reward, (const char*)done};
-      const size_t len[4] = {n * NU * sizeof(Ext), n * NOBS * sizeof(Ext), n * sizeof(Ext), n};
-      for (const StepRow& r : b->q) {
-        const char* qp[4] = {(const char*)r.action, (const char*)r.obs, (const char*)r.reward, (const char*)r.done};
-        for (int i = 0; i < 4 && !reuse; i++) for (int j = 0; j < 4; j++) {
-          if (p[i] < qp[j] + len[j] && qp[j] < p[i] + len[i]) { reuse = true; break; }
-        }
-        if (reuse) break;
-      }
-    }
+    const bool reuse = (nsub != b->q_nsub && !b->q.empty()) || overlaps_queued(b, action, obs, reward, done);
     if (reuse || (int)b->q.size() >= b->queue_cap) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
     b->q.push_back(StepRow{action, obs, reward, done}); b->q_nsub = nsub;
     return DM_OK;
   }
   if (!b->q.empty()) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
-  const void* a = action;
+  const Ext* a = action;
   if (kind == DM_PTR_HOST) {
     memcpy(b->h_action, action, (size_t)b->n * NU * sizeof(Ext));
     HIPCHK(hipMemcpyAsync(b->d_action, b->h_action, (size_t)b->n * NU * sizeof(Ext), hipMemcpyHostToDevice, b->stream));
@@ -616,21 +567,9 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   if (!piped && pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
   if (b->timing) { if (b->ev_pending) { hipEventSynchronize(b->ev1); hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1); } if (!piped) HIPCHK(hipEventRecord(b->ev0, b->stream)); }
   const bool reorder = b->reorder && b->has_rows && b->n > b->resident_waves;   // more envs than resident waves: later rounds exist, their tail matters
-  // the packed kernel covers: models without constraint rows, reward modes alive / v3-config / v2-pose, no fused policy step
-  const bool packed_step = b->packed && b->B.reward_mode <= 4 && b->two_tier;      // this call runs on the packed kernels (profiled or not)
-  const bool use_packed = packed_step && !b->prof;
-  const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
-  // the kernels of this call: action modes 3 and 4 have their own instantiations (kernels_spd.hip, kernels_packed_spd.hip), launched exactly like the others
-  const bool spd = b->B.action_mode >= 3;
-  const auto kn_packed = spd ? (b->packed_ext ? k_step_packed_ext_spd : k_step_packed_spd) : (b->packed_ext ? k_step_packed_ext : k_step_packed);
-  const auto kn_packed_act = spd ? (b->packed_ext ? k_step_packed_act_ext_spd : k_step_packed_act_spd) : (b->packed_ext ? k_step_packed_act_ext : k_step_packed_act);
-  const auto kn_packed_prof = spd ? k_step_packed_prof_spd : k_step_packed_prof;
-  const auto kn_redo = spd ? k_step_redo_spd : k_step_redo;
-  const auto kn_narrow = spd ? k_step_narrow_spd : k_step_narrow;
-  const auto kn_act = spd ? k_step_act_spd : k_step_act;
-  const auto kn_single = spd ? k_step_spd : k_step;
-  const auto kn_prof = spd ? k_step_prof_spd : k_step_prof;
-  if (packed_step) {
+  const bool packed = packed_covers(b);      // this call runs on the packed kernels (profiled or not)
+  const StepKernels K = step_kernels(b->B.action_mode >= 3, b->packed_ext);
+  if (packed) {
     const int mode = piped ? 1 : 0;
     if (mode != b->redo_mode) {      // (rare: the first packed step, or a host-pointer step between pipelined ones; every earlier launch is ordered before this stream here)
       if (piped && pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
@@ -638,14 +577,28 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       b->redo_mode = mode; b->redo_phase = 0;
     }
   }
+  // The launches of one part [lo, lo + count) of the batch (a pipelined sub-batch, or the whole batch) on stream `st`, with the descriptor Bp.  Packed: the
+  // packed kernel counts the environments beyond its capacities into the first counter of `pair` (this call's phase), the redo launch steps them one
+  // per wave and clears the other one for the next call.
+  auto launch_part = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count, int* pair, const dmp::PolicyArgs* pa) {
+    constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
+    const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
+    if (packed) {
+      const dim3 grid((count + SLOTS - 1) / SLOTS);
+      int* rc = pair + b->redo_phase; int* rn = pair + (1 - b->redo_phase);
+      if (b->prof) hipLaunchKernelGGL(K.packed_prof, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, b->d_prof);
+      else if (pa) hipLaunchKernelGGL(K.packed_act, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, *pa);
+      else hipLaunchKernelGGL(K.packed, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc);
+      if (b->has_rows) hipLaunchKernelGGL(K.redo, dim3(REDO_BLOCKS), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pa ? *pa : nopol);
+    }
+    else if (pa) hipLaunchKernelGGL(K.act, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, *pa);
+    else hipLaunchKernelGGL(K.narrow, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count);
+  };
   unsigned ord_bound = 0;               // parts whose launch of this call took a ticket descriptor (committed below, after the launches went out)
-  constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
-  if (b->prof && packed_step) {
+  if (b->prof && packed) {
     HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
-    int* rc = b->B.redo_count + b->redo_phase; int* rn = b->B.redo_count + (1 - b->redo_phase);
-    hipLaunchKernelGGL(kn_packed_prof, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, b->d_prof);
-    if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, nopol);
-  } else if (b->prof) hipLaunchKernelGGL(kn_prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub, b->d_prof);
+    launch_part(b->stream, b->B, 0, b->n, b->B.redo_count, nullptr);
+  } else if (b->prof) hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof);
   else if (piped) {
     // Sub-batch h's launch of THIS call depends on its own launch of the previous call (stream order on ps[h]) and on the
     // caller's inputs (ev_in), not on the other sub-batches: while the last, cheap workgroups of one sub-batch drain, the
@@ -659,14 +612,7 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       Batch<Real> Bh = b->B;                                                   // this part's launch orders itself from the tickets its previous launch left
       if (reorder) { const int rc2 = ord_bind(b, Bh, h, lo, b->ps[h]); if (rc2 != DM_OK) return rc2; ord_bound |= 1u << h; }
       if (b->timing && h == 0) HIPCHK(hipEventRecord(b->ev0, b->ps[0]));     // timing: sub-batch 0's kernel on ITS stream
-      if (use_packed) {
-        int* rc = b->B.redo_count + 2 * h + b->redo_phase; int* rn = b->B.redo_count + 2 * h + (1 - b->redo_phase);
-        if (pol) hipLaunchKernelGGL(kn_packed_act, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc, *pol);
-        else hipLaunchKernelGGL(kn_packed, dim3((hi - lo + SLOTS - 1) / SLOTS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, rc);
-        if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pol ? *pol : nopol);
-      }
-      else if (pol) hipLaunchKernelGGL(kn_act, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo, *pol);
-      else hipLaunchKernelGGL(kn_narrow, dim3(hi - lo), dim3(64), 0, b->ps[h], b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, lo, hi - lo);
+      launch_part(b->ps[h], Bh, lo, hi - lo, b->B.redo_count + 2 * h, pol);
       if (b->timing && h == 0) { HIPCHK(hipEventRecord(b->ev1, b->ps[0])); b->ev_pending = true; }
       HIPCHK(hipEventRecord(b->ev_done[h], b->ps[h]));
     }
@@ -678,20 +624,13 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     //  results do not depend on the dispatch order; include/dmenv.h says so.)
     Batch<Real> Bh = b->B;
     if (reorder && b->pipe <= 1) { const int rc2 = ord_bind(b, Bh, 0, 0, b->stream); if (rc2 != DM_OK) return rc2; ord_bound |= 1u; }
-    if (use_packed) {
-      // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of counters is clean — pair 0's
-      //  two are cleared here once if a pipelined step used them before)
-      int* rc = b->B.redo_count + b->redo_phase; int* rn = b->B.redo_count + (1 - b->redo_phase);
-      if (pol) hipLaunchKernelGGL(kn_packed_act, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc, *pol);
-      else hipLaunchKernelGGL(kn_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, rc);
-      if (b->has_rows) hipLaunchKernelGGL(kn_redo, dim3(REDO_BLOCKS), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, (const int*)rc, rn, pol ? *pol : nopol);
-    }
-    else if (pol) hipLaunchKernelGGL(kn_act, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n, *pol);
-    else hipLaunchKernelGGL(kn_narrow, dim3(b->n), dim3(64), 0, b->stream, b->d_model, Bh, (const Ext*)a, o, r, dn, (int)nsub, 0, b->n);
-  } else hipLaunchKernelGGL(kn_single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const Ext*)a, o, r, dn, (int)nsub);
+    // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of redo counters is clean — pair 0's
+    //  two are cleared above once if a pipelined step used them before)
+    launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, pol);
+  } else hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub);
   HIPCHK(hipGetLastError());
   for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
-  if (packed_step) b->redo_phase ^= 1;
+  if (packed) b->redo_phase ^= 1;
   if (b->timing && !piped) { HIPCHK(hipEventRecord(b->ev1, b->stream)); b->ev_pending = true; }
   if (kind == DM_PTR_HOST) {
     HIPCHK(hipMemcpyAsync(b->h_out, b->d_obs, b->out_bytes, hipMemcpyDeviceToHost, b->stream));
@@ -822,137 +761,6 @@ extern "C" int dm_batch_debug_forward(dm_batch* b, int32_t env, double* out_host
   return DM_OK;
 }
 
-// ------------------------------------------------------------------ rendering (render_kernel.h)
-extern "C" int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, const dm_render_desc* d, uint8_t* rgb,
-                               float* depth, int32_t* seg, double* geom_xform, int32_t kind) {
-  if (!b || !d) return fail(DM_EINVAL, "dm_batch_render: null argument");
-  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_render: bad ptr_kind");
-  if (n <= 0) return fail(DM_EINVAL, "dm_batch_render: n must be positive");
-  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_render: env_ids must be NULL when qpos is given");
-  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_render: n exceeds the batch size");
-  const int W = d->width, H = d->height;
-  if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(DM_EINVAL, "dm_batch_render: width and height must be 1..4096");
-  const size_t npix = (size_t)n * W * H;
-  if (npix >= (size_t)1 << 31) return fail(DM_EINVAL, "dm_batch_render: n * width * height must stay below 2^31");
-  if (!(d->fovy > 0 && d->fovy < 180)) return fail(DM_EINVAL, "dm_batch_render: fovy must lie in (0, 180) degrees");
-  if (!rgb && !depth && !seg && !geom_xform) return fail(DM_EINVAL, "dm_batch_render: no output requested");
-  const double ln = std::sqrt(d->light_dir[0] * d->light_dir[0] + d->light_dir[1] * d->light_dir[1] + d->light_dir[2] * d->light_dir[2]);
-  if (!(ln > 0)) return fail(DM_EINVAL, "dm_batch_render: light_dir must be nonzero");
-  if (!(d->floor_square > 0)) return fail(DM_EINVAL, "dm_batch_render: floor_square must be positive");
-  HIPCHK(hipSetDevice(b->device));
-  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  const bool host = kind == DM_PTR_HOST;
-  // scratch: records | qpos | env ids | (host outputs) rgb | depth | seg | xform
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_rec = take((size_t)n * sizeof(dmr::ViewRec));
-  const size_t o_q = host && qpos ? take((size_t)n * NQ * sizeof(double)) : 0;
-  const size_t o_id = host && env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
-  const size_t o_rgb = host && rgb ? take(npix * 3) : 0;
-  const size_t o_dep = host && depth ? take(npix * sizeof(float)) : 0;
-  const size_t o_seg = host && seg ? take(npix * sizeof(int32_t)) : 0;
-  const size_t o_xf = host && geom_xform ? take((size_t)n * NG * 12 * sizeof(double)) : 0;
-  if (off > b->rbuf_bytes) {
-    HIPCHK(hipStreamSynchronize(b->stream));       // (the old buffer may still be read by an earlier render)
-    if (b->d_rbuf) { HIPCHK(hipFree(b->d_rbuf)); b->d_rbuf = nullptr; b->rbuf_bytes = 0; }
-    if (hipMalloc((void**)&b->d_rbuf, off) != hipSuccess) { (void)hipGetLastError(); return fail(DM_ENOMEM, "dm_batch_render: hipMalloc failed"); }
-    b->rbuf_bytes = off;
-  }
-  unsigned char* base = b->d_rbuf;
-  // env ids are checked on the host (device ids are read back first)
-  if (env_ids) {
-    std::vector<int32_t> ids((size_t)n);
-    if (host) std::memcpy(ids.data(), env_ids, (size_t)n * sizeof(int32_t));
-    else { HIPCHK(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
-    for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= b->n) return fail(DM_EINVAL, "dm_batch_render: env id out of range");
-  }
-  const double* q = qpos;
-  const int32_t* ids = env_ids;
-  if (host && qpos) { HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q); }
-  if (host && env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
-  unsigned char* drgb = host && rgb ? base + o_rgb : rgb;
-  float* ddep = host && depth ? (float*)(base + o_dep) : depth;
-  int32_t* dseg = host && seg ? (int32_t*)(base + o_seg) : seg;
-  double* dxf = host && geom_xform ? (double*)(base + o_xf) : geom_xform;
-  dmr::ViewRec* rec = (dmr::ViewRec*)(base + o_rec);
-  dmr::Camera cam{};
-  for (int k = 0; k < 3; k++) cam.pos[k] = d->cam_pos[k];
-  for (int k = 0; k < 9; k++) cam.mat[k] = d->cam_mat[k];
-  cam.track_com = d->track_com != 0;
-  hipLaunchKernelGGL(k_render_pose, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, q, (const int*)ids, cam, rec, dxf);
-  HIPCHK(hipGetLastError());
-  if (drgb || ddep || dseg) {
-    const dmr::Params P = dmr::make_params(*d);
-    const int tiles_x = (W + 15) / 16, tiles = tiles_x * ((H + 15) / 16);
-    for (int v0 = 0; v0 < n; v0 += 65535) {
-      const int nv = n - v0 < 65535 ? n - v0 : 65535;
-      hipLaunchKernelGGL(k_render_rays, dim3(tiles, nv), dim3(256), 0, b->stream, (const dmr::ViewRec*)rec, P, tiles_x, v0, drgb, ddep, (int*)dseg);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  if (host) {
-    if (rgb) HIPCHK(hipMemcpyAsync(rgb, drgb, npix * 3, hipMemcpyDeviceToHost, b->stream));
-    if (depth) HIPCHK(hipMemcpyAsync(depth, ddep, npix * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    if (seg) HIPCHK(hipMemcpyAsync(seg, dseg, npix * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    if (geom_xform) HIPCHK(hipMemcpyAsync(geom_xform, dxf, (size_t)n * NG * 12 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return DM_OK;
-}
-
-// ------------------------------------------------------------------ DeepMimic's state features (state_kernel.h)
-static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
-extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
-                                       double* out, int32_t kind) {
-  if (!b || !out) return fail(DM_EINVAL, "dm_batch_state_features: null argument");
-  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_state_features: bad ptr_kind");
-  if (n <= 0) return fail(DM_EINVAL, "dm_batch_state_features: n must be positive");
-  if ((qpos || qvel || phase) && !(qpos && qvel && phase)) return fail(DM_EINVAL, "dm_batch_state_features: an explicit state needs qpos, qvel and phase");
-  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_state_features: env_ids must be NULL when a state is given");
-  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_state_features: n exceeds the batch size");
-  HIPCHK(hipSetDevice(b->device));
-  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  const bool host = kind == DM_PTR_HOST;
-  // env ids are checked on the host (device ids are read back first)
-  if (env_ids) {
-    std::vector<int32_t> ids((size_t)n);
-    if (host) std::memcpy(ids.data(), env_ids, (size_t)n * sizeof(int32_t));
-    else { HIPCHK(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
-    for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= b->n) return fail(DM_EINVAL, "dm_batch_state_features: env id out of range");
-  }
-  const double *q = qpos, *qv = qvel, *ph = phase;
-  const int32_t* ids = env_ids;
-  double* o = out;
-  if (host) {      // staging: qpos | qvel | phase | env ids | out
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-    const size_t o_q = qpos ? take((size_t)n * NQ * sizeof(double)) : 0, o_v = qpos ? take((size_t)n * NV * sizeof(double)) : 0;
-    const size_t o_p = qpos ? take((size_t)n * sizeof(double)) : 0, o_id = env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
-    const size_t o_out = take((size_t)n * DM_NSTATE * sizeof(double));
-    if (off > b->rbuf_bytes) {
-      HIPCHK(hipStreamSynchronize(b->stream));       // (the old buffer may still be read by an earlier call)
-      if (b->d_rbuf) { HIPCHK(hipFree(b->d_rbuf)); b->d_rbuf = nullptr; b->rbuf_bytes = 0; }
-      if (hipMalloc((void**)&b->d_rbuf, off) != hipSuccess) { (void)hipGetLastError(); return fail(DM_ENOMEM, "dm_batch_state_features: hipMalloc failed"); }
-      b->rbuf_bytes = off;
-    }
-    unsigned char* base = b->d_rbuf;
-    if (qpos) {
-      HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q);
-      HIPCHK(hipMemcpyAsync(base + o_v, qvel, (size_t)n * NV * sizeof(double), hipMemcpyHostToDevice, b->stream)); qv = (const double*)(base + o_v);
-      HIPCHK(hipMemcpyAsync(base + o_p, phase, (size_t)n * sizeof(double), hipMemcpyHostToDevice, b->stream)); ph = (const double*)(base + o_p);
-    }
-    if (env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
-    o = (double*)(base + o_out);
-  }
-  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, q, qv, ph, (const int*)ids, (Ext*)o);
-  HIPCHK(hipGetLastError());
-  if (host) {
-    HIPCHK(hipMemcpyAsync(out, o, (size_t)n * DM_NSTATE * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return DM_OK;
-}
-
 extern "C" int dm_batch_read_profile(dm_batch* b, long long* out_host) {   /* [N,8]: kin, mass, bias, rows, constraint, total, nefc, iters */
   if (!b || !out_host || !b->d_prof) return fail(DM_EINVAL, "profile not enabled");
   HIPCHK(hipStreamSynchronize(b->stream));
@@ -968,343 +776,6 @@ extern "C" int dm_batch_last_step_ms(dm_batch* b, float* ms) {
   HIPCHK(hipEventSynchronize(b->ev1));
   HIPCHK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
   *ms = b->last_ms;
-  return DM_OK;
-}
-extern "C" int dm_policy_weight_count(void) { return dmp::N_WEIGHTS; }
-extern "C" int dm_policy_act(const float* weights, const double* obs, double* action, float* vpred, int32_t n, int32_t stochastic,
-                             uint64_t seed, uint64_t counter, void* hip_stream) {
-  if (!weights || !obs || !action || !vpred || n <= 0) return fail(DM_EINVAL, "dm_policy_act: bad argument");
-  hipLaunchKernelGGL(dmp::k_policy_act, dim3((n + dmp::EB - 1) / dmp::EB), dim3(256), 0, (hipStream_t)hip_stream, weights, obs, action, vpred,
-                     (int)n, (int)stochastic, (unsigned long long)seed, (unsigned long long)counter);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_gae(const float* rew, const float* vpred, const int32_t* isnew, const float* nextvpred, float* adv, float* tdlamret,
-                      int32_t T, int32_t n, double gamma, double lam, void* hip_stream) {
-  if (!rew || !vpred || !isnew || !nextvpred || !adv || !tdlamret || T <= 0 || n <= 0) return fail(DM_EINVAL, "dm_gae: bad argument");
-  hipLaunchKernelGGL(dmp::k_gae, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, rew, vpred, (const int*)isnew, nextvpred, adv,
-                     tdlamret, (int)T, (int)n, (float)gamma, (float)lam);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-static int pg_set_device(const void* p);
-extern "C" int dm_episode_scan(const double* reward, const uint8_t* done, int32_t T, int32_t n, double* cur_ret, int64_t* cur_len, int32_t* count,
-                               int32_t cap, int64_t* records, void* hip_stream) {
-  if (!reward || !done || !cur_ret || !cur_len || !count || !records || T <= 0 || n <= 0 || cap < 0) return fail(DM_EINVAL, "dm_episode_scan: bad argument");
-  if (pg_set_device(reward)) return fail(DM_EHIP, "dm_episode_scan: hipSetDevice failed");      // (the launches go to the device that owns the arrays, whatever the thread's current one)
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIPCHK(hipMemsetAsync(count, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(dmp::k_episodes, dim3((n + 255) / 256), dim3(256), 0, st, reward, done, (int)T, (int)n, cur_ret, (long long*)cur_len, (int*)count, (int)cap,
-                     (long long*)records);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_vf_param_count(void) { return dmv::NP; }
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-struct VfScratch { size_t partial, rpart, part_all, means, stds, total; };
-static VfScratch vf_scratch_layout(int nb, int bs) {
-  const size_t ntile = (size_t)((bs + dmv::SB - 1) / dmv::SB);
-  VfScratch L;
-  size_t o = 0;
-  L.partial = o; o += up256(ntile * dmv::NPAD * sizeof(float));
-  L.rpart = o; o += up256((size_t)dmv::RMS_BLOCKS * 2 * dmv::OB * sizeof(double) + 64);          // + the ticket of the three-launch form
-  L.part_all = o; o += up256((size_t)nb * dmv::RMS_BLOCKS * 2 * dmv::OB * sizeof(double));
-  L.means = o; o += up256((size_t)nb * dmv::OB * sizeof(float));
-  L.stds = o; o += up256((size_t)nb * dmv::OB * sizeof(float));
-  L.total = o;
-  return L;
-}
-extern "C" size_t dm_vf_scratch_bytes(int32_t nb, int32_t bs) { return vf_scratch_layout(nb < 1 ? 1 : nb, bs < 1 ? 1 : bs).total; }
-extern "C" int dm_vf_fit_epoch(const float* ob, const float* ret, int32_t nb, int32_t bs, float* theta, float* adam_m, float* adam_v,
-                               const float* step_scale_host, double beta1, double beta2, double eps, double* rms_sum, double* rms_sumsq,
-                               double* rms_count, float* rms_mean, float* rms_std, void* scratch, void* hip_stream, int32_t epoch_filter) {
-  if (!ob || !ret || !theta || !adam_m || !adam_v || !step_scale_host || !rms_sum || !rms_sumsq || !rms_count || !rms_mean || !rms_std || !scratch ||
-      nb < 1 || bs < 1)
-    return fail(DM_EINVAL, "dm_vf_fit_epoch: bad argument");
-  hipStream_t st = (hipStream_t)hip_stream;
-  { // launch on the device that owns the parameters (the caller's stream belongs to it), whatever the thread's current device is
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, theta) == hipSuccess) HIPCHK(hipSetDevice(at.device));
-    else (void)hipGetLastError();
-  }
-  const VfScratch L = vf_scratch_layout(nb, bs);
-  const int nblk = (bs + dmv::SB - 1) / dmv::SB;
-  char* base = (char*)scratch;
-  float* partial = (float*)(base + L.partial);
-  if (epoch_filter) {
-    // the obs filter's sums of every minibatch up front and their scan (csrc/vf_kernel.h); per minibatch: gradient partials, reduction + Adam
-    double* part_all = (double*)(base + L.part_all);
-    float* means = (float*)(base + L.means); float* stds = (float*)(base + L.stds);
-    hipLaunchKernelGGL(dmv::k_vf_rms_part, dim3(dmv::RMS_BLOCKS, nb), dim3(256), 0, st, ob, (int)bs, part_all);
-    hipLaunchKernelGGL(dmv::k_vf_rms_fold, dim3(nb), dim3(128), 0, st, part_all);
-    hipLaunchKernelGGL(dmv::k_vf_rms_scan, dim3(1), dim3(64), 0, st, (const double*)part_all, (int)nb, (int)bs, rms_sum, rms_sumsq, rms_count, rms_mean, rms_std, means, stds);
-    for (int i = 0; i < nb; i++) {
-      hipLaunchKernelGGL(dmv::k_vf_grad, dim3(nblk), dim3(256), 0, st, ob + (size_t)i * bs * dmv::OB, ret + (size_t)i * bs, (int)bs, (const float*)theta,
-                         (const float*)(means + (size_t)i * dmv::OB), (const float*)(stds + (size_t)i * dmv::OB), partial);
-      hipLaunchKernelGGL(dmv::k_vf_adam, dim3((dmv::NP + dmv::ADAM_PARAMS - 1) / dmv::ADAM_PARAMS), dim3(256), 0, st, (const float*)partial, nblk, theta, adam_m, adam_v,
-                         step_scale_host[i], (float)beta1, (float)beta2, (float)eps);
-    }
-    HIPCHK(hipGetLastError());
-    return DM_OK;
-  }
-  double* rpart = (double*)(base + L.rpart);
-  unsigned* ticket = (unsigned*)(rpart + dmv::RMS_BLOCKS * 2 * dmv::OB);
-  HIPCHK(hipMemsetAsync(ticket, 0, sizeof(unsigned), st));
-  for (int i = 0; i < nb; i++) {
-    const float* mbob = ob + (size_t)i * bs * dmv::OB;
-    const float* mbret = ret + (size_t)i * bs;
-    hipLaunchKernelGGL(dmv::k_vf_rms, dim3(dmv::RMS_BLOCKS), dim3(256), 0, st, mbob, (int)bs, rpart, ticket, rms_sum, rms_sumsq, rms_count, rms_mean, rms_std);
-    hipLaunchKernelGGL(dmv::k_vf_grad, dim3(nblk), dim3(256), 0, st, mbob, mbret, (int)bs, (const float*)theta, (const float*)rms_mean,
-                       (const float*)rms_std, partial);
-    hipLaunchKernelGGL(dmv::k_vf_adam, dim3((dmv::NP + dmv::ADAM_PARAMS - 1) / dmv::ADAM_PARAMS), dim3(256), 0, st, (const float*)partial, nblk, theta, adam_m, adam_v,
-                       step_scale_host[i], (float)beta1, (float)beta2, (float)eps);
-    HIPCHK(hipGetLastError());
-  }
-  return DM_OK;
-}
-// the obs filter's update with a whole batch (src/trpo.py:242 `pi.ob_rms.update(ob)`): k_vf_rms on a grid sized to the batch — one launch
-constexpr int RMS_UPDATE_BLOCKS = 256;              // (the last block adds the partials up column by column: 32 rounds of 8 loads)
-extern "C" size_t dm_rms_scratch_bytes(void) { return (size_t)RMS_UPDATE_BLOCKS * 2 * dmv::OB * sizeof(double) + 64; }
-extern "C" int dm_rms_update(const float* ob, int32_t n, double* rms_sum, double* rms_sumsq, double* rms_count, float* rms_mean, float* rms_std,
-                             void* scratch, void* hip_stream) {
-  if (!ob || n < 1 || !rms_sum || !rms_sumsq || !rms_count || !rms_mean || !rms_std || !scratch) return fail(DM_EINVAL, "dm_rms_update: bad argument");
-  if (pg_set_device(ob)) return fail(DM_EHIP, "dm_rms_update: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  int blocks = (n + 255) / 256;                               // >= 64 rows per row group of a block
-  if (blocks > RMS_UPDATE_BLOCKS) blocks = RMS_UPDATE_BLOCKS;
-  double* part = (double*)scratch;
-  unsigned* ticket = (unsigned*)(part + (size_t)RMS_UPDATE_BLOCKS * 2 * dmv::OB);
-  HIPCHK(hipMemsetAsync(ticket, 0, sizeof(unsigned), st));
-  hipLaunchKernelGGL(dmv::k_vf_rms, dim3(blocks), dim3(256), 0, st, ob, (int)n, part, ticket, rms_sum, rms_sumsq, rms_count, rms_mean, rms_std);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-// ---- policy half of the TRPO update (csrc/pg_kernel.h) -------------------------------------------------------------------------
-static int pg_set_device(const void* p) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) == hipSuccess) { if (hipSetDevice(at.device) != hipSuccess) return DM_EHIP; }
-  else (void)hipGetLastError();
-  return DM_OK;
-}
-// one block per CU; `max_blocks` (0: all of them) leaves CUs to a kernel of another stream (the value fit beside the policy step)
-static int pg_blocks(int ntiles, int max_blocks) {
-  const int cap = (max_blocks > 0 && max_blocks < dmg::MAX_BLOCKS) ? max_blocks : dmg::MAX_BLOCKS;
-  return ntiles < cap ? ntiles : cap;
-}
-extern "C" int dm_pg_param_count(void) { return dmg::NP; }
-extern "C" size_t dm_pg_scratch_bytes(void) { return (size_t)dmg::MAX_BLOCKS * dmg::NPAD * sizeof(float) + (size_t)dmg::MAX_BLOCKS * 2 * sizeof(double) + 256; }
-extern "C" int dm_pg_losses(const float* ob, int32_t n, const float* ac, const float* atarg, float* old_mean, const float* old_logstd, int32_t write_old,
-                            const float* theta, const float* rms_mean, const float* rms_std, double entcoeff, int32_t with_grad,
-                            float* out_grad, double* out_losses, void* scratch, void* hip_stream, int32_t max_blocks) {
-  if (!ob || !ac || !atarg || !old_mean || !old_logstd || !theta || !rms_mean || !rms_std || !out_losses || !scratch || n < 1 || (with_grad && !out_grad) || max_blocks < 0)
-    return fail(DM_EINVAL, "dm_pg_losses: bad argument");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_pg_losses: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int ntiles = (n + dmg::SB - 1) / dmg::SB, nblk = pg_blocks(ntiles, max_blocks);
-  float* partial = (float*)scratch;
-  double* lpart = (double*)((char*)scratch + (((size_t)dmg::MAX_BLOCKS * dmg::NPAD * sizeof(float) + 255) / 256) * 256);
-  if (with_grad)
-    hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_GRAD>, dim3(nblk), dim3(256), 0, st, ob, 1, (int)n, ac, atarg, old_mean, old_logstd, (int)write_old, theta,
-                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
-  else
-    hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_LOSS>, dim3(nblk), dim3(256), 0, st, ob, 1, (int)n, ac, atarg, old_mean, old_logstd, (int)write_old, theta,
-                       (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
-  hipLaunchKernelGGL(dmg::k_pg_reduce, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, (const float*)partial, (const double*)lpart, nblk,
-                     with_grad ? (int)dmg::MODE_GRAD : (int)dmg::MODE_LOSS, (float)entcoeff, (const float*)nullptr, 1.0 / (double)n, out_grad, out_losses);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_pg_fvp(const float* ob, int32_t stride, int32_t n, const float* theta, const float* v, const float* rms_mean, const float* rms_std,
-                         float* out_fv, void* scratch, void* hip_stream, int32_t max_blocks) {
-  if (!ob || !theta || !v || !rms_mean || !rms_std || !out_fv || !scratch || n < 1 || stride < 1 || max_blocks < 0) return fail(DM_EINVAL, "dm_pg_fvp: bad argument");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_pg_fvp: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int ntiles = (n + dmg::SB - 1) / dmg::SB, nblk = pg_blocks(ntiles, max_blocks);
-  float* partial = (float*)scratch;
-  double* lpart = (double*)((char*)scratch + (((size_t)dmg::MAX_BLOCKS * dmg::NPAD * sizeof(float) + 255) / 256) * 256);
-  hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_FVP>, dim3(nblk), dim3(256), 0, st, ob, (int)stride, (int)n, (const float*)nullptr, (const float*)nullptr,
-                     (float*)nullptr, (const float*)nullptr, 0, theta, v, rms_mean, rms_std, 1.0f / (float)n, partial, lpart, dmg::BcArgs{});
-  hipLaunchKernelGGL(dmg::k_pg_reduce, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, (const float*)partial, (const double*)lpart, nblk, (int)dmg::MODE_FVP,
-                     0.0f, v, 1.0 / (double)n, out_fv, (double*)nullptr);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-// ---- the GAIL discriminator (csrc/disc_kernel.h) --------------------------------------------------------------------------------
-static bool have_device() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; } return n > 0; }
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static int disc_blocks(int n) { return (n + dmd::SB - 1) / dmd::SB; }
-extern "C" int dm_disc_param_count(void) { return dmd::NP; }
-extern "C" size_t dm_disc_scratch_bytes(int32_t n_g, int32_t n_e) {
-  if (n_g < 1 || n_e < 1) return 0;
-  return (size_t)(disc_blocks(n_g) + disc_blocks(n_e)) * dmd::NPAD * sizeof(float);
-}
-extern "C" int dm_disc_reward(const float* theta, const float* rms_mean, const float* rms_std, const double* ob, const double* ac, int32_t n, double* reward,
-                              void* hip_stream) {
-  if (!theta || !rms_mean || !rms_std || !ob || !ac || !reward || n < 1 || !aligned16(theta)) return fail(DM_EINVAL, "dm_disc_reward: bad argument");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_disc_reward: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_disc_reward: hipSetDevice failed");
-  hipLaunchKernelGGL(dmd::k_disc_reward, dim3(disc_blocks(n)), dim3(256), 0, (hipStream_t)hip_stream, ob, ac, (int)n, theta, rms_mean, rms_std, reward);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_disc_lossgrad(const float* theta, const float* rms_mean, const float* rms_std, const float* g_ob, const float* g_ac, int32_t n_g,
-                                const float* e_ob, const float* e_ac, int32_t n_e, double entcoeff, float* out_grad, double* out_losses, void* scratch,
-                                size_t scratch_bytes, void* hip_stream) {
-  if (!theta || !rms_mean || !rms_std || !g_ob || !g_ac || !e_ob || !e_ac || !out_grad || !out_losses || !scratch || n_g < 1 || n_e < 1 || !aligned16(theta) ||
-      !(entcoeff == entcoeff) || (int64_t)disc_blocks(n_g) + disc_blocks(n_e) > INT32_MAX / dmd::NPAD)
-    return fail(DM_EINVAL, "dm_disc_lossgrad: bad argument");
-  if (scratch_bytes < dm_disc_scratch_bytes(n_g, n_e)) return fail(DM_EINVAL, "dm_disc_lossgrad: scratch smaller than dm_disc_scratch_bytes(n_g, n_e)");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_disc_lossgrad: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_disc_lossgrad: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int nbg = disc_blocks(n_g), nblk = nbg + disc_blocks(n_e);
-  float* partial = (float*)scratch;
-  hipLaunchKernelGGL(dmd::k_disc_grad, dim3(nblk), dim3(256), 0, st, g_ob, g_ac, (int)n_g, e_ob, e_ac, (int)n_e, nbg, theta, rms_mean, rms_std,
-                     (float)entcoeff, partial);
-  hipLaunchKernelGGL(dmd::k_disc_reduce, dim3(dmd::RED_BLOCKS + 1), dim3(256), 0, st, (const float*)partial, nblk, nbg,
-                     (int)n_g, (int)n_e, (float)entcoeff, out_grad, out_losses);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-// ---- behaviour cloning of the policy on expert transitions (csrc/pg_kernel.h MODE_BC) -----------------------------------------------
-static int bc_blocks(int n) { return pg_blocks((n + dmg::SB - 1) / dmg::SB, 0); }
-static size_t bc_lpart_offset(int n) { return up256((size_t)bc_blocks(n) * dmg::NPAD * sizeof(float)); }
-extern "C" size_t dm_bc_scratch_bytes(int32_t bs) {
-  if (bs < 1) return 0;
-  return bc_lpart_offset(bs) + (size_t)bc_blocks(bs) * 2 * sizeof(double);
-}
-// k_pg<BC> over rows idx[0 .. n) (or 0 .. n) and the reduction: partial / lpart in scratch (dm_bc_scratch_bytes(n) bytes)
-static void bc_launch(const float* ob_all, const float* ac_all, const int32_t* idx, int n, const float* theta, const float* rms_mean, const float* rms_std,
-                      int stochastic, uint64_t seed, uint64_t counter, int grad, void* scratch, hipStream_t st) {
-  float* partial = (float*)scratch;
-  double* lpart = (double*)((char*)scratch + bc_lpart_offset(n));
-  const dmg::BcArgs bc{idx, (unsigned long long)seed, (unsigned long long)counter, stochastic ? 1 : 0, grad};
-  hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_BC>, dim3(bc_blocks(n)), dim3(256), 0, st, ob_all, 1, n, ac_all, (const float*)nullptr, (float*)nullptr,
-                     (const float*)nullptr, 1, theta, (const float*)nullptr, rms_mean, rms_std, (float)(1.0 / (28.0 * (double)n)), partial, lpart, bc);
-}
-extern "C" int dm_bc_lossgrad(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean,
-                              const float* rms_std, int32_t stochastic, uint64_t seed, uint64_t counter, float* out_grad, double* out_loss, void* scratch,
-                              size_t scratch_bytes, void* hip_stream) {
-  if (!ob_all || !ac_all || !theta || !rms_mean || !rms_std || !out_loss || !scratch || n < 1 || n > INT32_MAX / dmg::AC || !aligned16(theta))
-    return fail(DM_EINVAL, "dm_bc_lossgrad: bad argument");
-  if (scratch_bytes < dm_bc_scratch_bytes(n)) return fail(DM_EINVAL, "dm_bc_lossgrad: scratch smaller than dm_bc_scratch_bytes(n)");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_bc_lossgrad: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_bc_lossgrad: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  bc_launch(ob_all, ac_all, idx, (int)n, theta, rms_mean, rms_std, (int)stochastic, seed, counter, out_grad ? 1 : 0, scratch, st);
-  const float* partial = (const float*)scratch;
-  const double* lpart = (const double*)((const char*)scratch + bc_lpart_offset(n));
-  hipLaunchKernelGGL(dmg::k_pg_reduce, dim3(out_grad ? (dmg::NP + 255) / 256 : 1), dim3(256), 0, st, partial, lpart, bc_blocks(n), (int)dmg::MODE_BC, 0.0f,
-                     (const float*)nullptr, 1.0 / (28.0 * (double)n), out_grad, out_loss);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_bc_fit(const float* ob_all, const float* ac_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
-                         const float* step_scale_host, double beta1, double beta2, double eps, const float* rms_mean, const float* rms_std, int32_t stochastic,
-                         uint64_t seed, uint64_t counter0, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
-  if (!ob_all || !ac_all || !theta || !adam_m || !adam_v || !step_scale_host || !rms_mean || !rms_std || !out_loss || !scratch || iters < 1 || bs < 1 ||
-      bs > INT32_MAX / dmg::AC || !aligned16(theta) || !std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps))
-    return fail(DM_EINVAL, "dm_bc_fit: bad argument");
-  for (int i = 0; i < iters; i++) if (!std::isfinite(step_scale_host[i])) return fail(DM_EINVAL, "dm_bc_fit: non-finite step scale");
-  if (scratch_bytes < dm_bc_scratch_bytes(bs)) return fail(DM_EINVAL, "dm_bc_fit: scratch smaller than dm_bc_scratch_bytes(bs)");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_bc_fit: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_bc_fit: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const float* partial = (const float*)scratch;
-  const double* lpart = (const double*)((const char*)scratch + bc_lpart_offset(bs));
-  for (int i = 0; i < iters; i++) {
-    bc_launch(ob_all, ac_all, idx ? idx + (size_t)i * bs : nullptr, (int)bs, theta, rms_mean, rms_std, (int)stochastic, seed, counter0 + (uint64_t)i, 1, scratch, st);
-    hipLaunchKernelGGL(dmg::k_bc_adam, dim3((dmg::NP + 255) / 256), dim3(256), 0, st, partial, lpart, bc_blocks(bs), 1.0 / (28.0 * (double)bs), theta, adam_m,
-                       adam_v, step_scale_host[i], (float)beta1, (float)beta2, (float)eps, out_loss + i);
-  }
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-// ---- PPO's clipped-surrogate update of the policy and the value net (csrc/pg_kernel.h MODE_PPO, k_ppo_step; vf_kernel.h k_vf_grad_rows) -----
-// scratch: both halves' loss sums first (their offsets do not depend on n), then the gradient partials of a call with the gradient
-static int ppo_vf_blocks(int n, int grad) { const int t = (n + dmv::SB - 1) / dmv::SB; return grad ? t : (t < dmg::MAX_BLOCKS ? t : dmg::MAX_BLOCKS); }
-static_assert(dmg::NP % 4 == 0, "the value half of a PPO theta starts 16-byte aligned");
-struct PpoScratch { size_t pg_lp, vf_lp, pg_part, vf_part, total; };
-static PpoScratch ppo_scratch_layout(int n, int grad) {
-  PpoScratch L;
-  size_t o = 0;
-  L.pg_lp = o; o += up256((size_t)dmg::MAX_BLOCKS * dmg::PPO_LP * sizeof(double));
-  const int vb = ppo_vf_blocks(n, grad);
-  L.vf_lp = o; o += up256((size_t)(vb > dmg::MAX_BLOCKS ? vb : dmg::MAX_BLOCKS) * sizeof(double));
-  L.pg_part = o; if (grad) o += up256((size_t)pg_blocks((n + dmg::SB - 1) / dmg::SB, 0) * dmg::NPAD * sizeof(float));
-  L.vf_part = o; if (grad) o += up256((size_t)vb * dmv::NPAD * sizeof(float));
-  L.total = o;
-  return L;
-}
-extern "C" size_t dm_ppo_scratch_bytes(int32_t bs) {
-  if (bs < 1 || bs > INT32_MAX / dmg::AC) return 0;
-  return ppo_scratch_layout((int)bs, 1).total;
-}
-struct PpoRows { const float *ob, *ac, *atarg, *old_mean, *old_logstd, *ret; };
-// k_pg<PPO> and k_vf_grad_rows over rows idx[0 .. n) (or 0 .. n): partials and loss sums in scratch; -> the two grids
-static void ppo_grad_launch(const PpoRows& R, const int32_t* idx, int n, const float* theta, const float* rms_mean, const float* rms_std, float clip,
-                            int grad, const PpoScratch& L, void* scratch, hipStream_t st, int* pg_nblk, int* vf_nblk) {
-  char* base = (char*)scratch;
-  *pg_nblk = pg_blocks((n + dmg::SB - 1) / dmg::SB, 0);
-  *vf_nblk = ppo_vf_blocks(n, grad);
-  const dmg::BcArgs pa{idx, 0ull, 0ull, 0, grad, clip};
-  hipLaunchKernelGGL(dmg::k_pg<dmg::MODE_PPO>, dim3(*pg_nblk), dim3(256), 0, st, R.ob, 1, n, R.ac, R.atarg, (float*)R.old_mean, R.old_logstd, 0, theta,
-                     (const float*)nullptr, rms_mean, rms_std, 1.0f / (float)n, (float*)(base + L.pg_part), (double*)(base + L.pg_lp), pa);
-  if (grad)
-    hipLaunchKernelGGL(dmv::k_vf_grad_rows<true>, dim3(*vf_nblk), dim3(256), 0, st, R.ob, R.ret, idx, n, theta + dmg::NP, rms_mean, rms_std,
-                       (float*)(base + L.vf_part), (double*)(base + L.vf_lp));
-  else
-    hipLaunchKernelGGL(dmv::k_vf_grad_rows<false>, dim3(*vf_nblk), dim3(256), 0, st, R.ob, R.ret, idx, n, theta + dmg::NP, rms_mean, rms_std,
-                       (float*)nullptr, (double*)(base + L.vf_lp));
-}
-static bool ppo_rows_ok(const PpoRows& R) { return R.ob && R.ac && R.atarg && R.old_mean && R.old_logstd && R.ret; }
-extern "C" int dm_ppo_lossgrad(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
-                               const float* ret_all, const int32_t* idx, int32_t n, const float* theta, const float* rms_mean, const float* rms_std,
-                               double clip, double entcoeff, float* out_grad, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
-  const PpoRows R{ob_all, ac_all, atarg_all, old_mean_all, old_logstd, ret_all};
-  if (!ppo_rows_ok(R) || !theta || !rms_mean || !rms_std || !out_loss || !scratch || n < 1 || n > INT32_MAX / dmg::AC || !aligned16(theta) ||
-      !std::isfinite(clip) || clip < 0.0 || !std::isfinite(entcoeff))
-    return fail(DM_EINVAL, "dm_ppo_lossgrad: bad argument");
-  const int grad = out_grad ? 1 : 0;
-  const PpoScratch L = ppo_scratch_layout((int)n, grad);
-  if (scratch_bytes < L.total) return fail(DM_EINVAL, "dm_ppo_lossgrad: scratch smaller than dm_ppo_scratch_bytes(n)");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_ppo_lossgrad: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_ppo_lossgrad: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  int pg_nblk, vf_nblk;
-  ppo_grad_launch(R, idx, (int)n, theta, rms_mean, rms_std, (float)clip, grad, L, scratch, st, &pg_nblk, &vf_nblk);
-  const char* base = (const char*)scratch;
-  hipLaunchKernelGGL(dmg::k_ppo_step, dim3(grad ? dmg::PPO_STEP_BLOCKS : 1), dim3(256), 0, st, (const float*)(base + L.pg_part),
-                     (const double*)(base + L.pg_lp), pg_nblk, (const float*)(base + L.vf_part), (const double*)(base + L.vf_lp), vf_nblk,
-                     1.0 / (double)n, (float)entcoeff, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.0f, 0.0f, 0.0f, 0.0f, out_grad, out_loss);
-  HIPCHK(hipGetLastError());
-  return DM_OK;
-}
-extern "C" int dm_ppo_fit(const float* ob_all, const float* ac_all, const float* atarg_all, const float* old_mean_all, const float* old_logstd,
-                          const float* ret_all, const int32_t* idx, int32_t iters, int32_t bs, float* theta, float* adam_m, float* adam_v,
-                          const float* step_scale_host, const float* clip_host, double beta1, double beta2, double eps, double entcoeff,
-                          const float* rms_mean, const float* rms_std, double* out_loss, void* scratch, size_t scratch_bytes, void* hip_stream) {
-  const PpoRows R{ob_all, ac_all, atarg_all, old_mean_all, old_logstd, ret_all};
-  if (!ppo_rows_ok(R) || !theta || !adam_m || !adam_v || !step_scale_host || !clip_host || !rms_mean || !rms_std || !out_loss || !scratch || iters < 1 ||
-      bs < 1 || bs > INT32_MAX / dmg::AC || !aligned16(theta) || !std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps) ||
-      !std::isfinite(entcoeff))
-    return fail(DM_EINVAL, "dm_ppo_fit: bad argument");
-  for (int i = 0; i < iters; i++)
-    if (!std::isfinite(step_scale_host[i]) || !std::isfinite(clip_host[i]) || clip_host[i] < 0.0f) return fail(DM_EINVAL, "dm_ppo_fit: bad step scale or clip");
-  const PpoScratch L = ppo_scratch_layout((int)bs, 1);
-  if (scratch_bytes < L.total) return fail(DM_EINVAL, "dm_ppo_fit: scratch smaller than dm_ppo_scratch_bytes(bs)");
-  if (!have_device()) return fail(DM_ENODEVICE, "dm_ppo_fit: no HIP device visible (libdmenv has no CPU path)");
-  if (pg_set_device(theta)) return fail(DM_EHIP, "dm_ppo_fit: hipSetDevice failed");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const char* base = (const char*)scratch;
-  for (int i = 0; i < iters; i++) {
-    int pg_nblk, vf_nblk;
-    ppo_grad_launch(R, idx ? idx + (size_t)i * bs : nullptr, (int)bs, theta, rms_mean, rms_std, clip_host[i], 1, L, scratch, st, &pg_nblk, &vf_nblk);
-    hipLaunchKernelGGL(dmg::k_ppo_step, dim3(dmg::PPO_STEP_BLOCKS), dim3(256), 0, st, (const float*)(base + L.pg_part), (const double*)(base + L.pg_lp),
-                       pg_nblk, (const float*)(base + L.vf_part), (const double*)(base + L.vf_lp), vf_nblk, 1.0 / (double)bs, (float)entcoeff, theta,
-                       adam_m, adam_v, step_scale_host[i], (float)beta1, (float)beta2, (float)eps, (float*)nullptr, out_loss + (size_t)i * DM_PPO_NLOSS);
-  }
-  HIPCHK(hipGetLastError());
   return DM_OK;
 }
 extern "C" int dm_batch_redo_total(dm_batch* b, int64_t* out) {

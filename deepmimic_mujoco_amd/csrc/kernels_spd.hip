@@ -1,6 +1,8 @@
 // kernels_spd.hip — the one-environment-per-wavefront step kernels of action modes 3 and 4 (stable PD control per substep: env_step.h spd_control).
 // k_step_narrow, k_step_act, k_step, k_step_redo and k_step_prof of dmenv.hip with the controller compiled in (env_step_impl<.., SPD = true>), in a
 // translation unit of their own so that the kernels of modes 0..2 stay the code objects they were; default backend options, as dmenv.hip.
+// (the bodies stay written out in both units: through a shared template, as packed_body.h has for the packed kernels, every one of the ten kernels' code
+//  objects came out different — profiles/host_split.md)
 #define DM_NO_LAUNCH_KERNELS
 #include "kernels.h"
 

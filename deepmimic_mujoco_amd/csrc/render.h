@@ -37,6 +37,13 @@ struct Params {
   float ambient, headlight, diffuse;
 };
 
+// the camera of one call, as dm_render_desc gives it (float64 on the host side of every build; a kernel argument of the pose pass)
+struct Camera {
+  double pos[3];      // world position, or the offset from the centre of mass when track_com
+  double mat[9];      // row-major; columns = camera x (right), y (up), z (backward)
+  int track_com;
+};
+
 // one body geom as the ray caster sees it: centre relative to the camera, world axes (row-major: column k = local axis k)
 struct GeomRec {
   float c[3];

@@ -1,4 +1,4 @@
-// render_kernel.h — dm_batch_render's two launches.  Included by dmenv.hip after kernels.h.
+// render_kernel.h — dm_batch_render's two launches.  Included by dmenv.hip after kernels.h; launched from views.hip.
 //
 //   k_render_pose  one wave per view: the step kernels' kinematics (stage_kinematics) at the view's qpos, the 16 geom frames
 //                  formed as stage_rows forms them, the centre of mass, the resolved camera, and the view's ~1 KB record for
@@ -8,17 +8,6 @@
 #pragma once
 
 #include "render.h"
-
-namespace dmr {
-
-// the camera of one call, as dm_render_desc gives it (float64 on the host side of every build)
-struct Camera {
-  double pos[3];      // world position, or the offset from the centre of mass when track_com
-  double mat[9];      // row-major; columns = camera x (right), y (up), z (backward)
-  int track_com;
-};
-
-}  // namespace dmr
 
 // qpos of view v: an explicit pose (qpos_ext [n,35]) or the batch's state of env env_ids[v] (or v)
 __global__ __launch_bounds__(64) void k_render_pose(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos,

@@ -1,4 +1,4 @@
-// state_kernel.h — dm_batch_state_features' launch.  Included by dmenv.hip after kernels.h.
+// state_kernel.h — dm_batch_state_features' launch.  Included by dmenv.hip after kernels.h; launched from views.hip.
 //
 //   k_state_features  one wave per state: the step kernels' kinematics (stage_kinematics) at the state's qpos, then one lane per body forms
 //                     its 13 numbers (state_features.h: heading frame, quaternion product and sign rule, the velocity of its centre of mass

@@ -602,3 +602,32 @@ def test_self_ordering_launches_step_every_env_exactly_once_whatever_runs_in_bet
     for i in (1, 2, 3):
         assert np.array_equal(finals[0][i], finals[1][i])
     assert finals[0][3].max() > 8
+
+
+def test_last_error_is_per_thread_across_the_learner_and_batch_entry_points():
+    """dm_last_error is one thread-local text for the whole library, whichever translation unit's entry point failed: two threads that each
+    provoke a different DM_EINVAL — a learner entry point (dm_pg_fvp with n = 0) and a batch entry point (dm_batch_step with nsub = 0) — read
+    their own message after both have failed.  Both calls return from their argument checks: no kernel runs."""
+    import ctypes as C
+    import threading
+    L = A.load()
+    b = make_batch(4)
+    buf = (C.c_double * 8)()                                   # non-null stand-in for every array: the checks fail before anything is read
+    ptr = C.cast(buf, C.c_void_p)
+    both_failed = threading.Barrier(2)
+    seen = {}
+
+    def run(name, call):
+        rc = call()
+        both_failed.wait(timeout=30)
+        seen[name] = (rc, (L.dm_last_error() or b"").decode())
+
+    ths = [threading.Thread(target=run, args=("learner", lambda: L.dm_pg_fvp(ptr, 1, 0, ptr, ptr, ptr, ptr, ptr, ptr, None, 0))),
+           threading.Thread(target=run, args=("batch", lambda: L.dm_batch_step(b._h, ptr, ptr, ptr, ptr, 0, A.PTR_DEVICE)))]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    b.close()
+    assert seen["learner"] == (-1, "dm_pg_fvp: bad argument")
+    assert seen["batch"] == (-1, "dm_batch_step: bad argument")

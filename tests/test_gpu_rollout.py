@@ -483,6 +483,46 @@ def test_fused_policy_step_on_tiny_and_odd_batches(n, pipeline):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("n,depth", [(3, 4), (37, 2)])
+def test_pipelined_parts_of_a_small_packed_batch_equal_the_unpipelined_step(n, depth, fused):
+    """The launches of one part of a step call are written once for the pipelined parts and the whole batch: the shapes at which that can go
+    wrong.  3 envs at depth 4 leave part 0 empty (envs 0 * 3 / 4 .. 1 * 3 / 4), its launches and events are skipped; 37 envs at depth 2 are
+    parts of 18 and 19, each with a last packed wave of spare slots and its own pair of redo counters.  A packed batch whose environments
+    stand on the floor (constraint rows: the redo launch runs), 4 steps with and without the fused policy step: observations, rewards, done
+    flags, the policy's actions and values, and the final state are bit-identical to the same batch stepped unpipelined."""
+    steps = 4
+    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
+    pol.pack()                                                # the weight block step_act reads (act() would build it on first use)
+    g = torch.Generator(device=DEV); g.manual_seed(11)
+    ac_in = torch.randn((steps + 1, n, 28), generator=g, dtype=torch.float64, device=DEV) * 0.9
+    outs = []
+    for d in (1, depth):
+        env = DPVecEnv(n, motion="walk", device=0, reward="alive", autoreset="init", seed=3, packed=True)
+        b = env.batch
+        b.set_option(A.OPT_PIPELINE, d)
+        ob = torch.zeros((steps + 1, n, 56), dtype=torch.float64, device=DEV)
+        ac = ac_in.clone()                                    # (fused: rows 1 .. are overwritten by the policy)
+        vp = torch.zeros((steps + 1, n), dtype=torch.float32, device=DEV)
+        rew = torch.zeros((steps, n), dtype=torch.float64, device=DEV); dn = torch.zeros((steps, n), dtype=torch.uint8, device=DEV)
+        env.reset("init", out=ob[0])
+        for t in range(steps):                                # no join between calls: consecutive steps overlap
+            if fused:
+                b.step_act(ac[t], 1, (ob[t + 1], rew[t], dn[t]), pol._packed, ac[t + 1], vp[t + 1], True, pol._seed, 100 + t)
+            else:
+                b.step(ac[t], 1, (ob[t + 1], rew[t], dn[t]))
+        b.join(); b.sync()
+        torch.cuda.synchronize()
+        assert b.options[A.OPT_PACKED] == 1 and int(b.get(A.F_NEFC).max()) > 0, "the batch must run packed and hold constraint rows"
+        outs.append((ob.cpu().numpy(), rew.cpu().numpy(), dn.cpu().numpy(), ac.cpu().numpy(), vp.cpu().numpy(),
+                     b.get(A.F_QPOS), b.get(A.F_QVEL), b.get(A.F_QACC_WARMSTART)))
+        env.close()
+    for x, y in zip(*outs):
+        assert np.array_equal(x, y)
+    assert np.isfinite(outs[0][0]).all() and np.abs(outs[0][0][1:]).max() > 0
+
+
+@pytest.mark.gpu
 def test_auto_packed_follows_the_workload():
     """DPVecEnv(packed=None) at 8192 envs starts four-per-wave and re-decides from the batch's own row statistics: RSI + random actions
     (the benchmark regime: envs fall, few rows) stays on the lean packed kernel; a population standing on both feet (the init pose under zero

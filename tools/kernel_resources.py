@@ -15,7 +15,7 @@ READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
 
 def code_objects(lib):
-    """every gfx950 code object of the library: one clang offload bundle per translation unit (dmenv.hip, kernels_packed.hip)"""
+    """every gfx950 code object of the library: one clang offload bundle per translation unit (csrc/build.py UNITS: dmenv.hip, views.hip, learner.hip, kernels_packed.hip, kernels_rollout.hip, kernels_spd.hip, kernels_packed_spd.hip)"""
     blob = open(lib, "rb").read()
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
     out = []
