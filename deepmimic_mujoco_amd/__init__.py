@@ -9,7 +9,9 @@ Host side is pure Python over the C ABI of libdmenv.so (include/dmenv.h, HIP ker
     MlpPolicy  the learner's policy/value network, batched on the env's device (src/mlp_policy_trpo.py)
     traj_segment_generator / add_vtarg_and_adv   device-resident rollouts + GAE (src/trpo.py:27-94)
     load_checkpoint   reader for the reference's tf.train.Saver bundles
-    trpo.learn / TrpoLearner   the reference's TRPO learner on torch autograd + RCCL all-mean (src/trpo.py:97-319)
+    trpo.learn / TrpoLearner   the reference's TRPO learner (src/trpo.py:97-319): the policy step and the value fit as kernels (csrc/pg_kernel.h,
+                      csrc/vf_kernel.h) on a GPU, torch autograd elsewhere; RCCL all-mean across ranks
+    train_loop        the loop that trpo.learn, ppo.learn and gail.learn share
     logio             progress.csv / monitor.csv readers and writers
     gail              the reference's GAIL learner: TransitionClassifier (the discriminator on the device), ExpertDataset, learn (src/gail.py)
 """

@@ -197,6 +197,26 @@ def check(rc, L=None):
         raise DmenvError("libdmenv error %d: %s" % (rc, (L.dm_last_error() or b"").decode()))
 
 
+def ptr(t):
+    """A tensor's address as the kernels' `void *` argument; None stays None (a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(dev):
+    """torch's current stream on `dev` as the kernels' `hipStream_t` argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def scratch(old, nbytes, dev):
+    """A kernel's uint8 scratch tensor of at least `nbytes` on `dev`: `old` (the holder's current one, or None) when it fits, else a new one."""
+    import torch
+    dev = torch.device(dev)
+    if old is not None and old.numel() >= nbytes and old.device.type == dev.type and dev.index in (None, old.device.index):
+        return old
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+
 def parse_debug(buf):
     """Split the DM_DEBUG_DOUBLES dump of dm_batch_debug_forward into named arrays."""
     o = 0

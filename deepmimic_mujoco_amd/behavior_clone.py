@@ -17,12 +17,14 @@ Paths:  one process on a GPU: dm_bc_fit, `chunk` iterations per call (two launch
         CPU tensors or native=False: torch autograd + MpiAdam.
 The expert's shuffles (`expert.rng`) are restored after BC, so GAIL draws the same expert batches with and without pretraining.
 """
+import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from .trpo import POL_KEYS, MpiAdam, _world
+from . import _abi as A
+from .trpo import POL_KEYS, MpiAdam, _world, native_nets
 
 AC = 28
 _M64 = (1 << 64) - 1
@@ -50,9 +52,7 @@ def normal_from(seed, counter, idx):
 def _native_ok(pi, native):
     if native is False or pi.device.type != "cuda":
         return False
-    p = pi.params
-    ok = (getattr(pi, "native", False) and tuple(p["polfc1/w"].shape) == (56, 100) and tuple(p["polfc2/w"].shape) == (100, 100)
-          and tuple(p["polfinal/w"].shape) == (100, 28) and p["logstd"].numel() == 28 and all(p[k].dtype == torch.float32 for k in POL_KEYS))
+    ok = native_nets(pi, POL_KEYS)
     if not ok and native is True:
         raise ValueError("the BC kernels need the 56-100-100-28 float32 policy on a GPU")
     return ok
@@ -62,9 +62,7 @@ class _Kernels:
     """dm_bc_lossgrad / dm_bc_fit on the policy's device."""
 
     def __init__(self, pi, expert, bs, noise_seed):
-        import ctypes as C
-        from . import _abi as A
-        self.C, self.A, self.L = C, A, A.load()
+        self.L = A.load()
         self.pi, self.dev, self.seed = pi, pi.device, noise_seed
         assert self.L.dm_pg_param_count() == sum(pi.params[k].numel() for k in POL_KEYS)
         self.ob = expert.obs.to(self.dev, torch.float32).contiguous()
@@ -73,15 +71,7 @@ class _Kernels:
         self.reserve(bs)
 
     def reserve(self, n):
-        need = int(self.L.dm_bc_scratch_bytes(int(n)))
-        if self.scratch is None or self.scratch.numel() < need:
-            self.scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
-
-    def _p(self, t):
-        return self.C.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _stream(self):
-        return self.C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        self.scratch = A.scratch(self.scratch, self.L.dm_bc_scratch_bytes(int(n)), self.dev)
 
     def lossgrad(self, theta, idx_dev, counter, grad=True):
         """-> (loss [1] float64, flat gradient or None) on the device; idx_dev: int32 device rows."""
@@ -90,9 +80,9 @@ class _Kernels:
         rms = self.pi.ob_rms
         loss = torch.empty(1, dtype=torch.float64, device=self.dev)
         g = torch.empty(theta.numel(), dtype=torch.float32, device=self.dev) if grad else None
-        p = self._p
-        self.A.check(self.L.dm_bc_lossgrad(p(self.ob), p(self.ac), p(idx_dev), n, p(theta), p(rms.mean), p(rms.std), 1, self.seed & _M64, int(counter) & _M64,
-                                           p(g), p(loss), p(self.scratch), self.scratch.numel(), self._stream()), self.L)
+        p = A.ptr
+        A.check(self.L.dm_bc_lossgrad(p(self.ob), p(self.ac), p(idx_dev), n, p(theta), p(rms.mean), p(rms.std), 1, self.seed & _M64, int(counter) & _M64,
+                                      p(g), p(loss), p(self.scratch), self.scratch.numel(), A.stream(self.dev)), self.L)
         return loss, g
 
     def fit(self, theta, m, v, idx_dev, scales, beta1, beta2, eps, counter0):
@@ -101,11 +91,11 @@ class _Kernels:
         self.reserve(bs)
         rms = self.pi.ob_rms
         out = torch.empty(iters, dtype=torch.float64, device=self.dev)
-        sc = (self.C.c_float * iters)(*scales)
-        p = self._p
-        self.A.check(self.L.dm_bc_fit(p(self.ob), p(self.ac), p(idx_dev), iters, bs, p(theta), p(m), p(v), sc, float(beta1), float(beta2), float(eps),
-                                      p(rms.mean), p(rms.std), 1, self.seed & _M64, int(counter0) & _M64, p(out), p(self.scratch), self.scratch.numel(),
-                                      self._stream()), self.L)
+        sc = (C.c_float * iters)(*scales)
+        p = A.ptr
+        A.check(self.L.dm_bc_fit(p(self.ob), p(self.ac), p(idx_dev), iters, bs, p(theta), p(m), p(v), sc, float(beta1), float(beta2), float(eps),
+                                 p(rms.mean), p(rms.std), 1, self.seed & _M64, int(counter0) & _M64, p(out), p(self.scratch), self.scratch.numel(),
+                                 A.stream(self.dev)), self.L)
         return out
 
 
@@ -164,11 +154,7 @@ def learn(pi, expert, *, max_iters=10000, optim_batch_size=128, optim_stepsize=3
             if verbose:                                                 # a chunk ends with each iteration that reports the val loss
                 end = min(end, -(-it // val_per_iter) * val_per_iter + 1)
             idx = np.stack([np.asarray(expert.next_indices(bs, "train")) for _ in range(it, end)]).astype(np.int32)
-            scales = []
-            for k in range(end - it):
-                t = adam.t + 1 + k
-                scales.append(optim_stepsize * math.sqrt(1 - adam.beta2 ** t) / (1 - adam.beta1 ** t))
-            train.append(K.fit(theta, adam.m, adam.v, torch.from_numpy(idx).to(pi.device), scales, adam.beta1, adam.beta2, adam_epsilon, it))
+            train.append(K.fit(theta, adam.m, adam.v, torch.from_numpy(idx).to(pi.device), adam.stepsizes(optim_stepsize, end - it), adam.beta1, adam.beta2, adam_epsilon, it))
             adam.t += end - it
             it = end
             if verbose and (it - 1) % val_per_iter == 0 and vidx is not None:

@@ -9,14 +9,13 @@
 """
 import math
 import os
-import time
-from collections import deque
 
 import numpy as np
 import torch
 
+from . import _abi as A
 from .policy import RunningMeanStd
-from .trpo import MpiAdam, TrpoLearner, _world
+from .trpo import MpiAdam, TrpoLearner
 
 # adversary.py `get_trainable_variables()` order (tf.contrib.layers.fully_connected scopes)
 ADV_KEYS = ("fully_connected/weights", "fully_connected/biases", "fully_connected_1/weights", "fully_connected_1/biases",
@@ -111,10 +110,6 @@ class TransitionClassifier:
             return False
         return all(x.is_cuda and x.device == self.device for x in xs)
 
-    def _stream(self):
-        import ctypes as C
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- forward (torch) ------------------------------------------------------------------------------------------------------
     def logits(self, ob, ac, theta=None):
         """The network of adversary.py build_graph in float32 torch ops: [n] logits."""
@@ -136,11 +131,8 @@ class TransitionClassifier:
         n = out64.numel()
         if (self._native_ok(ob64, ac64, out64) and ob64.dtype == torch.float64 and ac64.dtype == torch.float64 and out64.dtype == torch.float64
                 and ob64.is_contiguous() and ac64.is_contiguous() and out64.is_contiguous() and ob64.numel() == 56 * n and ac64.numel() == 28 * n):
-            import ctypes as C
-            from . import _abi as A
-            L = A.load()
-            p = lambda x: C.c_void_p(x.data_ptr())
-            A.check(L.dm_disc_reward(p(self.theta), p(self.obs_rms.mean), p(self.obs_rms.std), p(ob64), p(ac64), int(n), p(out64), self._stream()), L)
+            L, p = A.load(), A.ptr
+            A.check(L.dm_disc_reward(p(self.theta), p(self.obs_rms.mean), p(self.obs_rms.std), p(ob64), p(ac64), int(n), p(out64), A.stream(self.device)), L)
             return out64
         with torch.no_grad():
             r = self.reward_of_logits(self.logits(ob64.reshape(-1, self.ob_dim), ac64.reshape(-1, self.ac_dim)))
@@ -164,19 +156,14 @@ class TransitionClassifier:
         if ng < 1 or ne < 1:
             raise ValueError("lossandgrad needs at least one generator and one expert row (%d, %d)" % (ng, ne))
         if self._native_ok(g_ob, g_ac, e_ob, e_ac):
-            import ctypes as C
-            from . import _abi as A
-            L = A.load()
+            L, p = A.load(), A.ptr
             f = lambda x, d: x.to(torch.float32).reshape(-1, d).contiguous()
             g_ob, g_ac, e_ob, e_ac = f(g_ob, 56), f(g_ac, 28), f(e_ob, 56), f(e_ac, 28)
-            need = int(L.dm_disc_scratch_bytes(ng, ne))
-            if self._scratch is None or self._scratch.numel() < need:
-                self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._scratch = A.scratch(self._scratch, L.dm_disc_scratch_bytes(ng, ne), self.device)
             grad = torch.empty(self.theta.numel(), dtype=torch.float32, device=self.device)
             losses = torch.empty(6, dtype=torch.float64, device=self.device)
-            p = lambda x: C.c_void_p(x.data_ptr())
             A.check(L.dm_disc_lossgrad(p(self.theta), p(self.obs_rms.mean), p(self.obs_rms.std), p(g_ob), p(g_ac), ng, p(e_ob), p(e_ac), ne,
-                                       self.entcoeff, p(grad), p(losses), p(self._scratch), self._scratch.numel(), self._stream()), L)
+                                       self.entcoeff, p(grad), p(losses), p(self._scratch), self._scratch.numel(), A.stream(self.device)), L)
             return losses, grad
         return self._lossandgrad_torch(g_ob, g_ac, e_ob, e_ac)
 
@@ -279,7 +266,7 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
     With `log_dir`, rank 0 writes progress.csv and monitor.csv (the env's returns of every finished episode) as trpo.learn does.
     algo="ppo" (the reference's --algo, src/gail.py:394): the G updates are ppo.PpoLearner's, with gamma, lam, entcoeff, seed and `ppo_kwargs`
     (its linear schedule over max_timesteps when that is the stopping rule, else a constant one); the TRPO arguments are then unused."""
-    import torch.distributed as dist
+    from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     from .rollout import can_fuse, traj_segment_generator
     if algo == "trpo":
@@ -298,33 +285,8 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
     seg_gen = traj_segment_generator(pi, env, timesteps_per_batch, stochastic=True, fused=use_fused, reward_giver=reward_giver)
     d_gen = torch.Generator(device=pi.device)
     d_gen.manual_seed(int(seed) + 1)
-    world = _world(group)
-    rank = dist.get_rank(group) if world > 1 else 0
-    episodes_so_far = timesteps_so_far = iters_so_far = 0
-    tstart = time.time()
-    lenbuffer, rewbuffer, true_rewbuffer = deque(maxlen=40), deque(maxlen=40), deque(maxlen=40)
-    history = []
-    progress = monitor = None
-    if log_dir and rank == 0:
-        from .logio import ProgressCsv, MonitorWriter
-        os.makedirs(log_dir, exist_ok=True)
-        progress = ProgressCsv(os.path.join(log_dir, "progress.csv"))
-        monitor = MonitorWriter(os.path.join(log_dir, "monitor.json"), t_start=tstart)
-    while True:
-        if callback:
-            callback(locals(), globals())
-        if max_timesteps and timesteps_so_far >= max_timesteps:
-            break
-        if max_iters and iters_so_far >= max_iters:
-            break
-        if max_seconds:
-            stop = time.time() - tstart >= max_seconds
-            if world > 1:
-                flag = torch.tensor([1.0 if stop else 0.0], dtype=torch.float32, device=pi.device)
-                dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
-                stop = bool(flag.item() > 0)
-            if stop:
-                break
+
+    def iterate(timesteps_so_far):
         # ---- update G (:259-326) ----
         segs = []
         for _ in range(g_step):
@@ -351,31 +313,17 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
         d_mean = torch.stack(d_losses).mean(0).tolist() if d_losses else [float("nan")] * 6
         for name, val in zip(reward_giver.loss_name, d_mean):
             stats[name] = val
-        # ---- episode statistics of the last segment (:345-364) ----
-        lens, rets, true_rets = list(seg["ep_lens"]), list(seg["ep_rets"]), list(seg["ep_true_rets"])
-        if world > 1:
-            sums = torch.tensor([len(lens), sum(lens), sum(rets), sum(true_rets)], dtype=torch.float64, device=pi.device)
-            dist.all_reduce(sums, group=group)
-            n_eps, n_steps = int(sums[0]), int(sums[1])
-        else:
-            n_eps, n_steps = len(lens), int(sum(lens))
-        lenbuffer.extend(lens[-40:]); rewbuffer.extend(rets[-40:]); true_rewbuffer.extend(true_rets[-40:])
-        episodes_so_far += n_eps
-        timesteps_so_far += n_steps
-        iters_so_far += 1
-        mean = lambda b: float(sum(b) / len(b)) if len(b) else float("nan")
-        stats.update(EpLenMean=mean(lenbuffer), EpRewMean=mean(rewbuffer), EpTrueRewMean=mean(true_rewbuffer), EpThisIter=n_eps,
-                     EpisodesSoFar=episodes_so_far, TimestepsSoFar=timesteps_so_far, TimeElapsed=time.time() - tstart, iteration=iters_so_far)
-        history.append(stats)
-        if progress is not None:
-            progress.writekvs({k: stats.get(k) for k in ("optimgain", "meankl", "entloss", "surrgain", "entropy", "ev_tdlam_before") + LOSS_NAMES
-                               + ("EpLenMean", "EpRewMean", "EpTrueRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed")})
-            for s in segs:
-                monitor.write_episodes(list(s["ep_true_rets"]), list(s["ep_lens"]))
-        if log and rank == 0:
-            log("iter %4d  eps %6d  EpLenMean %7.1f  EpRewMean %8.3f  EpTrueRewMean %8.3f  meankl %.4f  g_loss %.4f  e_loss %.4f  g_acc %.3f  e_acc %.3f  %.1fs"
-                % (iters_so_far, n_eps, stats["EpLenMean"], stats["EpRewMean"], stats["EpTrueRewMean"], stats.get("meankl", float("nan")),
+        # ---- episode statistics of the last segment (:345-364); the monitor file gets every segment's ----
+        episodes = {"EpLenMean": list(seg["ep_lens"]), "EpRewMean": list(seg["ep_rets"]), "EpTrueRewMean": list(seg["ep_true_rets"])}
+        return stats, episodes, [(list(s["ep_true_rets"]), list(s["ep_lens"])) for s in segs], None
+
+    def log_line(stats):
+        return ("iter %4d  eps %6d  EpLenMean %7.1f  EpRewMean %8.3f  EpTrueRewMean %8.3f  meankl %.4f  g_loss %.4f  e_loss %.4f  g_acc %.3f  e_acc %.3f  %.1fs"
+                % (stats["iteration"], stats["EpThisIter"], stats["EpLenMean"], stats["EpRewMean"], stats["EpTrueRewMean"], stats.get("meankl", float("nan")),
                    stats["generator_loss"], stats["expert_loss"], stats["generator_acc"], stats["expert_acc"], stats["TimeElapsed"]))
-    if progress is not None:
-        progress.close(); monitor.close()
-    return history
+
+    return train_loop.run(pi, iterate, window=40, log_line=log_line, names=locals(), max_iters=max_iters, max_timesteps=max_timesteps,
+                          max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir, empty_mean=float("nan"),
+                          len_mean_iter=False,
+                          columns=("optimgain", "meankl", "entloss", "surrgain", "entropy", "ev_tdlam_before") + LOSS_NAMES
+                          + ("EpLenMean", "EpRewMean", "EpTrueRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed"))

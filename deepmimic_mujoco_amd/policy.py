@@ -208,9 +208,8 @@ class MlpPolicy:
         return self._packed
 
     def _act_native(self, stochastic, ob, out, vpred_out):
-        import ctypes as C
         from . import _abi as A
-        L = A.load()
+        L, p = A.load(), A.ptr
         n = ob.shape[0]
         if self._dirty or self._packed is None:
             self.pack()
@@ -221,10 +220,8 @@ class MlpPolicy:
         if vpred_out is None:
             vpred_out = torch.empty(n, dtype=torch.float32, device=ob.device)
         self._counter += 1
-        stream = torch.cuda.current_stream(ob.device).cuda_stream
-        A.check(L.dm_policy_act(C.c_void_p(self._packed.data_ptr()), C.c_void_p(ob.data_ptr()), C.c_void_p(out.data_ptr()),
-                                C.c_void_p(vpred_out.data_ptr()), n, 1 if stochastic else 0, self._seed & (2 ** 64 - 1), self._counter,
-                                C.c_void_p(stream)), L)
+        A.check(L.dm_policy_act(p(self._packed), p(ob), p(out), p(vpred_out), n, 1 if stochastic else 0, self._seed & (2 ** 64 - 1), self._counter,
+                                A.stream(ob.device)), L)
         return out, vpred_out
 
     def act(self, stochastic, ob, out=None, vpred_out=None):

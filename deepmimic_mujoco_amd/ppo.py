@@ -20,26 +20,15 @@ Paths:  one process on a GPU: dm_ppo_fit, one call per epoch (three launches per
         several processes (or per_minibatch=True): dm_ppo_lossgrad + trpo.MpiAdam per minibatch (the gradient is all-mean'd across ranks);
         CPU tensors or native=False: torch autograd + MpiAdam, in the parameters' dtype.
 """
-import math
-import os
-import time
-from collections import deque
-
 import torch
 
-from .rollout import add_vtarg_and_adv, flatten_segment, pipelined_segment_generator, traj_segment_generator
-from .trpo import POL_KEYS, VF_KEYS, MpiAdam, TrpoLearner, _world, allmean, explained_variance, flat
+from . import _abi
+from .rollout import add_vtarg_and_adv, flatten_segment
+from .trpo import _HALF_LOG_2PI_E, POL_KEYS, VF_KEYS, MpiAdam, TrpoLearner, _neglogp, _world, allmean, explained_variance, flat, native_nets, rms_update
 
 LOSS_NAMES = ("pol_surr", "pol_entpen", "vf_loss", "kl", "ent")
 NLOSS = 6                                       # LOSS_NAMES + clipfrac (the fraction of rows with |ratio - 1| > clip)
 AC = 28
-_HALF_LOG_2PI_E = 0.5 * math.log(2.0 * math.pi * math.e)
-_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
-
-
-def _neglogp(x, mean, logstd):
-    """DiagGaussianPd.neglogp (src/distributions.py)"""
-    return 0.5 * (((x - mean) / torch.exp(logstd)) ** 2).sum(-1) + _HALF_LOG_2PI * x.shape[-1] + logstd.sum(-1)
 
 
 class PpoLearner:
@@ -71,6 +60,7 @@ class PpoLearner:
         self.perm_source = None              # tests: callable(n) -> index tensor replacing the shuffles of Dataset (one per epoch, then the loss pass)
         self._scratch = None
         self._pg_scratch = None
+        self._rms_scratch = None
         self.adam.sync()
 
     def lrmult(self):
@@ -82,31 +72,16 @@ class PpoLearner:
     def _native_ready(self, ob, ac):
         if self.native is False or ob.device.type != "cuda":
             return False
-        p = self.pi.params
         ok = (ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ac.dtype == torch.float32 and ac.dim() == 2 and ac.shape[1] == AC
-              and getattr(self.pi, "native", False) and tuple(p["polfc1/w"].shape) == (56, 100) and tuple(p["polfc2/w"].shape) == (100, 100)
-              and tuple(p["polfinal/w"].shape) == (100, AC) and p["logstd"].numel() == AC and tuple(p["vffc1/w"].shape) == (56, 100)
-              and tuple(p["vffc2/w"].shape) == (100, 100) and tuple(p["vffinal/w"].shape) == (100, 1)
-              and all(p[k].dtype == torch.float32 for k in POL_KEYS + VF_KEYS) and tuple(self.pi.ob_rms.shape) == (56,))
+              and native_nets(self.pi, POL_KEYS + VF_KEYS))
         if not ok and self.native is True:
             raise ValueError("the PPO kernels need float32 [n, 56] observations / [n, 28] actions and the 56-100-100-28 policy with the 56-100-100-1 "
                              "value net on a GPU")
         return ok
 
     # ---- the kernels (dm_ppo_*) ------------------------------------------------------------------------------------------------
-    def _lib(self):
-        from . import _abi as A
-        return A, A.load()
-
-    def _stream(self, dev):
-        import ctypes as C
-        return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
     def _reserve(self, bs, dev):
-        A, L = self._lib()
-        need = int(L.dm_ppo_scratch_bytes(int(max(1, bs))))
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._scratch = _abi.scratch(self._scratch, _abi.load().dm_ppo_scratch_bytes(int(max(1, bs))), dev)
         return self._scratch
 
     def _rows(self, D):
@@ -114,45 +89,39 @@ class PpoLearner:
 
     def kernel_lossgrad(self, D, idx, theta, clip, grad=True):
         """dm_ppo_lossgrad on rows idx (int32 device tensor, or None: all rows) -> (losses [NLOSS] float64, flat gradient [pol + vf] or None)."""
-        import ctypes as C
-        A, L = self._lib()
+        L, p = _abi.load(), _abi.ptr
         dev = D["ob"].device
         n = int(idx.numel()) if idx is not None else int(D["ob"].shape[0])
         sc = self._reserve(n if grad else 1, dev)
         out = torch.empty(NLOSS, dtype=torch.float64, device=dev)
         g = torch.empty(theta.numel(), dtype=torch.float32, device=dev) if grad else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        A.check(L.dm_ppo_lossgrad(*[p(t) for t in self._rows(D)], p(idx), n, p(theta), p(self.pi.ob_rms.mean), p(self.pi.ob_rms.std), float(clip),
-                                  float(self.entcoeff), p(g), p(out), p(sc), sc.numel(), self._stream(dev)), L)
+        _abi.check(L.dm_ppo_lossgrad(*[p(t) for t in self._rows(D)], p(idx), n, p(theta), p(self.pi.ob_rms.mean), p(self.pi.ob_rms.std), float(clip),
+                                     float(self.entcoeff), p(g), p(out), p(sc), sc.numel(), _abi.stream(dev)), L)
         return out, g
 
     def kernel_fit(self, D, idx, bs, theta, m, v, scales, clips):
         """dm_ppo_fit: len(scales) minibatches of bs rows idx [iters * bs] (int32 device) -> losses [iters, NLOSS] float64 on the device."""
         import ctypes as C
-        A, L = self._lib()
+        L, p = _abi.load(), _abi.ptr
         dev = D["ob"].device
         iters = len(scales)
         sc = self._reserve(bs, dev)
         out = torch.empty((iters, NLOSS), dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        A.check(L.dm_ppo_fit(*[p(t) for t in self._rows(D)], p(idx), iters, int(bs), p(theta), p(m), p(v), (C.c_float * iters)(*scales),
-                             (C.c_float * iters)(*clips), float(self.adam.beta1), float(self.adam.beta2), float(self.adam.epsilon), float(self.entcoeff),
-                             p(self.pi.ob_rms.mean), p(self.pi.ob_rms.std), p(out), p(sc), sc.numel(), self._stream(dev)), L)
+        _abi.check(L.dm_ppo_fit(*[p(t) for t in self._rows(D)], p(idx), iters, int(bs), p(theta), p(m), p(v), (C.c_float * iters)(*scales),
+                                (C.c_float * iters)(*clips), float(self.adam.beta1), float(self.adam.beta2), float(self.adam.epsilon), float(self.entcoeff),
+                                p(self.pi.ob_rms.mean), p(self.pi.ob_rms.std), p(out), p(sc), sc.numel(), _abi.stream(dev)), L)
         return out
 
     def _kernel_old_mean(self, ob, ac, atarg, old_logstd):
         """assign_old_eq_new as one dm_pg_losses launch with write_old = 1 (the kernel writes the policy's mean of every row)."""
-        import ctypes as C
-        A, L = self._lib()
+        L, p = _abi.load(), _abi.ptr
         dev = ob.device
-        if self._pg_scratch is None or self._pg_scratch.device != dev:
-            self._pg_scratch = torch.empty(int(L.dm_pg_scratch_bytes()), dtype=torch.uint8, device=dev)
+        self._pg_scratch = _abi.scratch(self._pg_scratch, L.dm_pg_scratch_bytes(), dev)
         old_mean = torch.empty((ob.shape[0], AC), dtype=torch.float32, device=dev)
         out = torch.empty(2, dtype=torch.float64, device=dev)
         theta = flat([t.detach() for t in self.pol]).contiguous()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        A.check(L.dm_pg_losses(p(ob), int(ob.shape[0]), p(ac), p(atarg), p(old_mean), p(old_logstd), 1, p(theta), p(self.pi.ob_rms.mean),
-                               p(self.pi.ob_rms.std), 0.0, 0, None, p(out), p(self._pg_scratch), self._stream(dev), 0), L)
+        _abi.check(L.dm_pg_losses(p(ob), int(ob.shape[0]), p(ac), p(atarg), p(old_mean), p(old_logstd), 1, p(theta), p(self.pi.ob_rms.mean),
+                                  p(self.pi.ob_rms.std), 0.0, 0, None, p(out), p(self._pg_scratch), _abi.stream(dev), 0), L)
         return old_mean
 
     # ---- torch autograd ----------------------------------------------------------------------------------------------------------
@@ -213,7 +182,7 @@ class PpoLearner:
         if native:
             ob = ob.contiguous(); ac = ac.contiguous()
             atarg = atarg.to(torch.float32).contiguous(); tdlamret = tdlamret.to(torch.float32).contiguous()
-        TrpoLearner._rms_update(self, ob)                                   # pi.ob_rms.update(ob): once, before any step
+        rms_update(pi, ob, self.group, self)                                # pi.ob_rms.update(ob): once, before any step
         old_logstd = pi.params["logstd"].detach().reshape(-1).clone()
         if native:
             old_mean = self._kernel_old_mean(ob, ac, atarg, old_logstd)
@@ -229,8 +198,7 @@ class PpoLearner:
                 continue
             if fused:
                 idx = perm[:nb * bs].to(torch.int32).contiguous()
-                scales = [stepsize * math.sqrt(1 - ad.beta2 ** (ad.t + 1 + k)) / (1 - ad.beta1 ** (ad.t + 1 + k)) for k in range(nb)]
-                self.kernel_fit(D, idx, bs, theta, ad.m, ad.v, scales, [clip] * nb)
+                self.kernel_fit(D, idx, bs, theta, ad.m, ad.v, ad.stepsizes(stepsize, nb), [clip] * nb)
                 ad.t += nb
                 continue
             for k in range(nb):
@@ -260,75 +228,33 @@ class PpoLearner:
 
 def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print, group=None, log_dir=None,
           fused=None, schedule="linear", **learner_kwargs):
-    """ppo1's `learn()` over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy, with trpo.learn's loop,
+    """ppo1's `learn()` over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy, with trpo.learn's loop (train_loop.run),
     stopping rules (`max_iters`, `max_timesteps` env steps (global), `max_seconds`), multi-rank handling and output files (`log_dir`: rank 0
     writes progress.csv and monitor.csv).  Episode statistics over ppo1's window of the last 100 episodes.  schedule="linear" needs
     max_timesteps.  fused: the rollout's policy step inside the env step kernel (None: when possible).  Returns the per-iteration stats:
     loss_pol_surr, loss_pol_entpen, loss_vf_loss, loss_kl, loss_ent, clipfrac, ev_tdlam_before, EpLenMean, EpRewMean, EpThisIter, ..."""
-    import torch.distributed as dist
+    from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = PpoLearner(pi, group=group, schedule=schedule, max_timesteps=max_timesteps, **learner_kwargs)
-    if isinstance(env, (list, tuple)):
-        seg_gen = pipelined_segment_generator(pi, list(env), timesteps_per_batch, stochastic=True)
-        n_envs_local = sum(e.num_envs for e in env)
-    else:
-        from .rollout import can_fuse
-        use_fused = can_fuse(pi, env) if fused is None else bool(fused)
-        seg_gen = traj_segment_generator(pi, env, timesteps_per_batch, stochastic=True, fused=use_fused)
-        n_envs_local = env.num_envs
-    world = _world(group)
-    rank = dist.get_rank(group) if world > 1 else 0
-    episodes_so_far = timesteps_so_far = iters_so_far = 0
-    tstart = time.time()
-    lenbuffer, rewbuffer = deque(maxlen=100), deque(maxlen=100)
-    history = []
-    progress = monitor = None
-    if log_dir and rank == 0:
-        from .logio import ProgressCsv, MonitorWriter
-        os.makedirs(log_dir, exist_ok=True)
-        progress = ProgressCsv(os.path.join(log_dir, "progress.csv"))
-        monitor = MonitorWriter(os.path.join(log_dir, "monitor.json"), t_start=tstart)
-    while True:
-        if callback:
-            callback(locals(), globals())
-        if max_timesteps and timesteps_so_far >= max_timesteps:
-            break
-        if max_iters and iters_so_far >= max_iters:
-            break
-        if max_seconds:
-            stop = time.time() - tstart >= max_seconds                  # decided collectively, as trpo.learn does
-            if world > 1:
-                flag = torch.tensor([1.0 if stop else 0.0], dtype=torch.float32, device=pi.device)
-                dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
-                stop = bool(flag.item() > 0)
-            if stop:
-                break
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused)
+    steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
+
+    def iterate(timesteps_so_far):
         seg = next(seg_gen)
         learner.timesteps_so_far = timesteps_so_far
         stats = learner.update(seg)
         if getattr(seg, "info", None):
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
-        n_eps = torch.tensor([len(lens), sum(lens), sum(rets)], dtype=torch.float64, device=pi.device)
-        if world > 1:
-            dist.all_reduce(n_eps, group=group)
-        lenbuffer.extend(lens[-100:]); rewbuffer.extend(rets[-100:])
-        episodes_so_far += int(n_eps[0]); timesteps_so_far += timesteps_per_batch * n_envs_local * world
-        iters_so_far += 1
-        stats.update(EpLenMean=float(sum(lenbuffer) / max(1, len(lenbuffer))), EpRewMean=float(sum(rewbuffer) / max(1, len(rewbuffer))),
-                     EpLenMeanIter=float(n_eps[1] / max(1.0, float(n_eps[0]))), EpThisIter=int(n_eps[0]), EpisodesSoFar=episodes_so_far,
-                     TimestepsSoFar=timesteps_so_far, TimeElapsed=time.time() - tstart, iteration=iters_so_far)
-        history.append(stats)
-        if progress is not None:
-            progress.writekvs({k: stats.get(k) for k in ("loss_pol_surr", "loss_pol_entpen", "loss_vf_loss", "loss_kl", "loss_ent", "clipfrac",
-                                                        "ev_tdlam_before", "EpLenMean", "EpRewMean", "EpThisIter", "EpisodesSoFar",
-                                                        "TimestepsSoFar", "TimeElapsed")})
-            monitor.write_episodes(rets, lens)
-        if log and rank == 0:
-            log("iter %4d  steps %10d  eps %7d  EpLenMean %7.1f  (this iter %7.1f)  pol_surr %+.4f  vf_loss %.4f  kl %.5f  clipfrac %.3f  ent %6.2f  "
-                "ev %.3f  %.1fs" % (iters_so_far, timesteps_so_far, stats["EpThisIter"], stats["EpLenMean"], stats["EpLenMeanIter"],
+        return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
+
+    def log_line(stats):
+        return ("iter %4d  steps %10d  eps %7d  EpLenMean %7.1f  (this iter %7.1f)  pol_surr %+.4f  vf_loss %.4f  kl %.5f  clipfrac %.3f  ent %6.2f  "
+                "ev %.3f  %.1fs" % (stats["iteration"], stats["TimestepsSoFar"], stats["EpThisIter"], stats["EpLenMean"], stats["EpLenMeanIter"],
                                     stats["loss_pol_surr"], stats["loss_vf_loss"], stats["loss_kl"], stats["clipfrac"], stats["loss_ent"],
                                     stats["ev_tdlam_before"], stats["TimeElapsed"]))
-    if progress is not None:
-        progress.close(); monitor.close()
-    return history
+
+    return train_loop.run(pi, iterate, window=100, log_line=log_line, names=locals(), max_iters=max_iters, max_timesteps=max_timesteps,
+                          max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir,
+                          columns=("loss_pol_surr", "loss_pol_entpen", "loss_vf_loss", "loss_kl", "loss_ent", "clipfrac", "ev_tdlam_before",
+                                   "EpLenMean", "EpRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed"))

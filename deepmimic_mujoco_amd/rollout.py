@@ -66,14 +66,12 @@ def add_vtarg_and_adv(seg, gamma, lam):
     if (rew.is_cuda and rew.dim() == 2 and rew.dtype == torch.float32 and vpred.dtype == torch.float32 and new.dtype == torch.int32
             and rew.is_contiguous() and vpred.is_contiguous() and new.is_contiguous()):
         # one launch of the k_gae kernel (csrc/policy_kernel.h) instead of T small ones
-        import ctypes as C
         from . import _abi as A
-        L = A.load()
+        L, p = A.load(), A.ptr
         nxt = seg["nextvpred"].to(torch.float32).contiguous()
         adv = torch.empty_like(rew); ret = torch.empty_like(rew)
-        p = lambda x: C.c_void_p(x.data_ptr())
         A.check(L.dm_gae(p(rew), p(vpred), p(new), p(nxt), p(adv), p(ret), T, rew.shape[1], float(gamma), float(lam),
-                         C.c_void_p(torch.cuda.current_stream(rew.device).cuda_stream)), L)
+                         A.stream(rew.device)), L)
         seg["adv"], seg["tdlamret"] = adv, ret
         return seg
     new1 = torch.cat([new.to(torch.float32), torch.zeros_like(new[:1], dtype=torch.float32)], 0)     # np.append(new, 0)
@@ -381,7 +379,6 @@ class SegmentCollector(object):
         of ~100 launch-bound tensor ops.  Returns are float64 sums in step order, like the reference's `cur_ep_ret += rew`.  Nothing waits
         here: the records travel to pinned memory behind the kernel, and `_PendingEpisodes.result()` sorts them when somebody asks — the
         learner does while the device is busy with the update's first kernels."""
-        import ctypes as C
         import torch
         from . import _abi as A
         T, n, dev = self.T, self.n, self.device
@@ -396,10 +393,9 @@ class SegmentCollector(object):
         if getattr(self, slot + "_pending") is not None:
             getattr(self, slot + "_pending").result()                     # (its pinned buffers are about to be overwritten)
         cnt, rec, h_cnt, h_rec = getattr(self, slot + "_buf")
-        p = lambda x: C.c_void_p(x.data_ptr())
-        L = A.load()
+        L, p = A.load(), A.ptr
         A.check(L.dm_episode_scan(p(rew64), p(done8), T, n, p(cur_ret), p(cur_len), p(cnt), rec.shape[0], p(rec),
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), L)
+                                  A.stream(dev)), L)
         h_cnt.copy_(cnt, non_blocking=True)
         h_rec.copy_(rec[:h_rec.shape[0]], non_blocking=True)
         ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(dev))

@@ -24,15 +24,47 @@ use a few thousand (a 1M-sample segment at 128 would be 8 000 sequential Adam st
 import math
 import os
 import time
-from collections import deque
 
 import numpy as np
 import torch
 
-from .rollout import add_vtarg_and_adv, flatten_segment, traj_segment_generator, pipelined_segment_generator
+from .rollout import add_vtarg_and_adv, flatten_segment
 
 POL_KEYS = ("polfc1/w", "polfc1/b", "polfc2/w", "polfc2/b", "polfinal/w", "polfinal/b", "logstd")   # var_list   (:139)
 VF_KEYS = ("vffc1/w", "vffc1/b", "vffc2/w", "vffc2/b", "vffinal/w", "vffinal/b")                     # vf_var_list (:140)
+_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+_HALF_LOG_2PI_E = 0.5 * math.log(2.0 * math.pi * math.e)
+_NATIVE_SHAPES = {"polfc1/w": (56, 100), "polfc2/w": (100, 100), "polfinal/w": (100, 28), "vffc1/w": (56, 100), "vffc2/w": (100, 100), "vffinal/w": (100, 1)}
+
+
+def _neglogp(x, mean, logstd):
+    """DiagGaussianPd.neglogp, src/distributions.py:231-234."""
+    return 0.5 * (((x - mean) / torch.exp(logstd)) ** 2).sum(-1) + _HALF_LOG_2PI * x.shape[-1] + logstd.sum(-1)
+
+
+def native_nets(pi, keys):
+    """True when the nets `keys` of `pi` (POL_KEYS, VF_KEYS or both) are what the learner kernels are written for: float32, 56-100-100-28 /
+    56-100-100-1, behind a 56-wide obs filter, in a policy that runs its own forward pass on kernels."""
+    p = pi.params
+    return bool(getattr(pi, "native", False) and tuple(pi.ob_rms.shape) == (56,) and all(p[k].dtype == torch.float32 for k in keys)
+                and all(tuple(p[k].shape) == shape for k, shape in _NATIVE_SHAPES.items() if k in keys)
+                and ("logstd" not in keys or p["logstd"].numel() == 28))
+
+
+def rms_update(pi, ob, group, holder):
+    """`pi.ob_rms.update(ob)` (:242): one launch (dm_rms_update) for a float32 batch on the GPU of a single-process run, else the tensor ops.
+    holder: the learner, whose `_rms_scratch` keeps the kernel's scratch buffer."""
+    rms = pi.ob_rms
+    if (ob.device.type == "cuda" and ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ob.is_contiguous() and _world(group) == 1
+            and tuple(rms.shape) == (56,) and torch.is_tensor(rms.count) and rms.sum.is_cuda and getattr(pi, "native", False)):
+        from . import _abi as A
+        L = A.load()
+        p = A.ptr
+        holder._rms_scratch = A.scratch(holder._rms_scratch, L.dm_rms_scratch_bytes(), ob.device)
+        A.check(L.dm_rms_update(p(ob), int(ob.shape[0]), p(rms.sum), p(rms.sumsq), p(rms.count), p(rms.mean), p(rms.std), p(holder._rms_scratch),
+                                A.stream(ob.device)), L)
+        return
+    rms.update(ob, group=group)
 
 
 def _world(group=None):
@@ -115,12 +147,16 @@ class MpiAdam:
                 p.copy_(theta[o:o + n].reshape(p.shape))
                 o += n
 
+    def stepsizes(self, stepsize, k):
+        """The bias-corrected step sizes of the next k updates (steps t + 1 .. t + k), src/mpi_adam.py:30."""
+        return [stepsize * math.sqrt(1 - self.beta2 ** t) / (1 - self.beta1 ** t) for t in range(self.t + 1, self.t + 1 + k)]
+
     def update(self, localg, stepsize):
         if self.t % 100 == 0:
             self.check_synced()
         g = allmean(localg.to(torch.float32).clone(), self.group)
+        a, = self.stepsizes(stepsize, 1)
         self.t += 1
-        a = stepsize * math.sqrt(1 - self.beta2 ** self.t) / (1 - self.beta1 ** self.t)
         self.m.mul_(self.beta1).add_(g, alpha=1 - self.beta1)
         self.v.mul_(self.beta2).addcmul_(g, g, value=1 - self.beta2)
         step = (-a) * self.m / (torch.sqrt(self.v) + self.epsilon)
@@ -218,11 +254,7 @@ class _VfGraph:
         used = inds[:self.nb * self.bs]
         self.ob_s.view(self.nb * self.bs, *ob.shape[1:]).copy_(ob[used])
         self.ret_s.view(-1).copy_(ret[used])
-        a = []
-        for k in range(self.nb):
-            t = ad.t + 1 + k
-            a.append(L.vf_stepsize * math.sqrt(1 - ad.beta2 ** t) / (1 - ad.beta1 ** t))
-        self.a_s.copy_(torch.tensor(a, dtype=torch.float32), non_blocking=False)
+        self.a_s.copy_(torch.tensor(ad.stepsizes(L.vf_stepsize, self.nb), dtype=torch.float32), non_blocking=False)
         self.ctr.zero_()
         for _ in range(self.nb):
             self.graph.replay()
@@ -241,7 +273,6 @@ class TrpoLearner:
         self.fvp_subsample = fvp_subsample
         # value-fit minibatch steps as one captured hipGraph each (single-process GPU runs; None = when possible)
         self.vf_graph = vf_graph
-        import os
         self.vf_overlap = os.environ.get("DM_VF_OVERLAP", "1") != "0"     # value fit on a second stream beside the policy step (both on kernels)
         self.vf_share = os.environ.get("DM_VF_SHARE", "1") != "0"         # ... and the policy launches leave it its CUs while it runs (_pg_share_begin)
         self._share = None
@@ -256,6 +287,7 @@ class TrpoLearner:
         # (None = when possible: CUDA tensors, the reference's 56-100-100-28 policy; multi-rank runs all-mean the kernels' results)
         self.pg_native = pg_native
         self._pg_scratch = None
+        self._rms_scratch = None
         self.group = group
         for k in POL_KEYS + VF_KEYS:
             pi.params[k].requires_grad_(True)
@@ -299,14 +331,12 @@ class TrpoLearner:
         """DiagGaussianPd.kl(self = 0, other = 1), src/distributions.py:235-237."""
         return (logstd1 - logstd0 + (torch.exp(2 * logstd0) + (mean0 - mean1) ** 2) / (2.0 * torch.exp(2 * logstd1)) - 0.5).sum(-1)
 
-    @staticmethod
-    def _neglogp(x, mean, logstd):
-        return 0.5 * (((x - mean) / torch.exp(logstd)) ** 2).sum(-1) + 0.5 * math.log(2.0 * math.pi) * x.shape[-1] + logstd.sum(-1)
+    _neglogp = staticmethod(_neglogp)
 
     def _losses(self, ob, ac, atarg, old_mean, old_logstd):
         mean, logstd = self._pd(ob)
         meankl = self._kl(old_mean, old_logstd, mean, logstd).mean()
-        meanent = (logstd + 0.5 * math.log(2.0 * math.pi * math.e)).sum(-1).mean()
+        meanent = (logstd + _HALF_LOG_2PI_E).sum(-1).mean()
         entbonus = self.entcoeff * meanent
         ratio = torch.exp(self._neglogp(ac, old_mean, old_logstd) - self._neglogp(ac, mean, logstd))     # pnew / pold
         surrgain = (ratio * atarg).mean()
@@ -332,10 +362,7 @@ class TrpoLearner:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             return False
-        p = self.pi.params
-        ok = (ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ret.dtype == torch.float32 and getattr(self.pi, "native", False)
-              and tuple(p["vffc1/w"].shape) == (56, 100) and tuple(p["vffc2/w"].shape) == (100, 100) and tuple(p["vffinal/w"].shape) == (100, 1)
-              and all(p[k].dtype == torch.float32 for k in VF_KEYS) and tuple(self.pi.ob_rms.shape) == (56,))
+        ok = ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ret.dtype == torch.float32 and native_nets(self.pi, VF_KEYS)
         if not ok and self.vf_native is True:
             raise ValueError("the native value fit needs float32 [n, 56] observations and the 56-100-100-1 value net on a GPU")
         return ok
@@ -351,14 +378,12 @@ class TrpoLearner:
         ob_s = ob[used].contiguous(); ret_s = ret[used].contiguous()
         theta = ad.getflat().to(torch.float32).contiguous()
         assert theta.numel() == L.dm_vf_param_count()
-        need = int(L.dm_vf_scratch_bytes(int(nb), int(bs)))
-        if self._vf_scratch is None or self._vf_scratch.numel() < need or self._vf_scratch.device != ob.device:
-            self._vf_scratch = torch.empty(need, dtype=torch.uint8, device=ob.device)
-        scale = (C.c_float * nb)(*[self.vf_stepsize * math.sqrt(1 - ad.beta2 ** (ad.t + 1 + k)) / (1 - ad.beta1 ** (ad.t + 1 + k)) for k in range(nb)])
-        pp = lambda t: C.c_void_p(t.data_ptr())
+        self._vf_scratch = A.scratch(self._vf_scratch, L.dm_vf_scratch_bytes(int(nb), int(bs)), ob.device)
+        scale = (C.c_float * nb)(*ad.stepsizes(self.vf_stepsize, nb))
+        pp = A.ptr
         A.check(L.dm_vf_fit_epoch(pp(ob_s), pp(ret_s), nb, int(bs), pp(theta), pp(ad.m), pp(ad.v), scale, float(ad.beta1), float(ad.beta2), float(ad.epsilon),
                                   pp(rms.sum), pp(rms.sumsq), pp(rms.count), pp(rms.mean), pp(rms.std), pp(self._vf_scratch),
-                                  C.c_void_p(torch.cuda.current_stream(ob.device).cuda_stream), 1 if self.vf_epoch_filter else 0), L)
+                                  A.stream(ob.device), 1 if self.vf_epoch_filter else 0), L)
         ad.setfromflat(theta)
         ad.t += nb
 
@@ -391,27 +416,23 @@ class TrpoLearner:
     def _pg_native_ready(self, ob, ac):
         if self.pg_native is False or ob.device.type != "cuda":
             return False
-        p = self.pi.params
         ok = (ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ac.dtype == torch.float32 and ac.dim() == 2 and ac.shape[1] == 28
-              and getattr(self.pi, "native", False) and tuple(p["polfc1/w"].shape) == (56, 100) and tuple(p["polfc2/w"].shape) == (100, 100)
-              and tuple(p["polfinal/w"].shape) == (100, 28) and p["logstd"].numel() == 28 and all(p[k].dtype == torch.float32 for k in POL_KEYS)
-              and tuple(self.pi.ob_rms.shape) == (56,))
+              and native_nets(self.pi, POL_KEYS))
         if not ok and self.pg_native is True:
             raise ValueError("the native policy update needs float32 [n, 56] observations / [n, 28] actions and the 56-100-100-28 policy on a GPU")
         return ok
 
     def _pg_call(self, name, *args):
-        import ctypes as C
         from . import _abi as A
         L = A.load()
-        A.check(getattr(L, name)(*[C.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args]), L)
+        A.check(getattr(L, name)(*[A.ptr(a) if torch.is_tensor(a) else a for a in args]), L)
 
     def _pg_buffers(self, dev):
         from . import _abi as A
         L = A.load()
-        if self._pg_scratch is None or self._pg_scratch.device != dev:
+        if self._pg_scratch is None:
             assert L.dm_pg_param_count() == sum(p.numel() for p in self.pol)
-            self._pg_scratch = torch.empty(int(L.dm_pg_scratch_bytes()), dtype=torch.uint8, device=dev)
+        self._pg_scratch = A.scratch(self._pg_scratch, L.dm_pg_scratch_bytes(), dev)
         return self._pg_scratch
 
     # ---- CU sharing between the policy step and the value fit running beside it ----
@@ -463,48 +484,36 @@ class TrpoLearner:
     def _pg_losses(self, ob, ac, atarg, old_mean, old_logstd, theta, write_old, with_grad):
         """-> (losses [5] float32 like `_losses`: optimgain, meankl, entbonus, surrgain, meanent; flat gradient or None)"""
         import ctypes as C
+        from . import _abi as A
         dev = ob.device
         sc = self._pg_buffers(dev)
         rms_mean, rms_std = self._rms_pol or (self.pi.ob_rms.mean, self.pi.ob_rms.std)
         out = torch.empty(2, dtype=torch.float64, device=dev)
         g = torch.empty(theta.numel(), dtype=torch.float32, device=dev) if with_grad else None
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = A.stream(dev)
         self._pg_call("dm_pg_losses", ob, int(ob.shape[0]), ac, atarg, old_mean, old_logstd, 1 if write_old else 0, theta, rms_mean, rms_std,
                       C.c_double(float(self.entcoeff)), 1 if with_grad else 0, g if with_grad else C.c_void_p(0), out, sc, st,
                       self._pg_grid((self.PG_GRAD_NS if with_grad else self.PG_LOSS_NS) * ob.shape[0]))
         logstd = theta[-28:]
-        meanent = (logstd + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+        meanent = (logstd + _HALF_LOG_2PI_E).sum()
         surr, kl = out[0].to(torch.float32), out[1].to(torch.float32)
         entbonus = self.entcoeff * meanent
         return torch.stack([surr + entbonus, kl, entbonus, surr, meanent]), g
 
     def _pg_fvp(self, ob, theta, v):
-        import ctypes as C
+        from . import _abi as A
         dev = ob.device
         sc = self._pg_buffers(dev)
         rms_mean, rms_std = self._rms_pol or (self.pi.ob_rms.mean, self.pi.ob_rms.std)
         k = int(self.fvp_subsample)
         nf = (int(ob.shape[0]) + k - 1) // k                                # rows of ob[::k]
         hv = torch.empty_like(v)
-        self._pg_call("dm_pg_fvp", ob, k, nf, theta, v.contiguous(), rms_mean, rms_std, hv, sc, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+        self._pg_call("dm_pg_fvp", ob, k, nf, theta, v.contiguous(), rms_mean, rms_std, hv, sc, A.stream(dev),
                       self._pg_grid(self.PG_FVP_NS * nf))
         return hv
 
     def _rms_update(self, ob):
-        """`pi.ob_rms.update(ob)` (:242): one launch (dm_rms_update) for a float32 batch on the GPU of a single-process run, else the tensor ops."""
-        rms = self.pi.ob_rms
-        if (ob.device.type == "cuda" and ob.dtype == torch.float32 and ob.dim() == 2 and ob.shape[1] == 56 and ob.is_contiguous() and _world(self.group) == 1
-                and tuple(rms.shape) == (56,) and torch.is_tensor(rms.count) and rms.sum.is_cuda and getattr(self.pi, "native", False)):
-            import ctypes as C
-            from . import _abi as A
-            L = A.load()
-            if getattr(self, "_rms_scratch", None) is None or self._rms_scratch.device != ob.device:
-                self._rms_scratch = torch.empty(int(L.dm_rms_scratch_bytes()), dtype=torch.uint8, device=ob.device)
-            p = lambda x: C.c_void_p(x.data_ptr())
-            A.check(L.dm_rms_update(p(ob), int(ob.shape[0]), p(rms.sum), p(rms.sumsq), p(rms.count), p(rms.mean), p(rms.std), p(self._rms_scratch),
-                                    C.c_void_p(torch.cuda.current_stream(ob.device).cuda_stream)), L)
-            return
-        rms.update(ob, group=self.group)
+        rms_update(self.pi, ob, self.group, self)
 
     def _next_perm(self, n, dev):
         """The next shuffle of `dataset.iterbatches` (:289) from this learner's generator — taken from the ones drawn ahead when they fit."""
@@ -527,7 +536,6 @@ class TrpoLearner:
     # ---- one update ----------------------------------------------------------------------------------------------------------
     def update(self, seg):
         pi = self.pi
-        import os
         prof = {} if os.environ.get("DM_TRPO_PROFILE") else None             # phase times (ms, device-synchronised) in stats["profile_ms"]
         t_last = [time.perf_counter()]
 
@@ -686,47 +694,13 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
     TimeElapsed, entropy, meankl, optimgain, surrgain, ev_tdlam_before).  With `log_dir`, rank 0 also writes the reference's
     files there: `progress.csv` (logger CSV, src/logger.py:101-135) and `monitor.json.monitor.csv` (bench.Monitor, one row per
     finished episode of rank 0's envs) — readable by the reference's plot_curve.py / load_results."""
-    import torch.distributed as dist
+    from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = TrpoLearner(pi, group=group, **learner_kwargs)
-    if isinstance(env, (list, tuple)):          # several env batches of this rank, stepped concurrently on their own streams
-        seg_gen = pipelined_segment_generator(pi, list(env), timesteps_per_batch, stochastic=True)
-        n_envs_local = sum(e.num_envs for e in env)
-    else:
-        # fused (default when possible): the policy step runs inside the env step kernel, one launch per rollout step
-        from .rollout import can_fuse
-        use_fused = can_fuse(pi, env) if fused is None else bool(fused)
-        seg_gen = traj_segment_generator(pi, env, timesteps_per_batch, stochastic=True, fused=use_fused)
-        n_envs_local = env.num_envs
-    world = _world(group)
-    rank = dist.get_rank(group) if world > 1 else 0
-    episodes_so_far = timesteps_so_far = iters_so_far = 0
-    tstart = time.time()
-    lenbuffer, rewbuffer = deque(maxlen=40), deque(maxlen=40)
-    history = []
-    progress = monitor = None
-    if log_dir and rank == 0:
-        from .logio import ProgressCsv, MonitorWriter
-        os.makedirs(log_dir, exist_ok=True)
-        progress = ProgressCsv(os.path.join(log_dir, "progress.csv"))
-        monitor = MonitorWriter(os.path.join(log_dir, "monitor.json"), t_start=tstart)
-    while True:
-        if callback:
-            callback(locals(), globals())
-        if max_timesteps and timesteps_so_far >= max_timesteps:
-            break
-        if max_iters and iters_so_far >= max_iters:
-            break
-        if max_seconds:
-            # the deadline is a per-process wall clock: decide collectively (MAX over ranks), or a rank that breaks first leaves
-            # the others waiting forever in the next update's all-reduces
-            stop = time.time() - tstart >= max_seconds
-            if world > 1:
-                flag = torch.tensor([1.0 if stop else 0.0], dtype=torch.float32, device=pi.device)
-                dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
-                stop = bool(flag.item() > 0)
-            if stop:
-                break
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused)
+    steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
+
+    def iterate(timesteps_so_far):
         if os.environ.get("DM_TRPO_PROFILE") and pi.device.type == "cuda":
             torch.cuda.synchronize(pi.device); t_seg = time.perf_counter()
             seg = next(seg_gen)
@@ -741,27 +715,18 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
         if getattr(seg, "info", None):
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
-        n_eps = torch.tensor([len(lens), sum(lens), sum(rets)], dtype=torch.float64, device=pi.device)
-        if world > 1:                                            # :300-302 allgather of (ep_lens, ep_rets): the sums suffice here
-            dist.all_reduce(n_eps, group=group)
-        lenbuffer.extend(lens[-40:]); rewbuffer.extend(rets[-40:])
-        episodes_so_far += int(n_eps[0]); timesteps_so_far += timesteps_per_batch * n_envs_local * world
-        iters_so_far += 1
-        stats.update(EpLenMean=float(sum(lenbuffer) / max(1, len(lenbuffer))), EpRewMean=float(sum(rewbuffer) / max(1, len(rewbuffer))),
-                     EpLenMeanIter=float(n_eps[1] / max(1.0, float(n_eps[0]))), EpThisIter=int(n_eps[0]), EpisodesSoFar=episodes_so_far,
-                     TimestepsSoFar=timesteps_so_far, TimeElapsed=time.time() - tstart, iteration=iters_so_far)
-        history.append(stats)
-        if progress is not None:
-            progress.writekvs({k: stats.get(k) for k in ("EpRewMean", "EpThisIter", "TimestepsSoFar", "EpisodesSoFar", "surrgain", "optimgain",
-                                                        "TimeElapsed", "meankl", "entloss", "ev_tdlam_before", "entropy", "EpLenMean")})
-            monitor.write_episodes(rets, lens)
-        if log and rank == 0:
-            log("iter %4d  steps %10d  eps %7d  EpLenMean %7.1f  (this iter %7.1f)  entropy %6.2f  meankl %.4f  surrgain %+.4f  ev %.3f  %.1fs"
-                % (iters_so_far, timesteps_so_far, stats["EpThisIter"], stats["EpLenMean"], stats["EpLenMeanIter"], stats.get("entropy", float("nan")),
-                   stats.get("meankl", float("nan")), stats.get("surrgain", float("nan")), stats["ev_tdlam_before"], stats["TimeElapsed"]))
-    if progress is not None:
-        progress.close(); monitor.close()
-    return history
+        return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
+
+    def log_line(stats):
+        return ("iter %4d  steps %10d  eps %7d  EpLenMean %7.1f  (this iter %7.1f)  entropy %6.2f  meankl %.4f  surrgain %+.4f  ev %.3f  %.1fs"
+                % (stats["iteration"], stats["TimestepsSoFar"], stats["EpThisIter"], stats["EpLenMean"], stats["EpLenMeanIter"],
+                   stats.get("entropy", float("nan")), stats.get("meankl", float("nan")), stats.get("surrgain", float("nan")),
+                   stats["ev_tdlam_before"], stats["TimeElapsed"]))
+
+    return train_loop.run(pi, iterate, window=40, log_line=log_line, names=locals(), max_iters=max_iters, max_timesteps=max_timesteps,
+                          max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir,
+                          columns=("EpRewMean", "EpThisIter", "TimestepsSoFar", "EpisodesSoFar", "surrgain", "optimgain", "TimeElapsed", "meankl",
+                                   "entloss", "ev_tdlam_before", "entropy", "EpLenMean"))
 
 
 def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print, save_sample=None, frames=None, render_size=(500, 500),

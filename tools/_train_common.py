@@ -1,0 +1,71 @@
+"""What train_trpo.py, train_ppo.py and train_gail.py share: the env arguments, device / process-group set-up, reading and writing a policy,
+and the `--task evaluate` branch."""
+import os
+
+import torch
+
+from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
+
+
+def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
+    """--motion, --obs-mode, --action-mode and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    ap.add_argument("--motion", default="walk")
+    if reward_help:
+        ap.add_argument("--reward", default="alive", help=reward_help)
+    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
+                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
+                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
+                         "env; at 171 the learners run on their torch paths")
+    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
+                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
+    if autoreset_help:
+        ap.add_argument("--autoreset", default="init", help=autoreset_help)
+    if frame_skip_help:
+        ap.add_argument("--frame-skip", default=None, help=frame_skip_help)
+
+
+def env_kwargs(args):
+    """The DPVecEnv arguments that the env flags set."""
+    fs = getattr(args, "frame_skip", None)
+    return dict(motion=args.motion, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
+                frame_skip=fs if fs in (None, "mocap") else int(fs))
+
+
+def init_device(dist_backend):
+    """This rank's GPU and, in a torchrun launch, the process group -> (world, rank, local device index, torch device)."""
+    world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); lr = int(os.environ.get("LOCAL_RANK", "0"))
+    ndev = torch.cuda.device_count()
+    if dist_backend == "nccl" and world > ndev:
+        raise SystemExit("RCCL needs one GPU per rank: %d ranks, %d devices visible (use --dist-backend gloo to share a GPU)" % (world, ndev))
+    lr = lr % max(1, ndev)
+    torch.cuda.set_device(lr)
+    dev = torch.device("cuda", lr)
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if dist_backend == "nccl":
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        else:
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+    return world, rank, lr, dev
+
+
+def load_policy(path, dev):
+    """An .npz (reference variable names) or a tf.train.Saver checkpoint prefix."""
+    return MlpPolicy.from_npz(path, device=dev) if path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(path, device=dev)
+
+
+def save_policy(pi, path):
+    """`x.npz`, or a checkpoint prefix -> the tf.train.Saver bundle the reference's `--task evaluate --load_model_path x` restores."""
+    if path.endswith(".npz"):
+        pi.save_npz(path)
+    else:
+        pi.save_tf_checkpoint(path)
+
+
+def eval_setup(args, dev):
+    """`--task evaluate` (src/trpo.py:480-487) -> (an env of --number-trajs trajectories, the policy of --load-model-path) for trpo.runner."""
+    assert args.load_model_path, "--task %s needs --load-model-path" % args.task
+    pi = load_policy(args.load_model_path, dev)
+    pi.seed(args.seed)
+    return DPVecEnv(args.number_trajs, device=dev.index, autoreset="init", seed=args.seed, **env_kwargs(args)), pi

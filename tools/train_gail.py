@@ -21,6 +21,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import _train_common as common  # noqa: E402
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy  # noqa: E402
 from deepmimic_mujoco_amd import behavior_clone  # noqa: E402
 from deepmimic_mujoco_amd.gail import ExpertDataset, TransitionClassifier, learn  # noqa: E402
@@ -48,13 +49,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--num-timesteps", type=int, default=0, help="stop after this many timesteps of finished episodes (the reference's --num_timesteps)")
-    ap.add_argument("--motion", default="walk")
-    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
-                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
-                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
-                         "env; at 171 the learners run on their torch paths")
-    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
-                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
+    common.add_env_args(ap)
     ap.add_argument("--reward", default="alive", help="the env's own reward (logged as EpTrueRewMean)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON")
@@ -68,26 +63,21 @@ def main():
     torch.cuda.set_device(dev)
     if args.task in ("evaluate", "sample"):
         from deepmimic_mujoco_amd.trpo import runner
-        assert args.load_model_path, "--task %s needs --load-model-path" % args.task
-        pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
-        pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=0, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed)
+        env, pi = common.eval_setup(args, dev)
         save = args.save_sample or ("sample.npz" if args.task == "sample" else None)
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=save)
         return
     assert args.expert_path, "--task train needs --expert-path"
     expert = ExpertDataset(args.expert_path, traj_limitation=args.traj_limitation, seed=args.seed, device=dev)
-    env = DPVecEnv(args.envs, motion=args.motion, device=0, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed)
+    env = DPVecEnv(args.envs, device=0, autoreset="init", seed=args.seed, **common.env_kwargs(args))
     pi = MlpPolicy(ob_dim=env.observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed)
     if args.pretrained:                                     # src/gail.py:490-495
         t0 = time.time()
         train, _ = behavior_clone.learn(pi, expert, max_iters=args.BC_max_iter, verbose=True, seed=args.seed)
         print("BC done: %d iterations in %.2f s, train loss %.6f -> %.6f (mean of the first / last %d)"
               % (len(train), time.time() - t0, train[:100].mean(), train[-100:].mean(), min(100, len(train))))
-        if args.bc_save and args.bc_save.endswith(".npz"):
-            pi.save_npz(args.bc_save)
-        elif args.bc_save:
-            pi.save_tf_checkpoint(args.bc_save)
+        if args.bc_save:
+            common.save_policy(pi, args.bc_save)
     reward_giver = TransitionClassifier(ob_dim=env.observation_space.shape[0], hidden_size=args.adversary_hidden_size, entcoeff=args.adversary_entcoeff, device=dev, seed=args.seed)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     hist = learn(env, pi, reward_giver, expert, g_step=args.g_step, d_step=args.d_step, d_stepsize=args.d_stepsize, timesteps_per_batch=args.horizon,
@@ -96,12 +86,8 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump({"args": vars(args), "history": hist}, open(args.out, "w"))
     if args.save:
-        if args.save.endswith(".npz"):
-            pi.save_npz(args.save)
-            reward_giver.save_npz(args.save[:-4] + ".adversary.npz")
-        else:
-            pi.save_tf_checkpoint(args.save)
-            reward_giver.save_npz(args.save + ".adversary.npz")
+        common.save_policy(pi, args.save)
+        reward_giver.save_npz((args.save[:-4] if args.save.endswith(".npz") else args.save) + ".adversary.npz")
     if hist:
         h = hist[-1]
         print("done: %d iterations in %.1f s, EpLenMean %.1f, EpRewMean %.3f, EpTrueRewMean %.3f, generator_acc %.3f, expert_acc %.3f"

@@ -14,9 +14,8 @@ import os
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only (RCCL across processes)
 import sys
 
-import torch
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import _train_common as common  # noqa: E402
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy  # noqa: E402
 from deepmimic_mujoco_amd.ppo import learn  # noqa: E402
 
@@ -42,16 +41,9 @@ def main():
     ap.add_argument("--adam-epsilon", type=float, default=1e-5)
     ap.add_argument("--schedule", default=None, choices=["constant", "linear"], help="default: linear with --num-timesteps, else constant")
     ap.add_argument("--no-native", action="store_true", help="the update through torch autograd instead of the dm_ppo_* kernels")
-    ap.add_argument("--motion", default="walk")
-    ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
-    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
-                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
-                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
-                         "env; at 171 the learners run on their torch paths")
-    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
-                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
-    ap.add_argument("--autoreset", default="init", help="init (the reference's protocol) | rsi (DeepMimic reference-state initialisation)")
-    ap.add_argument("--frame-skip", default=None, help="sim steps per env step, or 'mocap' (default: 1)")
+    common.add_env_args(ap, reward_help="alive | v3-config | v2-pose | imitation",
+                        autoreset_help="init (the reference's protocol) | rsi (DeepMimic reference-state initialisation)",
+                        frame_skip_help="sim steps per env step, or 'mocap' (default: 1)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON")
     ap.add_argument("--log-dir", default=None, help="write progress.csv and monitor.csv in the reference's formats")
@@ -59,31 +51,13 @@ def main():
     ap.add_argument("--save", default=None, help="write the trained policy: `x.npz` or a checkpoint prefix (the tf.train.Saver bundle the "
                                                  "reference's `--task evaluate --load_model_path x` restores)")
     args = ap.parse_args()
-    world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); lr = int(os.environ.get("LOCAL_RANK", "0"))
-    ndev = torch.cuda.device_count()
-    if args.dist_backend == "nccl" and world > ndev:
-        raise SystemExit("RCCL needs one GPU per rank: %d ranks, %d devices visible (use --dist-backend gloo to share a GPU)" % (world, ndev))
-    lr = lr % max(1, ndev)
-    torch.cuda.set_device(lr)
-    dev = torch.device("cuda", lr)
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-        else:
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-    fs = args.frame_skip if args.frame_skip in (None, "mocap") else int(args.frame_skip)
+    world, rank, lr, dev = common.init_device(args.dist_backend)
     if args.task == "evaluate":
         from deepmimic_mujoco_amd.trpo import runner
-        assert args.load_model_path, "--task evaluate needs --load-model-path"
-        pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
-        pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed, frame_skip=fs)
+        env, pi = common.eval_setup(args, dev)
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy)
         return
-    env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
-                   env_offset=rank * args.envs, frame_skip=fs)
+    env = DPVecEnv(args.envs, device=lr, autoreset=args.autoreset, seed=args.seed + 10000 * rank, env_offset=rank * args.envs, **common.env_kwargs(args))
     pi = MlpPolicy(ob_dim=env.observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     schedule = args.schedule or ("linear" if "max_timesteps" in stop else "constant")
@@ -95,10 +69,7 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump({"args": vars(args), "world": world, "history": hist}, open(args.out, "w"))
         if args.save:
-            if args.save.endswith(".npz"):
-                pi.save_npz(args.save)
-            else:
-                pi.save_tf_checkpoint(args.save)
+            common.save_policy(pi, args.save)
         if hist:
             h = hist[-1]
             print("done: %d iterations, %d env steps in %.1f s, EpLenMean %.1f (last iter %.1f), loss_kl %.5f, clipfrac %.3f"

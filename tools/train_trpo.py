@@ -10,9 +10,8 @@ import os
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only (RCCL across processes)
 import sys
 
-import torch
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import _train_common as common  # noqa: E402
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy  # noqa: E402
 from deepmimic_mujoco_amd.trpo import learn  # noqa: E402
 
@@ -26,16 +25,9 @@ def main():
     ap.add_argument("--vf-batch", type=int, default=4096)
     ap.add_argument("--vf-stepsize", type=float, default=1e-3)
     ap.add_argument("--max-kl", type=float, default=0.01)
-    ap.add_argument("--motion", default="walk")
-    ap.add_argument("--reward", default="alive", help="alive | v3-config | v2-pose | imitation")
-    ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
-                    help="the observation: dp_env_v3 = the reference's 56 numbers; deepmimic = DeepMimic's 171 state features (phase, root height, every body's "
-                         "position / rotation in the root's heading frame and its velocities: one more launch per step).  The policy takes its width from the "
-                         "env; at 171 the learners run on their torch paths")
-    ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
-                    help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
-    ap.add_argument("--autoreset", default="init", help="init (the reference's trpo.py protocol) | rsi (DeepMimic reference-state initialisation)")
-    ap.add_argument("--frame-skip", default=None, help="sim steps per env step, or 'mocap' (default: 1; 'mocap' with --reward imitation)")
+    common.add_env_args(ap, reward_help="alive | v3-config | v2-pose | imitation",
+                        autoreset_help="init (the reference's trpo.py protocol) | rsi (DeepMimic reference-state initialisation)",
+                        frame_skip_help="sim steps per env step, or 'mocap' (default: 1; 'mocap' with --reward imitation)")
     ap.add_argument("--pipeline", type=int, default=2, help="sub-batches whose step launches overlap across consecutive steps (DM_OPT_PIPELINE; with "
                                                             "--unfused: that many env batches on their own streams, policy -> env chains overlap)")
     ap.add_argument("--unfused", action="store_true", help="separate policy launch per step instead of the policy step inside the env step kernel")
@@ -59,27 +51,11 @@ def main():
     ap.add_argument("--save", default=None, help="write the trained policy: `x.npz` (reference variable names) or a checkpoint prefix -> "
                                                  "tf.train.Saver bundle (x.index + x.data-00000-of-00001) the reference's `--task evaluate --load_model_path x` restores")
     args = ap.parse_args()
-    world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); lr = int(os.environ.get("LOCAL_RANK", "0"))
-    ndev = torch.cuda.device_count()
-    if args.dist_backend == "nccl" and world > ndev:
-        raise SystemExit("RCCL needs one GPU per rank: %d ranks, %d devices visible (use --dist-backend gloo to share a GPU)" % (world, ndev))
-    lr = lr % max(1, ndev)
-    torch.cuda.set_device(lr)
-    dev = torch.device("cuda", lr)
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-        else:
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-    fs = args.frame_skip if args.frame_skip in (None, "mocap") else int(args.frame_skip)
+    world, rank, lr, dev = common.init_device(args.dist_backend)
+    kw = common.env_kwargs(args)
     if args.task == "evaluate":                     # src/trpo.py:480-487
         from deepmimic_mujoco_amd.trpo import runner
-        assert args.load_model_path, "--task evaluate needs --load-model-path"
-        pi = MlpPolicy.from_npz(args.load_model_path, device=dev) if args.load_model_path.endswith(".npz") else MlpPolicy.from_tf_checkpoint(args.load_model_path, device=dev)
-        pi.seed(args.seed)
-        env = DPVecEnv(args.number_trajs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset="init", seed=args.seed, frame_skip=fs)
+        env, pi = common.eval_setup(args, dev)
         writer = None
         if args.render_out:
             from deepmimic_mujoco_amd.render import FrameWriter
@@ -92,13 +68,12 @@ def main():
     P = max(1, args.pipeline)
     if args.unfused:
         cuts = [args.envs * h // P for h in range(P + 1)]
-        envs = [DPVecEnv(cuts[h + 1] - cuts[h], motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
-                         env_offset=rank * args.envs + cuts[h], frame_skip=fs) for h in range(P)]
+        envs = [DPVecEnv(cuts[h + 1] - cuts[h], device=lr, autoreset=args.autoreset, seed=args.seed + 10000 * rank, env_offset=rank * args.envs + cuts[h], **kw)
+                for h in range(P)]
         env = envs if P > 1 else envs[0]
     else:
         from deepmimic_mujoco_amd import _abi as A
-        env = DPVecEnv(args.envs, motion=args.motion, device=lr, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode, autoreset=args.autoreset, seed=args.seed + 10000 * rank,
-                       env_offset=rank * args.envs, frame_skip=fs)
+        env = DPVecEnv(args.envs, device=lr, autoreset=args.autoreset, seed=args.seed + 10000 * rank, env_offset=rank * args.envs, **kw)
         env.batch.set_option(A.OPT_PIPELINE, min(P, A.MAX_PIPELINE))
     pi = MlpPolicy(ob_dim=(envs[0] if args.unfused else env).observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     hist = learn(env, pi, timesteps_per_batch=args.horizon, max_seconds=args.seconds if not args.iters else 0, max_iters=args.iters,
@@ -112,10 +87,7 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump({"args": vars(args), "world": world, "history": hist}, open(args.out, "w"))
         if args.save:
-            if args.save.endswith(".npz"):
-                pi.save_npz(args.save)
-            else:
-                pi.save_tf_checkpoint(args.save)
+            common.save_policy(pi, args.save)
         best = max(h["EpLenMeanIter"] for h in hist)
         print("done: %d iterations, %d env steps in %.1f s (%.0f steps/s incl. learner), EpLenMean(last iter) %.1f, best %.1f"
               % (len(hist), hist[-1]["TimestepsSoFar"], hist[-1]["TimeElapsed"], hist[-1]["TimestepsSoFar"] / hist[-1]["TimeElapsed"],
