@@ -647,6 +647,7 @@ extern "C" int dm_batch_step(dm_batch* b, const double* action, double* obs, dou
 extern "C" int dm_batch_step_act(dm_batch* b, const double* action, double* obs, double* reward, uint8_t* done, int32_t nsub,
                                  const float* weights, double* next_action, float* next_vpred, int32_t stochastic, uint64_t seed, uint64_t counter) {
   if (!weights || !next_action || !next_vpred) return fail(DM_EINVAL, "dm_batch_step_act: null policy argument");
+  if (!aligned16(weights)) return fail(DM_EINVAL, "dm_batch_step_act: weights must be 16-byte aligned");
   dmp::PolicyArgs pa{weights, next_action, next_vpred, (int)stochastic, (unsigned long long)seed, (unsigned long long)counter};
   return step_impl(b, action, obs, reward, done, nsub, DM_PTR_DEVICE, &pa);
 }
@@ -654,6 +655,9 @@ extern "C" int dm_batch_step_act(dm_batch* b, const double* action, double* obs,
 /* T steps per call (device pointers).  On the packed path ONE launch runs the whole horizon (k_rollout_packed); elsewhere T step launches. */
 extern "C" int dm_batch_rollout(dm_batch* b, double* action, double* obs, double* reward, uint8_t* done, int32_t T, int32_t nsub,
                                 const float* weights, float* vpred, int32_t stochastic, uint64_t seed, uint64_t counter) {
+  // (the in-wave policy step loads the weights as float4.  Refused before `b` is looked at, as in dm_batch_step_act, where step_impl checks `b`: a call
+  //  can then be shown to be refused without a device, on which alone a batch exists)
+  if (!aligned16(weights)) return fail(DM_EINVAL, "dm_batch_rollout: weights must be 16-byte aligned");
   if (!b || !action || !obs || !reward || !done || T < 1 || nsub < 1) return fail(DM_EINVAL, "dm_batch_rollout: bad argument");
   if (weights && !vpred) return fail(DM_EINVAL, "dm_batch_rollout: a policy needs the value rows");
   const size_t n = (size_t)b->n;

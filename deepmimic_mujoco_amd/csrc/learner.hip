@@ -56,7 +56,7 @@ extern "C" int dm_vf_fit_epoch(const float* ob, const float* ret, int32_t nb, in
                                const float* step_scale_host, double beta1, double beta2, double eps, double* rms_sum, double* rms_sumsq,
                                double* rms_count, float* rms_mean, float* rms_std, void* scratch, void* hip_stream, int32_t epoch_filter) {
   if (!ob || !ret || !theta || !adam_m || !adam_v || !step_scale_host || !rms_sum || !rms_sumsq || !rms_count || !rms_mean || !rms_std || !scratch ||
-      nb < 1 || bs < 1)
+      nb < 1 || bs < 1 || !aligned16(theta))                    // (the kernels stage theta with float4 loads)
     return fail(DM_EINVAL, "dm_vf_fit_epoch: bad argument");
   hipStream_t st = (hipStream_t)hip_stream;
   { // launch on the device that owns the parameters (the caller's stream belongs to it), whatever the thread's current device is
@@ -127,7 +127,8 @@ extern "C" size_t dm_pg_scratch_bytes(void) { return (size_t)dmg::MAX_BLOCKS * d
 extern "C" int dm_pg_losses(const float* ob, int32_t n, const float* ac, const float* atarg, float* old_mean, const float* old_logstd, int32_t write_old,
                             const float* theta, const float* rms_mean, const float* rms_std, double entcoeff, int32_t with_grad,
                             float* out_grad, double* out_losses, void* scratch, void* hip_stream, int32_t max_blocks) {
-  if (!ob || !ac || !atarg || !old_mean || !old_logstd || !theta || !rms_mean || !rms_std || !out_losses || !scratch || n < 1 || (with_grad && !out_grad) || max_blocks < 0)
+  if (!ob || !ac || !atarg || !old_mean || !old_logstd || !theta || !rms_mean || !rms_std || !out_losses || !scratch || n < 1 || (with_grad && !out_grad) || max_blocks < 0 ||
+      !aligned16(theta))
     return fail(DM_EINVAL, "dm_pg_losses: bad argument");
   if (set_device_of(theta)) return fail(DM_EHIP, "dm_pg_losses: hipSetDevice failed");
   hipStream_t st = (hipStream_t)hip_stream;
@@ -147,7 +148,8 @@ extern "C" int dm_pg_losses(const float* ob, int32_t n, const float* ac, const f
 }
 extern "C" int dm_pg_fvp(const float* ob, int32_t stride, int32_t n, const float* theta, const float* v, const float* rms_mean, const float* rms_std,
                          float* out_fv, void* scratch, void* hip_stream, int32_t max_blocks) {
-  if (!ob || !theta || !v || !rms_mean || !rms_std || !out_fv || !scratch || n < 1 || stride < 1 || max_blocks < 0) return fail(DM_EINVAL, "dm_pg_fvp: bad argument");
+  if (!ob || !theta || !v || !rms_mean || !rms_std || !out_fv || !scratch || n < 1 || stride < 1 || max_blocks < 0 || !aligned16(theta))
+    return fail(DM_EINVAL, "dm_pg_fvp: bad argument");
   if (set_device_of(theta)) return fail(DM_EHIP, "dm_pg_fvp: hipSetDevice failed");
   hipStream_t st = (hipStream_t)hip_stream;
   const int ntiles = (n + dmg::SB - 1) / dmg::SB, nblk = pg_blocks(ntiles, max_blocks);

@@ -313,7 +313,8 @@ int dm_batch_read_profile(dm_batch* b, long long* out_host);
  * for a whole batch in one launch: obz = clip((ob - mean) / std, +-5), policy and value 2x100 tanh MLPs, Gaussian sample.
  * All pointers are DEVICE pointers on the current HIP device; `weights` is the packed float32 parameter block
  * (dm_policy_weight_count() floats; layout in csrc/policy_kernel.h, filled by deepmimic_mujoco_amd/policy.py MlpPolicy.pack).
- * Noise is a counter-based stream keyed by (seed, counter, env, action): pass a fresh `counter` per call. */
+ * Noise is a counter-based stream keyed by (seed, counter, env, action): pass a fresh `counter` per call.  dm_policy_act reads `weights`
+ * element by element: it asks for no alignment beyond a float's (dm_batch_step_act / dm_batch_rollout below do). */
 int dm_policy_weight_count(void);
 int dm_policy_act(const float* weights, const double* obs, double* action, float* vpred, int32_t n, int32_t stochastic,
                   uint64_t seed, uint64_t counter, void* hip_stream);
@@ -322,7 +323,8 @@ int dm_policy_act(const float* weights, const double* obs, double* action, float
  * obs / reward / done as dm_batch_step does and then next_action[e] (28) and next_vpred[e] for that observation (the fresh episode's
  * after an auto-reset).  One launch per rollout step (src/trpo.py:47-66: `ac, vpred = pi.act(ob)`; `ob, rew, new, _ = env.step(ac)`),
  * so consecutive steps of a pipelined batch (DM_OPT_PIPELINE) overlap although every step's action depends on the last one's
- * observation: that dependency stays inside a sub-batch's stream.  Device pointers only; same noise stream as dm_policy_act. */
+ * observation: that dependency stays inside a sub-batch's stream.  Device pointers only; same noise stream as dm_policy_act.  `weights` must
+ * be 16-byte aligned (the in-wave policy step loads it as float4s): DM_EINVAL otherwise, before anything is launched. */
 int dm_batch_step_act(dm_batch* b, const double* action, double* obs, double* reward, uint8_t* done, int32_t n_substeps,
                       const float* weights, double* next_action, float* next_vpred, int32_t stochastic, uint64_t seed, uint64_t counter);
 
@@ -338,7 +340,7 @@ int dm_batch_step_act(dm_batch* b, const double* action, double* obs, double* re
  * wave's sum over T steps instead of the sum of every step's slowest wave (4 096 envs: 17.3 M env-steps/s against 12.2 M through
  * dm_batch_step); an environment that exceeds the packed path's capacities in some step is re-stepped inside its wave by the one-env code.
  * Otherwise — always in action modes 3 and 4, whose controller lives in the per-step kernels — T step launches are issued: the results are those
- * of T dm_batch_step / dm_batch_step_act calls, bit for bit. */
+ * of T dm_batch_step / dm_batch_step_act calls, bit for bit.  `weights`, when given, must be 16-byte aligned (DM_EINVAL otherwise). */
 int dm_batch_rollout(dm_batch* b, double* action, double* obs, double* reward, uint8_t* done, int32_t T, int32_t n_substeps,
                      const float* weights, float* vpred, int32_t stochastic, uint64_t seed, uint64_t counter);
 
@@ -363,7 +365,8 @@ int dm_episode_scan(const double* reward, const uint8_t* done, int32_t T, int32_
  * (step_scale_host: HOST array [nb]).  All of it enqueued by this one call; device pointers otherwise; `scratch`:
  * dm_vf_scratch_bytes(nb, bs) bytes on the device.  epoch_filter = 1: the filter's sums of all nb minibatches are taken up front (two
  * launches) and two launches per minibatch remain (gradient partials; reduction + Adam); 0: three launches per minibatch.  Same arithmetic
- * in the same order either way: bit-identical results. */
+ * in the same order either way: bit-identical results.  theta must be 16-byte aligned (the kernels stage it with float4 loads): DM_EINVAL
+ * otherwise, before anything is launched. */
 int dm_vf_param_count(void);
 size_t dm_vf_scratch_bytes(int32_t nb, int32_t bs);
 int dm_vf_fit_epoch(const float* ob, const float* ret, int32_t nb, int32_t bs, float* theta, float* adam_m, float* adam_v,
@@ -389,7 +392,8 @@ int dm_rms_update(const float* ob, int32_t n, double* rms_sum, double* rms_sumsq
  *                 caller adds cg_damping * v (:229).  One forward-mode and one reverse pass per sample, no second-order graph.
  * Both run one workgroup per CU (their LDS fills it); max_blocks > 0 caps the grid, which leaves the other CUs to a kernel of another stream
  * (the learner runs the value fit beside the policy step that way).  Sums are taken in block order: the result is a function of the grid
- * size, not of timing.  max_blocks = 0: every CU. */
+ * size, not of timing.  max_blocks = 0: every CU.  Both refuse a theta that is not 16-byte aligned (float4 loads) with DM_EINVAL, before anything
+ * is launched. */
 int dm_pg_param_count(void);
 size_t dm_pg_scratch_bytes(void);
 int dm_pg_losses(const float* ob, int32_t n, const float* ac, const float* atarg, float* old_mean, const float* old_logstd, int32_t write_old,

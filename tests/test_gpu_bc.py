@@ -12,6 +12,7 @@ from deepmimic_mujoco_amd import behavior_clone as BC
 from deepmimic_mujoco_amd.gail import ExpertDataset, TransitionClassifier, learn
 from deepmimic_mujoco_amd.trpo import POL_KEYS, VF_KEYS, MpiAdam
 from tests import bc_numpy as N
+from tests import learner_blocks as LB
 from tests.test_behavior_clone import random_policy
 from tests.test_policy import CKPT
 
@@ -96,6 +97,9 @@ def test_bc_lossgrad_matches_numpy(setup, n):
             assert np.isfinite(g).all()
             err = np.abs(g - gref).max() / np.abs(gref).max()
             assert err <= 1e-4, (gathered, stochastic, err)
+            print("bc n=%d gathered=%d stochastic=%d: per block %s" % (n, gathered, stochastic, LB.block_errors(g, gref, LB.POLICY)))
+            LB.assert_well_scaled(gref, LB.POLICY, exempt=() if stochastic else ("logstd",))
+            LB.assert_blocks(g, gref, LB.POLICY, LB.BAR, "bc n=%d gathered=%d stochastic=%d" % (n, gathered, stochastic))      # every block against its own largest entry
             if stochastic:
                 ls = np.abs(gref[-28:]).max()
                 assert np.abs(g[-28:] - gref[-28:]).max() <= 1e-4 * ls

@@ -10,6 +10,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy, SegmentCollector
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd.gail import ExpertDataset, TransitionClassifier, learn
 from tests import gail_numpy as G
+from tests import learner_blocks as LB
 from tests.test_policy import CKPT
 
 DEV = "cuda:0"
@@ -75,6 +76,8 @@ def test_disc_lossgrad_matches_numpy_and_is_reproducible():
     scale = np.abs(ref_g).max()
     assert abs(np.linalg.norm(gk) - np.linalg.norm(ref_g)) <= 1e-4 * np.linalg.norm(ref_g)
     assert np.abs(gk - ref_g).max() <= 1e-4 * scale, np.abs(gk - ref_g).max() / scale
+    print("disc 4099, 1000: per block %s" % LB.block_errors(gk, ref_g, LB.DISC))
+    LB.assert_blocks(gk, ref_g, LB.DISC, LB.BAR, "disc")               # ... and per block: against the block's own largest entry
     # and the torch path (used where the kernels cannot run) agrees with both
     rg.native = False
     lt, gt = rg.lossandgrad(f(gob), f(gac), f(eob), f(eac))

@@ -15,6 +15,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import ppo
 from deepmimic_mujoco_amd.trpo import MpiAdam
+from tests import learner_blocks as LB
 from tests import ppo_numpy as P
 from tests.test_policy import CKPT
 from tests.test_ppo import problem
@@ -96,6 +97,8 @@ def test_ppo_lossgrad_matches_numpy(setup, n, gathered):
     for lo, hi in ((0, P.NPI), (P.NPI, NTH)):                          # per half: against the half's largest entry
         scale = np.abs(gref[lo:hi]).max()
         assert np.abs(g[lo:hi] - gref[lo:hi]).max() <= 1e-4 * scale, (lo, np.abs(g[lo:hi] - gref[lo:hi]).max(), scale)
+    print("ppo n=%d gathered=%d: per block %s" % (n, gathered, LB.block_errors(g, gref, LB.PPO)))
+    LB.assert_blocks(g, gref, LB.PPO, LB.BAR, "ppo n=%d" % n)         # ... and per block: against the block's own largest entry
     # the losses alone (no gradient): the same numbers
     lonly, _ = lossgrad(setup, n, rows if gathered else None, ent=ent, grad=False)
     assert np.array_equal(lonly, losses)
@@ -110,7 +113,7 @@ def test_ppo_lossgrad_is_bitwise_reproducible(setup):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("bs", [64, 4096])
+@pytest.mark.parametrize("bs", [1, 33, 64, 4096])
 def test_ppo_fit_one_step_equals_lossgrad_and_adam(setup, bs):
     rng = np.random.RandomState(bs)
     rows = rng.choice(NROWS, bs, replace=False)

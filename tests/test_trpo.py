@@ -8,6 +8,7 @@ import torch
 
 from deepmimic_mujoco_amd.policy import MlpPolicy
 from deepmimic_mujoco_amd.trpo import TrpoLearner, MpiAdam, cg, flat, learn, explained_variance, POL_KEYS
+from tests import learner_blocks as LB
 
 
 def test_cg_matches_reference_iteration_and_solves_spd():
@@ -376,7 +377,7 @@ def _pg_case(n, seed=0):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [1, 33, 1000, 32 * 256 * 3 + 7])    # one sample; one tile + one row; a ragged last tile; more tiles than blocks (every block loops) + a ragged tail
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 161, 1000, 32 * 256 * 3 + 7])    # one sample; a tile less one row; one tile; one tile + one row; 33 Fisher samples (every 5th of 161); a ragged last tile; more tiles than blocks (every block loops) + a ragged tail
 def test_native_policy_gradient_and_fisher_product_match_the_analytic_float64_formulas_on_gpu(n):
     """dm_pg_losses / dm_pg_fvp against tests/trpo_numpy.py (src/trpo.py:224-230 written out by hand in float64): surrogate gradient at
     pi == oldpi, F v = J^T Sigma^-1 J v / N_f (+) 2 v on every 5th sample, and the losses at a moved policy — float32 tolerances."""
@@ -401,6 +402,9 @@ def test_native_policy_gradient_and_fisher_product_match_the_analytic_float64_fo
     rel = lambda a, b: float(np.linalg.norm(np.asarray(a, dtype=np.float64) - b) / np.linalg.norm(b))
     assert rel(old_mean.cpu().numpy(), m0) < 1e-5
     assert rel(g.cpu().numpy(), g_ref) < 2e-4, rel(g.cpu().numpy(), g_ref)
+    # ... and block by block: the biases and logstd cannot hide in the norm
+    print("pg n=%d: g per block %s" % (n, LB.block_errors(g.cpu().numpy(), g_ref, LB.POLICY)))
+    LB.assert_blocks(g.cpu().numpy(), g_ref, LB.POLICY, LB.BAR, "pg n=%d g" % n)
     L = losses.cpu().numpy()
     assert abs(L[3] - a64.mean()) < 1e-5 and abs(L[1]) < 1e-6 and abs(L[0] - L[3] - L[2]) < 1e-6      # ratio == 1, KL == 0 at pi == oldpi
     # Fisher-vector product on every 5th sample
@@ -411,6 +415,9 @@ def test_native_policy_gradient_and_fisher_product_match_the_analytic_float64_fo
     fv_ref = TN.pol_backward(p, cache_f, TN.pol_jvp(p, cache_f, vd) / sig2 / xs.shape[0], 2.0 * vd["logstd"].reshape(-1))
     fv = learner._pg_fvp(ob_t, theta0, t(v.astype(np.float32)))
     assert rel(fv.cpu().numpy(), fv_ref) < 2e-4, rel(fv.cpu().numpy(), fv_ref)
+    assert xs.shape[0] == (n + 4) // 5
+    print("pg n=%d: fv per block %s" % (n, LB.block_errors(fv.cpu().numpy(), fv_ref, LB.POLICY)))
+    LB.assert_blocks(fv.cpu().numpy(), fv_ref, LB.POLICY, LB.BAR, "pg n=%d fv" % n)
     v_t = t(v.astype(np.float32))
     assert float(v_t.dot(fv)) > 0                                             # positive definite along v
     # ... and against double back-propagation through torch's graph (the path it replaces)
@@ -569,3 +576,41 @@ def test_value_fit_with_the_epochs_filter_sums_up_front_equals_three_launches_pe
     for x, y in zip(*outs):
         assert torch.equal(x, y)
     assert bool(torch.isfinite(outs[1][0]).all()) and float((outs[1][1]).abs().max()) > 0
+
+
+@pytest.mark.parametrize("dtype", [64, 32])
+def test_pg_and_vf_abi_validates_arguments(dtype):
+    """dm_pg_losses, dm_pg_fvp and dm_vf_fit_epoch (and the weights of dm_batch_step_act / dm_batch_rollout, which the in-wave policy step
+    loads as float4s) refuse bad arguments — a theta that is not 16-byte aligned among them — before anything is launched: the calls below
+    pass host memory that is never dereferenced, and run without a device."""
+    import ctypes as C
+    from deepmimic_mujoco_amd import _abi as A
+    L = A.load(dtype)
+    assert L.dm_pg_param_count() == 18656 and L.dm_vf_param_count() == 15901
+    buf = np.zeros(72, dtype=np.float32)
+    base = (buf.ctypes.data + 15) // 16 * 16                           # a 16-byte aligned address inside the buffer
+    p = C.c_void_p(base)
+    off = C.c_void_p(base + 4)                                         # theta must be 16-byte aligned (float4 loads)
+    err = lambda: L.dm_last_error()
+
+    def losses(n=8, th=p, ob=p, g=p, with_grad=1, max_blocks=0):
+        return L.dm_pg_losses(ob, n, p, p, p, p, 1, th, p, p, 0.0, with_grad, g, p, p, None, max_blocks)
+    assert losses(th=off) == -1 and b"dm_pg_losses" in err()
+    assert losses(n=0) == -1 and losses(ob=None) == -1 and losses(th=None) == -1 and losses(g=None) == -1 and losses(max_blocks=-1) == -1
+    assert losses(th=off, with_grad=0, g=None) == -1 and b"dm_pg_losses" in err()
+
+    def fvp(n=8, stride=5, th=p, v=p):
+        return L.dm_pg_fvp(p, stride, n, th, v, p, p, p, p, None, 0)
+    assert fvp(th=off) == -1 and b"dm_pg_fvp" in err()
+    assert fvp(n=0) == -1 and fvp(stride=0) == -1 and fvp(v=None) == -1 and fvp(th=None) == -1
+    scale = (C.c_float * 2)(1e-4, 1e-4)
+
+    def vf(nb=2, bs=8, th=p, m=p, filt=0):
+        return L.dm_vf_fit_epoch(p, p, nb, bs, th, m, p, scale, 0.9, 0.999, 1e-8, p, p, p, p, p, p, None, filt)
+    assert vf(th=off) == -1 and b"dm_vf_fit_epoch" in err()
+    assert vf(th=off, filt=1) == -1 and b"dm_vf_fit_epoch" in err()
+    assert vf(nb=0) == -1 and vf(bs=0) == -1 and vf(th=None) == -1 and vf(m=None) == -1
+    # the policy step inside the env step kernels: the packed weights
+    assert L.dm_batch_step_act(None, p, p, p, p, 1, off, p, p, 0, 0, 0) == -1 and b"dm_batch_step_act" in err() and b"aligned" in err()
+    assert L.dm_batch_rollout(None, p, p, p, p, 4, 1, off, p, 0, 0, 0) == -1 and b"dm_batch_rollout" in err() and b"aligned" in err()
+    assert L.dm_batch_rollout(None, p, p, p, p, 4, 1, None, None, 0, 0, 0) == -1 and b"aligned" not in err()      # (no policy: nothing to align)
