@@ -376,6 +376,34 @@ class Batch(object):
         A.check(self._L.dm_batch_state_features(self._h, qp, vp, pp, ip, n, op, kind), self._L)
         return out
 
+    def floor_contacts(self, qpos=None, env_ids=None, out=None):
+        """Which geoms touch the floor, through dm_batch_floor_contacts (one launch): int32 [n], bit g (1..15) set when the collision stage of a
+        step would emit a contact for (floor, geom g) at the state.  Default: the batch's current state of every environment, or of `env_ids`
+        [n]; with qpos [n,35] (env_ids must then be None): those states.  Arrays as for `state_features`.  Reads the batch, changes nothing."""
+        if qpos is not None and env_ids is not None:
+            raise ValueError("qpos and env_ids exclude each other")
+        n = int(qpos.shape[0]) if qpos is not None else (int(len(env_ids)) if env_ids is not None else self.n)
+        device = any(_is_torch(x) for x in (qpos, env_ids, out))
+        if out is None:
+            if device:
+                import torch
+                out = torch.empty(n, dtype=torch.int32, device="cuda:%d" % self.device)
+            else:
+                out = np.empty(n, dtype=np.int32)
+        if device:
+            import torch
+            if qpos is not None and not _is_torch(qpos):
+                qpos = torch.as_tensor(np.ascontiguousarray(qpos, dtype=np.float64), device="cuda:%d" % self.device)
+            if env_ids is not None and not _is_torch(env_ids):
+                env_ids = torch.as_tensor(np.ascontiguousarray(env_ids, dtype=np.int32), device="cuda:%d" % self.device)
+        op, kind, _ko = self._ptr(out, np.int32, (n,), out=True)
+        qp, k1, _k1 = self._ptr(qpos, np.float64, (n, A.NQ)); ip, k2, _k2 = self._ptr(env_ids, np.int32, (n,))
+        kinds = {kind} | ({k1} if qpos is not None else set()) | ({k2} if env_ids is not None else set())
+        if len(kinds) != 1:
+            raise ValueError("floor_contacts buffers must be all numpy arrays or all device tensors")
+        A.check(self._L.dm_batch_floor_contacts(self._h, qp, ip, n, op, kind), self._L)
+        return out
+
     def set_state(self, qpos, qvel, frame_idx=None, mask=None):
         n = self.n
         qp, k, _a = self._ptr(qpos, np.float64, (n, A.NQ)); vp, k2, _b = self._ptr(qvel, np.float64, (n, A.NV))

@@ -1,5 +1,5 @@
 // batch_host.h — the batch behind a dm_batch* and what every entry point that takes one does first, shared by the units with batch entry points
-// (dmenv.hip: life cycle, state, step / rollout / queue; views.hip: render and state features).  Private to csrc/.
+// (dmenv.hip: life cycle, state, step / rollout / queue; views.hip: render, state features and floor contacts).  Private to csrc/.
 #pragma once
 #include <vector>
 
@@ -39,6 +39,8 @@ struct dm_batch {
   int pipe = 1; hipStream_t ps[DM_MAX_PIPELINE] = {}; hipEvent_t ev_in = nullptr, ev_done[DM_MAX_PIPELINE] = {}; bool pipe_pending = false;
   // dm_batch_render: view records and the staging of host arrays, grown on demand (dm_batch_state_features stages host arrays in it too)
   unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
+  // early termination (DM_OPT_FALL_BODIES, DM_OPT_MAX_EPISODE_STEPS; term_kernel.h): k_terminate follows every per-step launch while either is non-zero
+  unsigned fall_bodies = 0; int max_episode_steps = 0; int *d_ep_steps = nullptr, *d_done_reason = nullptr;   // [N] DM_F_EPISODE_STEPS, DM_F_DONE_REASON
 };
 // make the batch's stream wait for every sub-batch launch still in flight (no host wait)
 inline int pipe_join(dm_batch* b) {

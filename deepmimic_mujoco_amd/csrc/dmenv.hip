@@ -18,6 +18,7 @@ using namespace dm;
 // kinematics they share: in a unit of their own k_state_features and k_render_pose came out as different code objects (profiles/host_split.md)
 #include "render_kernel.h"
 #include "state_kernel.h"
+#include "term_kernel.h"
 static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
               DM_PACKED_MAXCAND == SLOT_MAXCAND, "include/dmenv.h documents the packed path's capacities: keep it in step with slot_kernel.h");
@@ -261,7 +262,7 @@ extern "C" void dm_batch_destroy(dm_batch* b) {
   if (b->ev_in) hipEventDestroy(b->ev_in);
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
@@ -306,6 +307,7 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   A(b->B.redo_list, n); A(b->B.redo_count, 2 * DM_MAX_PIPELINE); A(b->B.redo_why, 8);
   A(b->d_ord_cnt, DM_MAX_PIPELINE * 3 * ORD_BUCKETS);
   A(b->d_ord_list, (size_t)3 * ORD_BUCKETS * n);                      // (768 B per env of address space, 8 B of it touched per step; allocated here so that no step call can run out of memory half-way through its parts)
+  A(b->d_ep_steps, n); A(b->d_done_reason, n);
   A(b->d_qpos_in, (size_t)n * NQ); A(b->d_qvel_in, (size_t)n * NV); A(b->d_fidx_in, n); A(b->d_debug, DM_DEBUG_DOUBLES);
   if (sizeof(Real) != sizeof(Ext)) A(b->d_cvt, (size_t)n * NB * 3);   // largest Real field per env: xipos (42)
 #undef A
@@ -361,6 +363,12 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
     case DM_OPT_ACTION_MODE: if (v < 0 || v > 4) return fail(DM_EINVAL, "action mode must be 0..4"); b->B.action_mode = (int)v; break;
     case DM_OPT_SEED: b->B.seed = (unsigned long long)v; break;
     case DM_OPT_DIAGNOSTICS: b->B.diag = v != 0; break;
+    case DM_OPT_FALL_BODIES:
+      if (v < 0 || (v & ~(int64_t)0x3ffe)) return fail(DM_EINVAL, "DM_OPT_FALL_BODIES: a mask over model bodies 1..13 (bits 1..13)");
+      b->fall_bodies = (unsigned)v; break;
+    case DM_OPT_MAX_EPISODE_STEPS:
+      if (v < 0 || v > 0x7fffffff) return fail(DM_EINVAL, "DM_OPT_MAX_EPISODE_STEPS must be 0 (off) or a positive step count");
+      b->max_episode_steps = (int)v; break;
     case DM_OPT_PIPELINE: {
       if (v < 1 || v > DM_MAX_PIPELINE) return fail(DM_EINVAL, "pipeline depth must be 1..DM_MAX_PIPELINE");
       HIPCHK(hipSetDevice(b->device));
@@ -423,12 +431,15 @@ extern "C" int dm_batch_reset(dm_batch* b, int32_t mode, int32_t hard, const uin
   if ((rc = stage_in(b, b->d_mask, mask, (size_t)b->n, kind, &mk))) return rc;
   HIPCHK(hipMemsetAsync(b->B.kin_ok, 0, (size_t)b->n, b->stream));
   hipLaunchKernelGGL(k_reset, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk);
+  hipLaunchKernelGGL(k_zero_masked, dim3((b->n + 255) / 256), dim3(256), 0, b->stream, b->d_ep_steps, (const unsigned char*)mk, b->n);   // DM_F_EPISODE_STEPS
   HIPCHK(hipGetLastError());
   if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
   return DM_OK;
 }
 
 // the packed path covers this batch's configuration (reward modes alive / v3-config / v2-pose / imitation, the two-tier kernel family)
+// early termination is on: k_terminate follows every per-step launch; the horizon launch and the step queue carry no termination code
+static bool term_on(const dm_batch* b) { return b->fall_bodies != 0u || b->max_episode_steps > 0; }
 static bool packed_covers(const dm_batch* b) { return b->packed && b->B.reward_mode <= 4 && b->two_tier; }
 // a dm_batch_step call may be queued: device pointers, no fused policy step, no per-stage profiling, and a configuration for which ONE launch
 // per horizon is the faster form (rollout_as_one_launch)
@@ -437,9 +448,10 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // SIMD (8 192 envs on an MI355X; at 4 096 envs 17.3 M env-steps/s against 12.2 M for the one-env steps and 11.4 M for the packed ones).
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
-  // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches)
+  // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches;
+  //  so do those of a batch with early termination on)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && b->B.action_mode <= 2 && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && b->B.action_mode <= 2 && !term_on(b) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -569,6 +581,15 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   const bool reorder = b->reorder && b->has_rows && b->n > b->resident_waves;   // more envs than resident waves: later rounds exist, their tail matters
   const bool packed = packed_covers(b);      // this call runs on the packed kernels (profiled or not)
   const StepKernels K = step_kernels(b->B.action_mode >= 3, b->packed_ext);
+  // early termination: the plain step launches, then k_terminate on the same stream; a fused policy step would act on the observation of an episode
+  // k_terminate may still end, so the policy runs as a launch of its own behind it (below)
+  const bool term = term_on(b);
+  const dmp::PolicyArgs* fused = term ? nullptr : pol;
+  auto terminate = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count) {
+    if (!term) return;
+    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count};
+    hipLaunchKernelGGL(k_terminate, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn);
+  };
   if (packed) {
     const int mode = piped ? 1 : 0;
     if (mode != b->redo_mode) {      // (rare: the first packed step, or a host-pointer step between pipelined ones; every earlier launch is ordered before this stream here)
@@ -593,12 +614,13 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     }
     else if (pa) hipLaunchKernelGGL(K.act, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, *pa);
     else hipLaunchKernelGGL(K.narrow, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count);
+    terminate(st, Bp, lo, count);
   };
   unsigned ord_bound = 0;               // parts whose launch of this call took a ticket descriptor (committed below, after the launches went out)
   if (b->prof && packed) {
     HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
     launch_part(b->stream, b->B, 0, b->n, b->B.redo_count, nullptr);
-  } else if (b->prof) hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof);
+  } else if (b->prof) { hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof); terminate(b->stream, b->B, 0, b->n); }
   else if (piped) {
     // Sub-batch h's launch of THIS call depends on its own launch of the previous call (stream order on ps[h]) and on the
     // caller's inputs (ev_in), not on the other sub-batches: while the last, cheap workgroups of one sub-batch drain, the
@@ -612,7 +634,7 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       Batch<Real> Bh = b->B;                                                   // this part's launch orders itself from the tickets its previous launch left
       if (reorder) { const int rc2 = ord_bind(b, Bh, h, lo, b->ps[h]); if (rc2 != DM_OK) return rc2; ord_bound |= 1u << h; }
       if (b->timing && h == 0) HIPCHK(hipEventRecord(b->ev0, b->ps[0]));     // timing: sub-batch 0's kernel on ITS stream
-      launch_part(b->ps[h], Bh, lo, hi - lo, b->B.redo_count + 2 * h, pol);
+      launch_part(b->ps[h], Bh, lo, hi - lo, b->B.redo_count + 2 * h, fused);
       if (b->timing && h == 0) { HIPCHK(hipEventRecord(b->ev1, b->ps[0])); b->ev_pending = true; }
       HIPCHK(hipEventRecord(b->ev_done[h], b->ps[h]));
     }
@@ -626,12 +648,17 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     if (reorder && b->pipe <= 1) { const int rc2 = ord_bind(b, Bh, 0, 0, b->stream); if (rc2 != DM_OK) return rc2; ord_bound |= 1u; }
     // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of redo counters is clean — pair 0's
     //  two are cleared above once if a pipelined step used them before)
-    launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, pol);
-  } else hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub);
+    launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, fused);
+  } else { hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
   HIPCHK(hipGetLastError());
   for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
   if (packed) b->redo_phase ^= 1;
   if (b->timing && !piped) { HIPCHK(hipEventRecord(b->ev1, b->stream)); b->ev_pending = true; }
+  if (pol && term) {      // the policy's step on the observations the termination launch left: one launch over the whole batch, behind every part
+    if (pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
+    const int rc2 = dm_policy_act(pol->P, o, pol->action, pol->vpred, b->n, pol->stochastic, pol->seed, pol->counter, (void*)b->stream);
+    if (rc2 != DM_OK) return rc2;
+  }
   if (kind == DM_PTR_HOST) {
     HIPCHK(hipMemcpyAsync(b->h_out, b->d_obs, b->out_bytes, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -711,6 +738,8 @@ static int field_ptr(dm_batch* b, int field, void** p, size_t* count, bool* is_r
     case DM_F_CTRL: *p = b->B.ctrl; *count = n * NU; *is_real = true; break;
     case DM_F_EPISODE: *p = b->B.episode; *count = n; break;
     case DM_F_CYCLE: *p = b->B.cycle; *count = n; break;
+    case DM_F_EPISODE_STEPS: *p = b->d_ep_steps; *count = n; break;
+    case DM_F_DONE_REASON: *p = b->d_done_reason; *count = n; break;
     default: return fail(DM_EINVAL, "unknown field");
   }
   return DM_OK;

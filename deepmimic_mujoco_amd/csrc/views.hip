@@ -1,5 +1,6 @@
-// views.hip — read-only views of a batch's environments: images (dm_batch_render) and DeepMimic's state features (dm_batch_state_features),
-// DESIGN.md section 9.  Host side only: the kernels (render_kernel.h, state_kernel.h) are compiled in dmenv.hip's unit, which see.
+// views.hip — read-only views of a batch's environments: images (dm_batch_render), DeepMimic's state features (dm_batch_state_features) and the
+// floor-contact query (dm_batch_floor_contacts), DESIGN.md section 9.  Host side only: the kernels (render_kernel.h, state_kernel.h, term_kernel.h)
+// are compiled in dmenv.hip's unit, which see.
 #define DM_NO_LAUNCH_KERNELS
 #include <cmath>
 #include <cstring>
@@ -18,6 +19,8 @@ __global__ void k_render_rays(const dmr::ViewRec* __restrict__ rec, dmr::Params 
 __global__ void k_state_features(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const double* __restrict__ qpos_ext,
                                  const double* __restrict__ qvel_ext, const double* __restrict__ phase_ext, const int* __restrict__ env_ids,
                                  Ext* __restrict__ out);
+__global__ void k_floor_contacts(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos, const double* __restrict__ qpos_ext,
+                                 const int* __restrict__ env_ids, int* __restrict__ out);
 
 // env ids given by host or device pointer are checked on the host (device ids are read back first)
 static int check_env_ids(dm_batch* b, const int32_t* env_ids, int n, bool host, const char* who) {
@@ -143,6 +146,41 @@ extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const do
   HIPCHK(hipGetLastError());
   if (host) {
     HIPCHK(hipMemcpyAsync(out, o, (size_t)n * DM_NSTATE * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return DM_OK;
+}
+
+// ------------------------------------------------------------------ which geoms touch the floor (term_kernel.h)
+extern "C" int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, int32_t* out, int32_t kind) {
+  if (!b || !out) return fail(DM_EINVAL, "dm_batch_floor_contacts: null argument");
+  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_floor_contacts: bad ptr_kind");
+  if (n <= 0) return fail(DM_EINVAL, "dm_batch_floor_contacts: n must be positive");
+  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_floor_contacts: env_ids must be NULL when qpos is given");
+  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_floor_contacts: n exceeds the batch size");
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  const bool host = kind == DM_PTR_HOST;
+  int rc;
+  if ((rc = check_env_ids(b, env_ids, n, host, "dm_batch_floor_contacts"))) return rc;
+  const double* q = qpos;
+  const int32_t* ids = env_ids;
+  int32_t* o = out;
+  if (host) {      // staging: qpos | env ids | out
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
+    const size_t o_q = qpos ? take((size_t)n * NQ * sizeof(double)) : 0, o_id = env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
+    const size_t o_out = take((size_t)n * sizeof(int32_t));
+    if ((rc = grow_rbuf(b, off, "dm_batch_floor_contacts"))) return rc;
+    unsigned char* base = b->d_rbuf;
+    if (qpos) { HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q); }
+    if (env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
+    o = (int32_t*)(base + o_out);
+  }
+  hipLaunchKernelGGL(k_floor_contacts, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, q, (const int*)ids, (int*)o);
+  HIPCHK(hipGetLastError());
+  if (host) {
+    HIPCHK(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
   }
   return DM_OK;

@@ -32,6 +32,7 @@ from .mocap import MocapDM
 from .model import CompiledModel
 from .spaces import Box
 from .state_features import obs_width
+from .termination import fall_body_mask, geoms_of_bodies
 
 REWARD_MODES = {"alive": 0, "v3-config": 1, "v2-pose": 2, "imitation": 3, "v1-quat": 4}
 
@@ -128,8 +129,12 @@ class DPEnv(object):
     reward_range = (-float("inf"), float("inf"))
     spec = None
 
-    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None, action_mode="raw", obs_mode="dp_env_v3"):
-        """action_mode: one of ACTION_MODES ("raw" is the reference's behaviour; "spd-target" / "spd-mocap" make the action a PD target pose).
+    def __init__(self, motion=None, mocap_path=None, xml_path=None, device=0, reward="alive", batch_factory=None, action_mode="raw", obs_mode="dp_env_v3",
+                 fall_contact_bodies=None, max_episode_steps=0):
+        """fall_contact_bodies / max_episode_steps: DeepMimic's early termination (termination.py; include/dmenv.h DM_OPT_FALL_BODIES,
+        DM_OPT_MAX_EPISODE_STEPS): `step` also reports done when a body of the set touches the floor, or on the episode's M-th step.  Both are
+        switched on after the constructor's warm-up step.
+        action_mode: one of ACTION_MODES ("raw" is the reference's behaviour; "spd-target" / "spd-mocap" make the action a PD target pose).
         obs_mode: "dp_env_v3" (default: the reference's 56 numbers) or "deepmimic": `reset`, `step`, `_get_obs` and `reset_model*` return DeepMimic's
         171 state features (state_features.py) of the batch's state; their phase comes from the batch's cursor fields, which this class then writes from
         `idx_curr` / `idx_init` before every features call — for reward "alive" too, whose cursor never advances: its phase is the RSI draw."""
@@ -137,6 +142,8 @@ class DPEnv(object):
         obs_width(obs_mode)
         self.obs_mode = obs_mode
         self._action_mode = action_mode
+        self._fall_mask = fall_body_mask(fall_contact_bodies)
+        self._max_episode_steps = int(max_episode_steps)
         if action_mode not in ACTION_MODES:
             raise ValueError("action_mode must be one of %s" % sorted(ACTION_MODES))
         self._cm = _load_model(xml_path if xml_path is not None else Config.xml_path, explicit=xml_path is not None)
@@ -165,6 +172,7 @@ class DPEnv(object):
         assert not done
         self.action_space = _action_space(self._cm, action_mode)
         self.observation_space = Box(low=-np.inf, high=np.inf, shape=(observation.size,), dtype=np.float32)
+        self._set_termination()
         self.seed()
 
     # ---- plumbing ----------------------------------------------------------------------------------------
@@ -215,6 +223,13 @@ class DPEnv(object):
             self._batch.set_option(A.OPT_ACTION_MODE, ACTION_MODES[self._action_mode])
         if hasattr(self, "sim"):
             self.sim = _SimView(self); self.data = self.sim.data
+            self._set_termination()
+
+    def _set_termination(self):
+        if self._fall_mask:
+            self._batch.set_option(A.OPT_FALL_BODIES, self._fall_mask)
+        if self._max_episode_steps:
+            self._batch.set_option(A.OPT_MAX_EPISODE_STEPS, self._max_episode_steps)
 
     def _get_obs(self):
         if self.obs_mode == "deepmimic":
@@ -233,7 +248,11 @@ class DPEnv(object):
         self.idx_tmp_count = 0
 
     def early_termination(self):
-        pass
+        """the fall test of the current state: a body of `fall_contact_bodies` touches the floor (False without a set).  `is_done` stays the
+        reference's COM rule; `step` reports either."""
+        if not self._fall_mask:
+            return False
+        return bool(int(self._batch.floor_contacts()[0]) & geoms_of_bodies(self._fall_mask, self._cm.geom_bodyid))
 
     def get_joint_configs(self):
         return self.sim.data.qpos[7:]
@@ -361,8 +380,12 @@ class DPVecEnv(object):
 
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
-                 step_queue=0, obs_mode="dp_env_v3"):
-        """reward="imitation": the 5-term reward of code.md:1017-1143 (imitation.py) against the frame after the current one.
+                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0):
+        """fall_contact_bodies: DeepMimic's early termination by fall contact — a set name of termination.FALL_BODY_SETS ("deepmimic": every body but the two
+        ankles; "crawl": root, chest, neck), or body names / ids; None: off.  max_episode_steps: the episode's limit in env steps; 0: off.  While either is on,
+        one more launch follows every step launch, ends the episodes of the environments that fell or ran out of steps (done = 1, `done_reason()` says why) and,
+        with `autoreset`, starts their next episode as the step itself does on its own done; horizon launches and the step queue fall back to step launches.
+        reward="imitation": the 5-term reward of code.md:1017-1143 (imitation.py) against the frame after the current one.
         frame_skip: sim steps per env step (src/dp_env_v3.py:108-112 hard-codes 1); "mocap" = floor(mocap_dt / timestep), the
         commented intent of :107-110, so that one env step spans one mocap frame.  Default (None): 1, except "mocap" for the
         imitation reward — its reference advances one mocap frame per env step and its velocity features are per second, so any
@@ -431,11 +454,18 @@ class DPVecEnv(object):
         b.set_option(A.OPT_SEED, int(seed))
         b.set_option(A.OPT_ENV_OFFSET, int(env_offset))
         b.set_option(A.OPT_DIAGNOSTICS, 1 if diagnostics else 0)
+        self.fall_body_mask = fall_body_mask(fall_contact_bodies)
+        self.max_episode_steps = int(max_episode_steps)
+        if self.fall_body_mask:
+            b.set_option(A.OPT_FALL_BODIES, self.fall_body_mask)
+        if self.max_episode_steps:
+            b.set_option(A.OPT_MAX_EPISODE_STEPS, self.max_episode_steps)
         rowless = not (contacts or limits)          # no constraint rows: every wave costs the same, the packed kernel wins at any batch size
         auto = packed is None and batch_factory is None and (self.num_envs >= PACKED_FROM_ENVS or (rowless and self.num_envs >= 256)) and dtype == 64
         # a horizon launch (Batch.rollout, rollout.SegmentCollector) may use the packed kernel at ANY batch size: there a wave does not wait
         # for the slowest wave of every step
-        self.horizon_packed_ok = packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64
+        # (with early termination on there is no horizon launch: a horizon is step launches, for which the per-step choice above holds)
+        self.horizon_packed_ok = packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64 and not (self.fall_body_mask or self.max_episode_steps)
         if packed or auto:
             b.set_option(A.OPT_PACKED, 2 if (packed is not True and packed == 2) else 1)     # (packed=2: per-step launches with the three-set code, see the docstring)
         if auto:
@@ -462,6 +492,11 @@ class DPVecEnv(object):
 
     def seed(self, seed):
         self._batch.set_option(A.OPT_SEED, int(seed))
+
+    def done_reason(self, out=None):
+        """int32 [N]: why the last step ended each environment's episode — bits termination.DONE_STEP (COM band, clip end), DONE_FALL, DONE_TIME_LIMIT; 0
+        where it did not.  Maintained while `fall_contact_bodies` or `max_episode_steps` is on.  `out`: a numpy array or a device tensor."""
+        return self._batch.get(A.F_DONE_REASON, out)
 
     def reset(self, mode="rsi", out=None):
         self._batch.reset(mode={"rsi": 0, "init": 1, "qpos0": 2}[mode], hard=1)

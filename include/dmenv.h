@@ -156,7 +156,7 @@ enum {
                              use it at any size.  Results agree with the oracle to the same 1e-9 bar and do not depend
                              on which environments share a wave; they differ from the one-env kernel's in the last bits (other
                              summation orders). */
-  DM_OPT_STEP_QUEUE = 8   /* 0 (default): every dm_batch_step call launches.  Q = 1..DM_MAX_STEP_QUEUE: dm_batch_step calls with DEVICE
+  DM_OPT_STEP_QUEUE = 8,  /* 0 (default): every dm_batch_step call launches.  Q = 1..DM_MAX_STEP_QUEUE: dm_batch_step calls with DEVICE
                              pointers are QUEUED — nothing is launched — and run together, in call order, as one horizon launch
                              (k_rollout_packed: every wavefront steps its four environments through all queued steps at its own pace
                              instead of waiting for the slowest wave of every step) when Q calls are queued or when any other entry
@@ -170,7 +170,31 @@ enum {
                              0..3, action modes 0..2, constraint rows, at most two packed waves per SIMD); elsewhere — action modes 3 and
                              4 among it: nothing is queued, dm_batch_queue_stats stays 0 — calls launch at once as without it.
                              dm_batch_destroy() DROPS what is still queued (the buffers belong to the caller and may be gone). */
+  DM_OPT_FALL_BODIES = 9, /* DeepMimic's early termination by fall contact (--fall_contact_bodies).  A bit mask over model bodies, bit b for
+                             body b = 1..13; 0 (default): off.  An environment FALLS when a geom of a body in the mask touches the floor
+                             (dm_batch_floor_contacts has the rule) at the state the step left it in. */
+  DM_OPT_MAX_EPISODE_STEPS = 10 /* the episode time limit (--time_end_lim_max), in env steps.  0 (default): off.  M > 0: the episode ends on its
+                             M-th env step.
+                             While either of the two options is non-zero, every per-step launch of dm_batch_step is followed on the same
+                             stream (a pipelined part's: on that part's stream, over its env range) by one more launch, one wave per
+                             environment (k_terminate).  Where the step itself reported done (COM band, end of a "Loop: none" clip) it only
+                             records the reason and restarts DM_F_EPISODE_STEPS: the state may already be a fresh episode's, and a
+                             reference pose of a floor clip legitimately touches the floor.  Elsewhere it counts the step, tests the state
+                             the step left, and where a test fires sets done = 1 and DM_F_DONE_REASON, leaves the reward as it is, and with
+                             DM_OPT_AUTORESET resets the environment exactly as the step kernels do on their own done (RSI / noisy init,
+                             hard: time and warm start zeroed, the episode counter, the frame cursors and DM_F_CYCLE as there) and writes
+                             the fresh episode's observation row.  Host-pointer steps copy out after this launch.  The step kernels carry
+                             no termination code: with both options 0 nothing is launched and nothing changes.  Neither do the horizon
+                             launch and the step queue: while an option is on, dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches
+                             (as for action modes 3 and 4; dm_batch_queue_stats stays 0), and dm_batch_step_act and the policy rows of
+                             dm_batch_rollout run as the plain step launch, the termination launch, then the launch behind dm_policy_act
+                             on the returned observations (over the whole batch, after the parts of a pipelined step have joined): the
+                             result of dm_batch_step followed by dm_policy_act, bit for bit. */
 };
+/* bits of DM_F_DONE_REASON */
+#define DM_DONE_STEP 1       /* the step's own done: COM height outside (0.7, 2.0), or the end of a "Loop: none" clip */
+#define DM_DONE_FALL 2       /* DM_OPT_FALL_BODIES: a masked body touches the floor */
+#define DM_DONE_TIME_LIMIT 4 /* DM_OPT_MAX_EPISODE_STEPS */
 /* per-environment capacities of the DM_OPT_PACKED path (= csrc/slot_kernel.h SLOT_MAXROWS, SLOT_MAXLIMROWS, SLOT_MAXCON, SLOT_MAXFRAME, SLOT_MAXCAND) */
 #define DM_PACKED_MAXROWS 40
 #define DM_PACKED_MAXROWS_PER_STEP 32
@@ -228,7 +252,11 @@ enum {
   DM_F_SOLVER_ITER = 13,/* int32 [N] PGS sweeps of the last forward evaluation */
   DM_F_CTRL = 14,       /* double [N,28] last (unclamped) ctrl */
   DM_F_EPISODE = 15,    /* int32 [N] episode counter used by the reset RNG */
-  DM_F_CYCLE = 16       /* int32 [N] completed motion cycles since the episode started (reward mode 3) */
+  DM_F_CYCLE = 16,      /* int32 [N] completed motion cycles since the episode started (reward mode 3) */
+  DM_F_EPISODE_STEPS = 17, /* int32 [N] env steps since the episode began; maintained only while DM_OPT_FALL_BODIES or DM_OPT_MAX_EPISODE_STEPS
+                              is on; readable and writable; dm_batch_reset zeroes it for the masked envs */
+  DM_F_DONE_REASON = 18 /* int32 [N] why the LAST step ended the episode (maintained like DM_F_EPISODE_STEPS): DM_DONE_STEP, or
+                           DM_DONE_FALL | DM_DONE_TIME_LIMIT (both may be set); 0 where the env is not done */
 };
 int dm_batch_get(dm_batch* b, int32_t field, void* out, size_t bytes, int32_t ptr_kind);
 int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t bytes, int32_t ptr_kind);
@@ -297,6 +325,16 @@ int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int
  * without qpos, an env id out of range, a partial explicit state, env_ids with an explicit state, a bad ptr_kind. */
 int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
                             double* out, int32_t ptr_kind);
+
+/* Which geoms touch the floor at n humanoid states: bit g of out[i] (g = 1..15) is set exactly when the collision
+ * stage of a step would emit at least one contact for the pair (floor geom 0, geom g) at state i — with the floor's frame (point p0,
+ * normal n) and the pair margin max(margin_0, margin_g): a sphere (centre c, radius r) when n.(c - p0) <= margin + r; a capsule when that
+ * holds for either end's centre p +- axis * half; a box when some corner has ld = n.corner <= 0 and n.(p - p0) + ld <= margin.  The fall
+ * test of DM_OPT_FALL_BODIES is this mask against the geoms of the masked bodies.
+ * qpos == NULL: the batch's current states of env_ids[0..n) (env_ids NULL: envs 0..n-1, n <= the batch size).  qpos [n,35] non-NULL:
+ * explicit states; env_ids must then be NULL.  out [n] int32.  One launch on the batch's stream, one wave per state; argument checks,
+ * stream ordering, settle-first behaviour and ptr_kind as for dm_batch_state_features.  Read-only: changes no batch state. */
+int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, int32_t* out, int32_t ptr_kind);
 
 /* kernel timing of the last dm_batch_step launch, measured with HIP events on the batch's stream (ms) */
 int dm_batch_last_step_ms(dm_batch* b, float* ms);

@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --obs-mode, --action-mode and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk")
     if reward_help:
         ap.add_argument("--reward", default="alive", help=reward_help)
@@ -18,6 +18,11 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
                          "env; at 171 the learners run on their torch paths")
     ap.add_argument("--action-mode", default="raw", choices=["raw", "p-control", "pd", "spd-target", "spd-mocap"],
                     help="what the policy's action is: raw motor commands (default) | p-control, pd: plus a feedback term around the mocap frame | spd-target, spd-mocap: a PD target pose under a stable PD controller evaluated every substep")
+    ap.add_argument("--fall-contact", default="none", choices=["none", "deepmimic", "crawl"],
+                    help="DeepMimic's early termination: the episode ends when a body of the set touches the floor.  deepmimic = every body except the two ankles; "
+                         "crawl = root, chest, neck (the floor clips); none (default) = only the reference's centre-of-mass rule")
+    ap.add_argument("--max-episode-steps", type=int, default=0,
+                    help="the episode's time limit in env steps (0 = none).  A time-limit done is a done like any other: the learners do not bootstrap the value there")
     if autoreset_help:
         ap.add_argument("--autoreset", default="init", help=autoreset_help)
     if frame_skip_help:
@@ -28,7 +33,8 @@ def env_kwargs(args):
     """The DPVecEnv arguments that the env flags set."""
     fs = getattr(args, "frame_skip", None)
     return dict(motion=args.motion, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
-                frame_skip=fs if fs in (None, "mocap") else int(fs))
+                frame_skip=fs if fs in (None, "mocap") else int(fs),
+                fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps)
 
 
 def init_device(dist_backend):

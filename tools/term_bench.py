@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""Cost of early termination (DM_OPT_FALL_BODIES, csrc/term_kernel.h: one more launch per step) on one MI355X, written as
+profiles/term_kernels.md.  Modelled on tools/state_bench.py; two kinds of runs, the first without a profiler:
+
+  throughput    DPVecEnv.step env-steps/s (device tensors, one call's launches after the other's on one stream, a window closed by a device
+                synchronise) with termination off and with the "deepmimic" fall set, the two ALTERNATING in one process, `--reps` windows
+                each (median and spread), at each `--envs` size of `walk` with the 5-term imitation reward and RSI auto-reset; every shape is
+                warmed up first.  The off leg issues exactly the launches of a build without the feature.
+  kernel time   from `rocprofv3 --kernel-trace --stats` runs of their own (one per size), each running this file with `--trace N`: a few
+                hundred steps with termination on, nothing timed.  Their `*_kernel_stats.csv` files come back through `--stats N=file`; the
+                report then states k_terminate's time per launch and where a step's GPU time goes.
+
+`--resources-before file.md`: the table tools/kernel_resources.py printed for the library BEFORE the feature; the report lists the step
+kernels' rows of both and says whether any pre-existing kernel changed.  `--ab file`: the alternating parent / this-build lines of the
+default benchmark (tools/ab_bench.sh's form), quoted in the report.
+usage: python tools/term_bench.py [--envs 4096 8192] [--steps 200] [--warmup 30] [--reps 5] [--stats N=csv ...] [--resources-before file.md]
+                                  [--ab file] [--out profiles/term_kernels.md]
+       rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python tools/term_bench.py --trace 4096"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from state_bench import buffers, parse_before, read_stats, short  # noqa: E402
+
+
+def make_env(n, fall):
+    from deepmimic_mujoco_amd import DPVecEnv
+    return DPVecEnv(n, motion="walk", device=0, reward="imitation", autoreset="rsi", seed=1, fall_contact_bodies=fall)
+
+
+def trace_run(n, steps, warmup):
+    """the workload of a rocprofv3 run: closed-loop steps with the "deepmimic" fall set; nothing is timed here"""
+    import torch
+    dev = torch.device("cuda", 0)
+    env = make_env(n, "deepmimic")
+    g = torch.Generator(device=dev); g.manual_seed(5)
+    ac = torch.randn((n, 28), generator=g, dtype=torch.float64, device=dev) * 0.1
+    out = buffers(n, 56, dev)
+    env.reset("rsi")
+    for _ in range(warmup + steps):
+        env.step(ac, out=out)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out[0]).all())
+    print("trace run: %d envs, %d steps, packed=%s" % (n, warmup + steps, env.packed))
+    env.close()
+
+
+def measure(n, args):
+    import torch
+    from deepmimic_mujoco_amd import _abi as A
+    dev = torch.device("cuda", 0)
+    envs = {"off": make_env(n, None), "on": make_env(n, "deepmimic")}
+    out = buffers(n, 56, dev)
+    g = torch.Generator(device=dev); g.manual_seed(5)
+    ac = torch.randn((n, 28), generator=g, dtype=torch.float64, device=dev) * 0.1
+    rates = {m: [] for m in envs}
+    ended = {m: 0 for m in envs}
+    for rep in range(args.reps):
+        for m in ("off", "on") if rep % 2 == 0 else ("on", "off"):
+            env = envs[m]
+            env.reset("rsi")
+            for _ in range(args.warmup):
+                env.step(ac, out=out)
+            torch.cuda.synchronize()
+            ep0 = int(env.batch.get(A.F_EPISODE).sum())
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                env.step(ac, out=out)
+            torch.cuda.synchronize()
+            rates[m].append(n * args.steps / (time.perf_counter() - t0))
+            ended[m] += int(env.batch.get(A.F_EPISODE).sum()) - ep0
+    res = dict(envs=n, packed=bool(envs["on"].packed), frame_skip=envs["on"].frame_skip)
+    for m in envs:
+        res[m] = dict(median=float(np.median(rates[m])), min=float(min(rates[m])), max=float(max(rates[m])), episodes=ended[m])
+        envs[m].close()
+    res["ratio"] = res["on"]["median"] / res["off"]["median"]
+    return res
+
+
+def resources(before_path):
+    import kernel_resources as KR
+    rows = {r["name"]: r for r in KR.kernels(os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc", "libdmenv.so"))}
+    before = parse_before(open(before_path).read()) if before_path and os.path.exists(before_path) else None
+    return rows, before
+
+
+def report(results, stats, args, device):
+    L = ["# Early termination: cost of the termination launch (`tools/term_bench.py`)", "",
+         "Device: %s.  `walk`, the 5-term imitation reward, RSI auto-reset, frame_skip %s, float64 library, device tensors, `DPVecEnv.step` calls back to back on one stream"
+         % (device, results[0]["frame_skip"] if results else "?"),
+         "(a window ends in a device synchronise).  Termination off and `fall_contact_bodies=\"deepmimic\"` alternate in one process: %d windows of %d steps each after %d warm-up"
+         % (args.reps, args.steps, args.warmup),
+         "steps per window.  The off leg issues the launches of a build without the feature.", "",
+         "## Throughput", "", "| envs | step kernel when the run ended | off env-steps/s (median, min .. max) | on env-steps/s (median, min .. max) | on / off | episodes ended in the windows, off / on |",
+         "|---|---|---|---|---|---|"]
+    if not results:
+        L.append("| not measured | | | | | |")
+    for r in results:
+        a, d = r["off"], r["on"]
+        L.append("| %d | %s | %.3f M (%.3f .. %.3f) | %.3f M (%.3f .. %.3f) | %.4f | %d / %d |"
+                 % (r["envs"], "four envs per wave" if r["packed"] else "one env per wave", a["median"] / 1e6, a["min"] / 1e6, a["max"] / 1e6, d["median"] / 1e6, d["min"] / 1e6,
+                    d["max"] / 1e6, r["ratio"], a["episodes"], d["episodes"]))
+    L += ["", "With the fall set on, episodes may end earlier, and an environment early in its episode is a different workload from a late one: the ratio is the cost of the launch",
+          "plus that shift.  The kernel's own time is below.", "",
+          "## Kernel time (`rocprofv3 --kernel-trace --stats`, a run of its own per size: `--trace N`)", ""]
+    if not stats:
+        L.append("not measured")
+    for n, path in stats:
+        rows = read_stats(path)
+        tot = sum(r[3] for r in rows)
+        term = [r for r in rows if "k_terminate" in r[0]]
+        L += ["### %d envs" % n, ""]
+        if term:
+            L += ["`k_terminate`: %.2f us per launch (%d launches), %.2f %% of the run's GPU kernel time.  (For scale: the state-features launch, the same shape — kinematics plus a light"
+                  " epilogue — is 2.7-2.8 %% of a step, profiles/state_kernels.md.)" % (term[0][2] / 1e3, term[0][1], 100 * term[0][3] / tot), ""]
+        L += ["| kernel | launches | average us | share of GPU kernel time |", "|---|---|---|---|"]
+        for r in rows[:8]:
+            L.append("| %s | %d | %.2f | %.2f %% |" % (short(r[0]), r[1], r[2] / 1e3, 100 * r[3] / tot))
+        L.append("")
+    if args.ab and os.path.exists(args.ab):
+        L += ["## The default benchmark line, parent build against this one (alternating runs in one process chain, the form of `tools/ab_bench.sh`)", "", "```"]
+        L += [ln.rstrip() for ln in open(args.ab).read().splitlines() if ln.strip()]
+        L += ["```", ""]
+    rows, before = resources(args.resources_before)
+    L += ["## Resources (`tools/kernel_resources.py`: the code objects' own notes)", ""]
+    for k in ("k_terminate", "k_floor_contacts"):
+        if k in rows:
+            r = rows[k]
+            L.append("`%s`: %d VGPR, %d SGPR, %d B LDS, %d B scratch, %d spilled VGPR." % (k, r["vgpr"], r["sgpr"], r["lds"], r["scratch"], r["vspill"]))
+    L.append("")
+    if before is None:
+        L.append("No table of the library before the feature was given (`--resources-before`).")
+    else:
+        now = {k: (r["vgpr"], r["agpr"], r["sgpr"], r["vspill"], r["lds"], r["scratch"]) for k, r in rows.items()}
+        changed = sorted(k for k in before if k in now and now[k] != before[k])
+        gone = sorted(k for k in before if k not in now)
+        new = sorted(k for k in now if k not in before)
+        L += ["Against the table of the library before the feature: %d kernels then, %d now; new: %s; removed: %s; pre-existing kernels whose row changed: %s."
+              % (len(before), len(now), ", ".join("`%s`" % k for k in new) or "none", ", ".join(gone) or "none", ", ".join(changed) or "none"), "",
+              "| step kernel | before: VGPR / AGPR / SGPR / spilled VGPR / LDS B / scratch B | after |", "|---|---|---|"]
+        for k in sorted(before):
+            if "step" in k or "rollout" in k:
+                L.append("| %s | %s | %s |" % (k, " / ".join(str(x) for x in before[k]), " / ".join(str(x) for x in now.get(k, ()))))
+    return "\n".join(L) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, nargs="*", default=[4096, 8192])
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--stats", nargs="*", default=[])
+    ap.add_argument("--resources-before", default=None)
+    ap.add_argument("--ab", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "term_kernels.md"))
+    args = ap.parse_args()
+    if args.trace:
+        trace_run(args.trace, args.steps, args.warmup)
+        return
+    import torch
+    results = [measure(n, args) for n in args.envs]
+    stats = [(int(s.split("=")[0]), s.split("=", 1)[1]) for s in args.stats]
+    txt = report(results, stats, args, torch.cuda.get_device_name(0))
+    open(args.out, "w").write(txt)
+    print(json.dumps(dict(results=results, out=args.out)))
+
+
+if __name__ == "__main__":
+    main()
