@@ -14,6 +14,48 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+# numpy dtype -> the torch dtype's name (torch itself is imported only where a tensor is met or made)
+_TORCH_DTYPE = {np.float64: "float64", np.float32: "float32", np.int32: "int32", np.uint8: "uint8"}
+
+
+def _view_args(ptr, n_batch, device, state, env_ids, outs, who):
+    """The arrays of a read-only view call (Batch.render, state_features, floor_contacts).  ptr: Batch._ptr; state: the optional explicit
+    state as (value, dtype, shape after n) entries, all given or all None; env_ids [n] or None; outs: the requested outputs as (given or None,
+    dtype, shape after n).  n comes from the explicit state, else from env_ids, else it is the batch's.  One tensor among them makes the
+    call a device call: missing outputs are then allocated on cuda:<device> and numpy inputs moved there; otherwise everything is numpy.
+    -> (n, input pointers [state..., env_ids], output pointers, ptr_kind, keepalives, output objects); None inputs give None pointers."""
+    explicit = bool(state) and state[0][0] is not None
+    if explicit and env_ids is not None:
+        raise ValueError("%s: an explicit state and env_ids exclude each other" % who)
+    n = int(state[0][0].shape[0]) if explicit else (int(len(env_ids)) if env_ids is not None else n_batch)
+    ins = list(state) + [(env_ids, np.int32, ())]
+    on_device = False
+    for x, _dt, _shp in ins + outs:
+        if x is not None and _is_torch(x):
+            on_device = True
+            import torch
+            where = "cuda:%d" % device
+            break
+    in_ptrs, out_ptrs, objs, keep, kinds = [], [], [], [], set()
+    for x, dt, shp in ins:
+        if x is None:
+            in_ptrs.append(None)
+            continue
+        if on_device and not _is_torch(x):
+            x = torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=where)
+        p, kind, ka = ptr(x, dt, (n,) + shp)
+        in_ptrs.append(p); keep.append(ka); kinds.add(kind)
+    for x, dt, shp in outs:
+        shp = (n,) + shp
+        if x is None:
+            x = torch.empty(shp, dtype=getattr(torch, _TORCH_DTYPE[dt]), device=where) if on_device else np.empty(shp, dtype=dt)
+        p, kind, ka = ptr(x, dt, shp, out=True)
+        out_ptrs.append(p); keep.append(ka); objs.append(x); kinds.add(kind)
+    if len(kinds) != 1:
+        raise ValueError("%s buffers must be all numpy arrays or all device tensors" % who)
+    return n, in_ptrs, out_ptrs, kinds.pop(), keep, objs
+
+
 class Batch(object):
     def __init__(self, compiled_model, data_config, data_vel, n_envs, device=0, flags=0, mocap_dt=0.0, imitation=None, dtype=64):
         """dtype: arithmetic / device-state type of the kernels, 64 (default: the parity path) or 32 (the float32 build of the same
@@ -64,7 +106,7 @@ class Batch(object):
             return None, A.PTR_HOST, None
         if _is_torch(x):
             import torch
-            want = {np.float64: torch.float64, np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}[dtype]
+            want = getattr(torch, _TORCH_DTYPE[dtype])
             if x.dtype != want or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
                 raise ValueError("tensor must be contiguous %s of shape %s" % (want, shape))
             if x.device.type != "cuda" or (x.device.index or 0) != self.device:
@@ -288,48 +330,12 @@ class Batch(object):
         want = [k for k, on in (("rgb", rgb), ("depth", depth), ("segmentation", segmentation), ("geom_xform", geom_xform)) if on]
         if not want:
             raise ValueError("nothing to render")
-        if qpos is not None and env_ids is not None:
-            raise ValueError("qpos and env_ids exclude each other")
-        if qpos is not None:
-            n = int(qpos.shape[0])
-        elif env_ids is not None:
-            n = int(len(env_ids))
-        else:
-            n = self.n
         W, H = int(width), int(height)
-        spec = {"rgb": (np.uint8, (n, H, W, 3)), "depth": (np.float32, (n, H, W)), "segmentation": (np.int32, (n, H, W)),
-                "geom_xform": (np.float64, (n, A.NGEOM, 12))}
-        out = dict(out or {})
-        device = any(_is_torch(v) for v in list(out.values()) + [qpos, env_ids])
-        for k in want:
-            if k not in out:
-                if device:
-                    import torch
-                    out[k] = torch.empty(spec[k][1], dtype={np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32,
-                                                            np.float64: torch.float64}[spec[k][0]], device="cuda:%d" % self.device)
-                else:
-                    out[k] = np.empty(spec[k][1], dtype=spec[k][0])
-        if device:
-            import torch
-            if qpos is not None and not _is_torch(qpos):
-                qpos = torch.as_tensor(np.ascontiguousarray(qpos, dtype=np.float64), device="cuda:%d" % self.device)
-            if env_ids is not None and not _is_torch(env_ids):
-                env_ids = torch.as_tensor(np.ascontiguousarray(env_ids, dtype=np.int32), device="cuda:%d" % self.device)
-        ptrs, kinds, keep = {}, set(), []
-        for k in ("rgb", "depth", "segmentation", "geom_xform"):
-            if k in want:
-                p, kind, ka = self._ptr(out[k], spec[k][0], spec[k][1], out=True)
-                ptrs[k] = p; kinds.add(kind); keep.append(ka)
-            else:
-                ptrs[k] = None
-        qp, kq, ka = self._ptr(qpos, np.float64, (n, A.NQ)); keep.append(ka)
-        ip, ki, ka = self._ptr(env_ids, np.int32, (n,)); keep.append(ka)
-        if qpos is not None:
-            kinds.add(kq)
-        if env_ids is not None:
-            kinds.add(ki)
-        if len(kinds) != 1:
-            raise ValueError("render buffers must be all numpy arrays or all device tensors")
+        spec = {"rgb": (np.uint8, (H, W, 3)), "depth": (np.float32, (H, W)), "segmentation": (np.int32, (H, W)), "geom_xform": (np.float64, (A.NGEOM, 12))}
+        out = out or {}
+        n, (qp, ip), ps, kind, _keep, objs = _view_args(self._ptr, self.n, self.device, [(qpos, np.float64, (A.NQ,))], env_ids,
+                                                         [(out.get(k),) + spec[k] for k in want], "render")
+        ptrs = dict(zip(want, ps))
         key = (W, H, camera, id(visual)) if isinstance(camera, str) else None      # (model cameras: resolved once per size and visual table)
         cache = self.__dict__.setdefault("_render_descs", {})
         desc = cache[key][0] if key in cache else None
@@ -337,9 +343,9 @@ class Batch(object):
             desc = R.make_desc(self.compiled_model, W, H, camera, visual)
             if key is not None:
                 cache[key] = (desc, visual)          # (holding `visual` keeps its id from being reused)
-        A.check(self._L.dm_batch_render(self._h, qp, ip, n, C.byref(desc), ptrs["rgb"], ptrs["depth"], ptrs["segmentation"],
-                                        ptrs["geom_xform"], kinds.pop()), self._L)
-        return {k: out[k] for k in want}
+        A.check(self._L.dm_batch_render(self._h, qp, ip, n, C.byref(desc), ptrs.get("rgb"), ptrs.get("depth"), ptrs.get("segmentation"),
+                                        ptrs.get("geom_xform"), kind), self._L)
+        return dict(zip(want, objs))
 
     def state_features(self, out=None, env_ids=None, qpos=None, qvel=None, phase=None):
         """DeepMimic's state features through dm_batch_state_features (one launch; state_features.py has the layout): [n, 171]
@@ -351,28 +357,9 @@ class Batch(object):
         explicit = [x is not None for x in (qpos, qvel, phase)]
         if any(explicit) and not all(explicit):
             raise ValueError("an explicit state needs qpos, qvel and phase")
-        if explicit[0] and env_ids is not None:
-            raise ValueError("an explicit state and env_ids exclude each other")
-        n = int(qpos.shape[0]) if explicit[0] else (int(len(env_ids)) if env_ids is not None else self.n)
-        ins = [qpos, qvel, phase, env_ids]
-        device = any(_is_torch(x) for x in ins + [out])
-        if out is None:
-            if device:
-                import torch
-                out = torch.empty((n, A.NSTATE), dtype=torch.float64, device="cuda:%d" % self.device)
-            else:
-                out = np.empty((n, A.NSTATE))
-        if device:
-            import torch
-            for i, dt in enumerate((np.float64, np.float64, np.float64, np.int32)):
-                if ins[i] is not None and not _is_torch(ins[i]):
-                    ins[i] = torch.as_tensor(np.ascontiguousarray(ins[i], dtype=dt), device="cuda:%d" % self.device)
-        op, kind, _ko = self._ptr(out, np.float64, (n, A.NSTATE), out=True)
-        qp, k1, _k1 = self._ptr(ins[0], np.float64, (n, A.NQ)); vp, k2, _k2 = self._ptr(ins[1], np.float64, (n, A.NV))
-        pp, k3, _k3 = self._ptr(ins[2], np.float64, (n,)); ip, k4, _k4 = self._ptr(ins[3], np.int32, (n,))
-        kinds = {kind} | ({k1, k2, k3} if explicit[0] else set()) | ({k4} if env_ids is not None else set())
-        if len(kinds) != 1:
-            raise ValueError("state_features buffers must be all numpy arrays or all device tensors")
+        f64 = np.float64
+        n, (qp, vp, pp, ip), (op,), kind, _keep, (out,) = _view_args(self._ptr, self.n, self.device, [(qpos, f64, (A.NQ,)), (qvel, f64, (A.NV,)), (phase, f64, ())],
+                                                                     env_ids, [(out, f64, (A.NSTATE,))], "state_features")
         A.check(self._L.dm_batch_state_features(self._h, qp, vp, pp, ip, n, op, kind), self._L)
         return out
 
@@ -380,27 +367,8 @@ class Batch(object):
         """Which geoms touch the floor, through dm_batch_floor_contacts (one launch): int32 [n], bit g (1..15) set when the collision stage of a
         step would emit a contact for (floor, geom g) at the state.  Default: the batch's current state of every environment, or of `env_ids`
         [n]; with qpos [n,35] (env_ids must then be None): those states.  Arrays as for `state_features`.  Reads the batch, changes nothing."""
-        if qpos is not None and env_ids is not None:
-            raise ValueError("qpos and env_ids exclude each other")
-        n = int(qpos.shape[0]) if qpos is not None else (int(len(env_ids)) if env_ids is not None else self.n)
-        device = any(_is_torch(x) for x in (qpos, env_ids, out))
-        if out is None:
-            if device:
-                import torch
-                out = torch.empty(n, dtype=torch.int32, device="cuda:%d" % self.device)
-            else:
-                out = np.empty(n, dtype=np.int32)
-        if device:
-            import torch
-            if qpos is not None and not _is_torch(qpos):
-                qpos = torch.as_tensor(np.ascontiguousarray(qpos, dtype=np.float64), device="cuda:%d" % self.device)
-            if env_ids is not None and not _is_torch(env_ids):
-                env_ids = torch.as_tensor(np.ascontiguousarray(env_ids, dtype=np.int32), device="cuda:%d" % self.device)
-        op, kind, _ko = self._ptr(out, np.int32, (n,), out=True)
-        qp, k1, _k1 = self._ptr(qpos, np.float64, (n, A.NQ)); ip, k2, _k2 = self._ptr(env_ids, np.int32, (n,))
-        kinds = {kind} | ({k1} if qpos is not None else set()) | ({k2} if env_ids is not None else set())
-        if len(kinds) != 1:
-            raise ValueError("floor_contacts buffers must be all numpy arrays or all device tensors")
+        n, (qp, ip), (op,), kind, _keep, (out,) = _view_args(self._ptr, self.n, self.device, [(qpos, np.float64, (A.NQ,))], env_ids, [(out, np.int32, ())],
+                                                             "floor_contacts")
         A.check(self._L.dm_batch_floor_contacts(self._h, qp, ip, n, op, kind), self._L)
         return out
 

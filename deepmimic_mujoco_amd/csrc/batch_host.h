@@ -37,7 +37,7 @@ struct dm_batch {
   bool timing = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; float last_ms = 0.f; bool ev_pending = false;
   // pipelined sub-batches (DM_OPT_PIPELINE): the env range is cut into `pipe` contiguous parts, each stepped on its own stream
   int pipe = 1; hipStream_t ps[DM_MAX_PIPELINE] = {}; hipEvent_t ev_in = nullptr, ev_done[DM_MAX_PIPELINE] = {}; bool pipe_pending = false;
-  // dm_batch_render: view records and the staging of host arrays, grown on demand (dm_batch_state_features stages host arrays in it too)
+  // the views' staging block (views.hip Stage): a host caller's arrays and render's view records, laid out per call, grown on demand, freed with the batch
   unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
   // early termination (DM_OPT_FALL_BODIES, DM_OPT_MAX_EPISODE_STEPS; term_kernel.h): k_terminate follows every per-step launch while either is non-zero
   unsigned fall_bodies = 0; int max_episode_steps = 0; int *d_ep_steps = nullptr, *d_done_reason = nullptr;   // [N] DM_F_EPISODE_STEPS, DM_F_DONE_REASON

@@ -2,7 +2,7 @@
 // kernels that one unit defines and dmenv.hip launches.  The library's seven units (csrc/build.py UNITS):
 //   dmenv.hip           one-env step kernels of action modes 0..2, reset / state / ordering / render / state-feature / termination kernels, the batch half of the C ABI
 //                       (host side: models, mocap, batches, options, state, step / rollout / queue, profiling and timing)
-//   views.hip           dm_batch_render, dm_batch_state_features and dm_batch_floor_contacts (host side; their kernels are compiled in dmenv.hip's unit)
+//   views.hip           dm_batch_render, dm_batch_state_features and dm_batch_floor_contacts (host side: one prologue, one staging helper over view_stage.h; kernels in dmenv.hip's unit)
 //   learner.hip         the learner half of the C ABI with its kernels (policy_kernel.h, vf_kernel.h, pg_kernel.h, disc_kernel.h); does not include this file
 //   kernels_rollout.hip the horizon launch (k_rollout_packed + the step bodies it calls): the packed options and the load-store vectoriser off
 //   kernels_spd.hip / kernels_packed_spd.hip   the one-env and the packed step kernels of action modes 3 and 4 (stable PD control per substep), units

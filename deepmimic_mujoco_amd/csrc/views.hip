@@ -1,6 +1,7 @@
 // views.hip — read-only views of a batch's environments: images (dm_batch_render), DeepMimic's state features (dm_batch_state_features) and the
 // floor-contact query (dm_batch_floor_contacts), DESIGN.md section 9.  Host side only: the kernels (render_kernel.h, state_kernel.h, term_kernel.h)
-// are compiled in dmenv.hip's unit, which see.
+// are compiled in dmenv.hip's unit, which see.  Every view is: view_args, its own argument rules, view_enter, the arrays it declares on a Stage,
+// commit(), its launches on ptr(index), finish().
 #define DM_NO_LAUNCH_KERNELS
 #include <cmath>
 #include <cstring>
@@ -9,6 +10,7 @@
 
 #include "batch_host.h"
 #include "render.h"
+#include "view_stage.h"
 
 using namespace dm;
 
@@ -22,8 +24,21 @@ __global__ void k_state_features(const DevModel<Real>* __restrict__ Mp, Batch<Re
 __global__ void k_floor_contacts(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos, const double* __restrict__ qpos_ext,
                                  const int* __restrict__ env_ids, int* __restrict__ out);
 
-// env ids given by host or device pointer are checked on the host (device ids are read back first)
-static int check_env_ids(dm_batch* b, const int32_t* env_ids, int n, bool host, const char* who) {
+// the argument checks every view starts with, in this order; nothing here touches a device.  required: the pointers the view cannot do without;
+// explicit_state: the caller gave states of their own (`state_word` names them in the message) instead of the batch's
+static int view_args(dm_batch* b, bool required, int kind, int n, bool explicit_state, const char* state_word, const int32_t* env_ids, const char* who) {
+  if (!b || !required) return fail(DM_EINVAL, std::string(who) + ": null argument");
+  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, std::string(who) + ": bad ptr_kind");
+  if (n <= 0) return fail(DM_EINVAL, std::string(who) + ": n must be positive");
+  if (explicit_state && env_ids) return fail(DM_EINVAL, std::string(who) + ": env_ids must be NULL when " + state_word + " is given");
+  if (!explicit_state && n > b->n) return fail(DM_EINVAL, std::string(who) + ": n exceeds the batch size");
+  return DM_OK;
+}
+// the first touch of the device: run what the batch has queued, then range-check the env ids on the host — before anything is allocated for the call.
+// Ids given by device pointer are read back first: the one host wait of a device caller
+static int view_enter(dm_batch* b, const int32_t* env_ids, int n, bool host, const char* who) {
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
   if (!env_ids) return DM_OK;
   std::vector<int32_t> ids((size_t)n);
   if (host) std::memcpy(ids.data(), env_ids, (size_t)n * sizeof(int32_t));
@@ -40,15 +55,37 @@ static int grow_rbuf(dm_batch* b, size_t bytes, const char* who) {
   b->rbuf_bytes = bytes;
   return DM_OK;
 }
+// One call's arrays (view_stage.h has the layout).  A host caller's arrays are staged in d_rbuf: inputs copied in by commit(), outputs copied back by
+// finish(), which then waits for the stream.  A device caller's arrays are used where they are and nothing waits; only scratch takes room in d_rbuf.
+// in / out / scratch return the array's index; ptr(index) is what the kernel gets, valid once commit() has returned (the buffer may move when it grows)
+struct Stage : dmst::Layout {
+  dm_batch* b; const char* who;
+  Stage(dm_batch* b_, int kind, const char* who_) : dmst::Layout(kind == DM_PTR_HOST), b(b_), who(who_) {}
+  int in(const void* user, size_t bytes) { return add(dmst::COPY_IN, user, bytes); }
+  int out(void* user, size_t bytes) { return add(dmst::COPY_OUT, user, bytes); }
+  int scratch(size_t bytes) { return add(dmst::SCRATCH, nullptr, bytes); }
+  template <class T> T* ptr(int i) const { return (T*)at(i, b->d_rbuf); }
+  int commit() {
+    if (full) return fail(DM_EINVAL, std::string(who) + ": more arrays than the staging table holds");
+    const int rc = grow_rbuf(b, total, who);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) if (r[i].staged && r[i].dir == dmst::COPY_IN) HIPCHK(hipMemcpyAsync(b->d_rbuf + r[i].off, r[i].user, r[i].bytes, hipMemcpyHostToDevice, b->stream));
+    return DM_OK;
+  }
+  int finish() {
+    if (!host) return DM_OK;
+    for (int i = 0; i < n; i++) if (r[i].staged && r[i].dir == dmst::COPY_OUT) HIPCHK(hipMemcpyAsync(r[i].user, b->d_rbuf + r[i].off, r[i].bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return DM_OK;
+  }
+};
 
 // ------------------------------------------------------------------ rendering (render_kernel.h)
 extern "C" int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, const dm_render_desc* d, uint8_t* rgb,
                                float* depth, int32_t* seg, double* geom_xform, int32_t kind) {
-  if (!b || !d) return fail(DM_EINVAL, "dm_batch_render: null argument");
-  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_render: bad ptr_kind");
-  if (n <= 0) return fail(DM_EINVAL, "dm_batch_render: n must be positive");
-  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_render: env_ids must be NULL when qpos is given");
-  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_render: n exceeds the batch size");
+  const char* who = "dm_batch_render";
+  int rc;
+  if ((rc = view_args(b, d != nullptr, kind, n, qpos != nullptr, "qpos", env_ids, who))) return rc;
   const int W = d->width, H = d->height;
   if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(DM_EINVAL, "dm_batch_render: width and height must be 1..4096");
   const size_t npix = (size_t)n * W * H;
@@ -58,130 +95,62 @@ extern "C" int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* e
   const double ln = std::sqrt(d->light_dir[0] * d->light_dir[0] + d->light_dir[1] * d->light_dir[1] + d->light_dir[2] * d->light_dir[2]);
   if (!(ln > 0)) return fail(DM_EINVAL, "dm_batch_render: light_dir must be nonzero");
   if (!(d->floor_square > 0)) return fail(DM_EINVAL, "dm_batch_render: floor_square must be positive");
-  HIPCHK(hipSetDevice(b->device));
-  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  const bool host = kind == DM_PTR_HOST;
-  // scratch: records | qpos | env ids | (host outputs) rgb | depth | seg | xform
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up256(bytes); return o; };
-  const size_t o_rec = take((size_t)n * sizeof(dmr::ViewRec));
-  const size_t o_q = host && qpos ? take((size_t)n * NQ * sizeof(double)) : 0;
-  const size_t o_id = host && env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
-  const size_t o_rgb = host && rgb ? take(npix * 3) : 0;
-  const size_t o_dep = host && depth ? take(npix * sizeof(float)) : 0;
-  const size_t o_seg = host && seg ? take(npix * sizeof(int32_t)) : 0;
-  const size_t o_xf = host && geom_xform ? take((size_t)n * NG * 12 * sizeof(double)) : 0;
-  int rc;
-  if ((rc = grow_rbuf(b, off, "dm_batch_render"))) return rc;
-  unsigned char* base = b->d_rbuf;
-  if ((rc = check_env_ids(b, env_ids, n, host, "dm_batch_render"))) return rc;
-  const double* q = qpos;
-  const int32_t* ids = env_ids;
-  if (host && qpos) { HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q); }
-  if (host && env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
-  unsigned char* drgb = host && rgb ? base + o_rgb : rgb;
-  float* ddep = host && depth ? (float*)(base + o_dep) : depth;
-  int32_t* dseg = host && seg ? (int32_t*)(base + o_seg) : seg;
-  double* dxf = host && geom_xform ? (double*)(base + o_xf) : geom_xform;
-  dmr::ViewRec* rec = (dmr::ViewRec*)(base + o_rec);
+  if ((rc = view_enter(b, env_ids, n, kind == DM_PTR_HOST, who))) return rc;
+  Stage st(b, kind, who);
+  const int i_rec = st.scratch((size_t)n * sizeof(dmr::ViewRec)), i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_id = st.in(env_ids, (size_t)n * sizeof(int32_t));
+  const int i_rgb = st.out(rgb, npix * 3), i_dep = st.out(depth, npix * sizeof(float)), i_seg = st.out(seg, npix * sizeof(int32_t));
+  const int i_xf = st.out(geom_xform, (size_t)n * NG * 12 * sizeof(double));
+  if ((rc = st.commit())) return rc;
+  dmr::ViewRec* rec = st.ptr<dmr::ViewRec>(i_rec);
+  unsigned char* drgb = st.ptr<unsigned char>(i_rgb); float* ddep = st.ptr<float>(i_dep); int* dseg = st.ptr<int>(i_seg);
   dmr::Camera cam{};
   for (int k = 0; k < 3; k++) cam.pos[k] = d->cam_pos[k];
   for (int k = 0; k < 9; k++) cam.mat[k] = d->cam_mat[k];
   cam.track_com = d->track_com != 0;
-  hipLaunchKernelGGL(k_render_pose, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, q, (const int*)ids, cam, rec, dxf);
+  hipLaunchKernelGGL(k_render_pose, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, st.ptr<const double>(i_q), st.ptr<const int>(i_id), cam, rec,
+                     st.ptr<double>(i_xf));
   HIPCHK(hipGetLastError());
   if (drgb || ddep || dseg) {
     const dmr::Params P = dmr::make_params(*d);
     const int tiles_x = (W + 15) / 16, tiles = tiles_x * ((H + 15) / 16);
     for (int v0 = 0; v0 < n; v0 += 65535) {
       const int nv = n - v0 < 65535 ? n - v0 : 65535;
-      hipLaunchKernelGGL(k_render_rays, dim3(tiles, nv), dim3(256), 0, b->stream, (const dmr::ViewRec*)rec, P, tiles_x, v0, drgb, ddep, (int*)dseg);
+      hipLaunchKernelGGL(k_render_rays, dim3(tiles, nv), dim3(256), 0, b->stream, (const dmr::ViewRec*)rec, P, tiles_x, v0, drgb, ddep, dseg);
       HIPCHK(hipGetLastError());
     }
   }
-  if (host) {
-    if (rgb) HIPCHK(hipMemcpyAsync(rgb, drgb, npix * 3, hipMemcpyDeviceToHost, b->stream));
-    if (depth) HIPCHK(hipMemcpyAsync(depth, ddep, npix * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    if (seg) HIPCHK(hipMemcpyAsync(seg, dseg, npix * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    if (geom_xform) HIPCHK(hipMemcpyAsync(geom_xform, dxf, (size_t)n * NG * 12 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return DM_OK;
+  return st.finish();
 }
 
 // ------------------------------------------------------------------ DeepMimic's state features (state_kernel.h)
 extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
                                        double* out, int32_t kind) {
-  if (!b || !out) return fail(DM_EINVAL, "dm_batch_state_features: null argument");
-  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_state_features: bad ptr_kind");
-  if (n <= 0) return fail(DM_EINVAL, "dm_batch_state_features: n must be positive");
-  if ((qpos || qvel || phase) && !(qpos && qvel && phase)) return fail(DM_EINVAL, "dm_batch_state_features: an explicit state needs qpos, qvel and phase");
-  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_state_features: env_ids must be NULL when a state is given");
-  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_state_features: n exceeds the batch size");
-  HIPCHK(hipSetDevice(b->device));
-  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  const bool host = kind == DM_PTR_HOST;
+  const char* who = "dm_batch_state_features";
   int rc;
-  if ((rc = check_env_ids(b, env_ids, n, host, "dm_batch_state_features"))) return rc;
-  const double *q = qpos, *qv = qvel, *ph = phase;
-  const int32_t* ids = env_ids;
-  double* o = out;
-  if (host) {      // staging: qpos | qvel | phase | env ids | out
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    const size_t o_q = qpos ? take((size_t)n * NQ * sizeof(double)) : 0, o_v = qpos ? take((size_t)n * NV * sizeof(double)) : 0;
-    const size_t o_p = qpos ? take((size_t)n * sizeof(double)) : 0, o_id = env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
-    const size_t o_out = take((size_t)n * DM_NSTATE * sizeof(double));
-    if ((rc = grow_rbuf(b, off, "dm_batch_state_features"))) return rc;
-    unsigned char* base = b->d_rbuf;
-    if (qpos) {
-      HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q);
-      HIPCHK(hipMemcpyAsync(base + o_v, qvel, (size_t)n * NV * sizeof(double), hipMemcpyHostToDevice, b->stream)); qv = (const double*)(base + o_v);
-      HIPCHK(hipMemcpyAsync(base + o_p, phase, (size_t)n * sizeof(double), hipMemcpyHostToDevice, b->stream)); ph = (const double*)(base + o_p);
-    }
-    if (env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
-    o = (double*)(base + o_out);
-  }
-  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, q, qv, ph, (const int*)ids, (Ext*)o);
+  if ((rc = view_args(b, out != nullptr, kind, n, qpos || qvel || phase, "a state", env_ids, who))) return rc;
+  if ((qpos || qvel || phase) && !(qpos && qvel && phase)) return fail(DM_EINVAL, "dm_batch_state_features: an explicit state needs qpos, qvel and phase");
+  if ((rc = view_enter(b, env_ids, n, kind == DM_PTR_HOST, who))) return rc;
+  Stage st(b, kind, who);
+  const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_p = st.in(phase, (size_t)n * sizeof(double));
+  const int i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NSTATE * sizeof(double));
+  if ((rc = st.commit())) return rc;
+  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                     st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());
-  if (host) {
-    HIPCHK(hipMemcpyAsync(out, o, (size_t)n * DM_NSTATE * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return DM_OK;
+  return st.finish();
 }
 
 // ------------------------------------------------------------------ which geoms touch the floor (term_kernel.h)
 extern "C" int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, int32_t* out, int32_t kind) {
-  if (!b || !out) return fail(DM_EINVAL, "dm_batch_floor_contacts: null argument");
-  if (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE) return fail(DM_EINVAL, "dm_batch_floor_contacts: bad ptr_kind");
-  if (n <= 0) return fail(DM_EINVAL, "dm_batch_floor_contacts: n must be positive");
-  if (qpos && env_ids) return fail(DM_EINVAL, "dm_batch_floor_contacts: env_ids must be NULL when qpos is given");
-  if (!qpos && n > b->n) return fail(DM_EINVAL, "dm_batch_floor_contacts: n exceeds the batch size");
-  HIPCHK(hipSetDevice(b->device));
-  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  const bool host = kind == DM_PTR_HOST;
+  const char* who = "dm_batch_floor_contacts";
   int rc;
-  if ((rc = check_env_ids(b, env_ids, n, host, "dm_batch_floor_contacts"))) return rc;
-  const double* q = qpos;
-  const int32_t* ids = env_ids;
-  int32_t* o = out;
-  if (host) {      // staging: qpos | env ids | out
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    const size_t o_q = qpos ? take((size_t)n * NQ * sizeof(double)) : 0, o_id = env_ids ? take((size_t)n * sizeof(int32_t)) : 0;
-    const size_t o_out = take((size_t)n * sizeof(int32_t));
-    if ((rc = grow_rbuf(b, off, "dm_batch_floor_contacts"))) return rc;
-    unsigned char* base = b->d_rbuf;
-    if (qpos) { HIPCHK(hipMemcpyAsync(base + o_q, qpos, (size_t)n * NQ * sizeof(double), hipMemcpyHostToDevice, b->stream)); q = (const double*)(base + o_q); }
-    if (env_ids) { HIPCHK(hipMemcpyAsync(base + o_id, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream)); ids = (const int32_t*)(base + o_id); }
-    o = (int32_t*)(base + o_out);
-  }
-  hipLaunchKernelGGL(k_floor_contacts, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, q, (const int*)ids, (int*)o);
+  if ((rc = view_args(b, out != nullptr, kind, n, qpos != nullptr, "qpos", env_ids, who))) return rc;
+  if ((rc = view_enter(b, env_ids, n, kind == DM_PTR_HOST, who))) return rc;
+  Stage st(b, kind, who);
+  const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * sizeof(int32_t));
+  if ((rc = st.commit())) return rc;
+  hipLaunchKernelGGL(k_floor_contacts, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, st.ptr<const double>(i_q),
+                     st.ptr<const int>(i_id), st.ptr<int>(i_o));
   HIPCHK(hipGetLastError());
-  if (host) {
-    HIPCHK(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return DM_OK;
+  return st.finish();
 }
