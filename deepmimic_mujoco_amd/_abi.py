@@ -20,6 +20,8 @@ OPT_STEP_QUEUE = 8
 # the episode, and the episode's limit in env steps; 0 = off.  DONE_*: the bits of F_DONE_REASON.
 OPT_FALL_BODIES, OPT_MAX_EPISODE_STEPS = 9, 10
 DONE_STEP, DONE_FALL, DONE_TIME_LIMIT = 1, 2, 4
+# the truncation log's capacity in records (0 = off): the states the time limit alone cut off, kept for the value bootstrap (dm_batch_truncations)
+OPT_TRUNCATION_LOG = 11
 # DM_OPT_ACTION_MODE values (include/dmenv.h): 3 and 4 make the action a PD target pose under a stable PD controller evaluated per substep
 ACTION_RAW, ACTION_P_CONTROL, ACTION_PD, ACTION_SPD_TARGET, ACTION_SPD_MOCAP = 0, 1, 2, 3, 4
 MAX_PIPELINE = 8
@@ -114,7 +116,7 @@ LIB_PATH = os.environ.get("DMENV_LIB") or os.path.join(_HERE, "csrc", "libdmenv.
 EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_destroy", "dm_batch_create",
            "dm_batch_destroy", "dm_batch_set_stream", "dm_batch_set_option", "dm_batch_set_state", "dm_batch_reset",
            "dm_batch_step", "dm_batch_get_obs", "dm_batch_get", "dm_batch_set", "dm_batch_debug_forward",
-           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_last_error", "dm_abi_version", "dm_real_bits",
+           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_truncations", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
            "dm_device_count"]
 _LIB = None
 
@@ -188,6 +190,8 @@ def load(dtype=64):
     L.dm_batch_render.argtypes = [vp, vp, vp, i32, C.POINTER(RenderDesc), vp, vp, vp, vp, i32]
     L.dm_batch_state_features.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32]
     L.dm_batch_floor_contacts.argtypes = [vp, vp, vp, i32, vp, i32]
+    L.dm_batch_truncations.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32]
+    L.dm_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]
     L.dm_episode_scan.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]
     if L.dm_abi_version() != ABI_VERSION:
         raise DmenvError("libdmenv.so ABI version %d != %d" % (L.dm_abi_version(), ABI_VERSION))

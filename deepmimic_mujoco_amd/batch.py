@@ -372,6 +372,41 @@ class Batch(object):
         A.check(self._L.dm_batch_floor_contacts(self._h, qp, ip, n, op, kind), self._L)
         return out
 
+    def truncations(self, clear=True, out=None, device=None):
+        """The truncation log (set_option(OPT_TRUNCATION_LOG, C), C > 0; include/dmenv.h) through dm_batch_truncations: the states of the episodes
+        the time limit ALONE ended since the log was last cleared, kept because auto-reset overwrites them — what a learner bootstraps the value
+        from.  -> (count, index [C,4] int32 rows {env, tick, frame_idx, frame_init}, qpos [C,35], qvel [C,34] float64); the first min(count, C) records
+        are valid, in arrival order (key on (tick, env)), and count > C says the log overflowed.  clear: the count and the tick (step calls since
+        the last clear) then start again.  out: the four buffers, each of index / qpos / qvel optional (None: not copied), all numpy arrays (host:
+        count is an int32 [1] array, the call waits once) or all tensors on the batch's device (count an int32 [1] tensor; stream-ordered, nothing
+        waits).  Without `out`: device tensors when the batch has been stepped with device tensors (or device=True), else numpy arrays."""
+        C_ = int(self.__dict__.get("options", {}).get(A.OPT_TRUNCATION_LOG, 0))
+        if out is None:
+            if device is None:
+                device = getattr(self, "_stream_handle", None) is not None
+            if device:
+                import torch
+                where = "cuda:%d" % self.device
+                out = (torch.zeros(1, dtype=torch.int32, device=where), torch.zeros((C_, 4), dtype=torch.int32, device=where),
+                       torch.zeros((C_, A.NQ), dtype=torch.float64, device=where), torch.zeros((C_, A.NV), dtype=torch.float64, device=where))
+            else:
+                out = (np.zeros(1, dtype=np.int32), np.zeros((C_, 4), dtype=np.int32), np.zeros((C_, A.NQ)), np.zeros((C_, A.NV)))
+        count, index, qpos, qvel = out
+        if count is None:
+            raise ValueError("truncations: the count buffer is required")
+        rows = [int(x.shape[0]) for x in (index, qpos, qvel) if x is not None]
+        if len(set(rows)) > 1:
+            raise ValueError("truncations: index, qpos and qvel must hold the same number of records")
+        cap = rows[0] if rows else 0
+        cp, k0, _a = self._ptr(count, np.int32, (1,), out=True)
+        ip, k1, _b = self._ptr(index, np.int32, (cap, 4), out=True)
+        qp, k2, _c = self._ptr(qpos, np.float64, (cap, A.NQ), out=True)
+        vp, k3, _d = self._ptr(qvel, np.float64, (cap, A.NV), out=True)
+        if len({k0} | {k for k, x in ((k1, index), (k2, qpos), (k3, qvel)) if x is not None}) != 1:
+            raise ValueError("truncations buffers must be all numpy arrays or all device tensors")
+        A.check(self._L.dm_batch_truncations(self._h, cp, ip, qp, vp, cap, 1 if clear else 0, k0), self._L)
+        return count, index, qpos, qvel
+
     def set_state(self, qpos, qvel, frame_idx=None, mask=None):
         n = self.n
         qp, k, _a = self._ptr(qpos, np.float64, (n, A.NQ)); vp, k2, _b = self._ptr(qvel, np.float64, (n, A.NV))

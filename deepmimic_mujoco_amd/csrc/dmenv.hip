@@ -262,7 +262,7 @@ extern "C" void dm_batch_destroy(dm_batch* b) {
   if (b->ev_in) hipEventDestroy(b->ev_in);
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
@@ -369,6 +369,32 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
     case DM_OPT_MAX_EPISODE_STEPS:
       if (v < 0 || v > 0x7fffffff) return fail(DM_EINVAL, "DM_OPT_MAX_EPISODE_STEPS must be 0 (off) or a positive step count");
       b->max_episode_steps = (int)v; break;
+    case DM_OPT_TRUNCATION_LOG: {
+      if (v < 0 || v > 0x7fffffff) return fail(DM_EINVAL, "DM_OPT_TRUNCATION_LOG must be 0 (off) or a capacity in records");
+      HIPCHK(hipSetDevice(b->device));
+      if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+      HIPCHK(hipStreamSynchronize(b->stream));       /* (a termination launch still appending to the old log) */
+      void* old[] = {b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
+      for (void* p : old) if (p) hipFree(p);
+      b->d_trunc_count = b->d_trunc_index = nullptr; b->d_trunc_qpos = b->d_trunc_qvel = nullptr; b->trunc_cap = 0; b->trunc_tick = 0;
+      if (v > 0) {
+        const size_t c = (size_t)v;
+        const bool ok = hipMalloc((void**)&b->d_trunc_count, sizeof(int)) == hipSuccess && hipMalloc((void**)&b->d_trunc_index, c * 4 * sizeof(int)) == hipSuccess &&
+                        hipMalloc((void**)&b->d_trunc_qpos, c * NQ * sizeof(double)) == hipSuccess && hipMalloc((void**)&b->d_trunc_qvel, c * NV * sizeof(double)) == hipSuccess;
+        if (!ok) {
+          void* part[] = {b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
+          for (void* p : part) if (p) hipFree(p);
+          b->d_trunc_count = b->d_trunc_index = nullptr; b->d_trunc_qpos = b->d_trunc_qvel = nullptr;
+          (void)hipGetLastError();
+          return fail(DM_ENOMEM, "DM_OPT_TRUNCATION_LOG: hipMalloc failed");
+        }
+        /* cleared on the batch's stream, ahead of every later launch (a pipelined part's waits for this stream at the time of its call) */
+        HIPCHK(hipMemsetAsync(b->d_trunc_count, 0, sizeof(int), b->stream)); HIPCHK(hipMemsetAsync(b->d_trunc_index, 0, c * 4 * sizeof(int), b->stream));
+        HIPCHK(hipMemsetAsync(b->d_trunc_qpos, 0, c * NQ * sizeof(double), b->stream)); HIPCHK(hipMemsetAsync(b->d_trunc_qvel, 0, c * NV * sizeof(double), b->stream));
+        b->trunc_cap = (int)v;
+      }
+      break;
+    }
     case DM_OPT_PIPELINE: {
       if (v < 1 || v > DM_MAX_PIPELINE) return fail(DM_EINVAL, "pipeline depth must be 1..DM_MAX_PIPELINE");
       HIPCHK(hipSetDevice(b->device));
@@ -584,10 +610,13 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   // early termination: the plain step launches, then k_terminate on the same stream; a fused policy step would act on the observation of an episode
   // k_terminate may still end, so the policy runs as a launch of its own behind it (below)
   const bool term = term_on(b);
+  const int tick = b->trunc_tick;            // the truncation log's clock: this call's index since the log was cleared
+  if (b->trunc_cap > 0) b->trunc_tick += 1;
   const dmp::PolicyArgs* fused = term ? nullptr : pol;
   auto terminate = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count) {
     if (!term) return;
-    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count};
+    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count,
+                      b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->trunc_cap, tick};
     hipLaunchKernelGGL(k_terminate, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn);
   };
   if (packed) {
@@ -824,6 +853,21 @@ extern "C" int dm_batch_redo_total(dm_batch* b, int64_t* out) {
 extern "C" int dm_batch_queue_stats(dm_batch* b, int64_t* out) {
   if (!b || !out) return fail(DM_EINVAL, "dm_batch_queue_stats: null argument");
   out[0] = b->queue_flushes; out[1] = b->queue_steps; out[2] = (int64_t)b->q.size();
+  return DM_OK;
+}
+extern "C" int dm_batch_truncations(dm_batch* b, int32_t* count, int32_t* index, double* qpos, double* qvel, int32_t cap, int32_t clear, int32_t kind) {
+  if (!b || !count || cap < 0 || (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE)) return fail(DM_EINVAL, "dm_batch_truncations: null batch or count, negative cap, or bad ptr_kind");
+  if (b->trunc_cap <= 0) return fail(DM_EINVAL, "dm_batch_truncations: the truncation log is off (DM_OPT_TRUNCATION_LOG)");
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  const hipMemcpyKind k = kind == DM_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t m = (size_t)(cap < b->trunc_cap ? cap : b->trunc_cap);
+  HIPCHK(hipMemcpyAsync(count, b->d_trunc_count, sizeof(int32_t), k, b->stream));
+  if (index && m) HIPCHK(hipMemcpyAsync(index, b->d_trunc_index, m * 4 * sizeof(int32_t), k, b->stream));
+  if (qpos && m) HIPCHK(hipMemcpyAsync(qpos, b->d_trunc_qpos, m * NQ * sizeof(double), k, b->stream));
+  if (qvel && m) HIPCHK(hipMemcpyAsync(qvel, b->d_trunc_qvel, m * NV * sizeof(double), k, b->stream));
+  if (clear) { HIPCHK(hipMemsetAsync(b->d_trunc_count, 0, sizeof(int), b->stream)); b->trunc_tick = 0; }
+  if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
   return DM_OK;
 }
 extern "C" int dm_batch_join(dm_batch* b) {

@@ -26,6 +26,14 @@ extern "C" int dm_gae(const float* rew, const float* vpred, const int32_t* isnew
   HIPCHK(hipGetLastError());
   return DM_OK;
 }
+extern "C" int dm_gae_boot(const float* rew, const float* vpred, const int32_t* isnew, const float* nextvpred, const float* vboot, float* adv,
+                           float* tdlamret, int32_t T, int32_t n, double gamma, double lam, void* hip_stream) {
+  if (!rew || !vpred || !isnew || !nextvpred || !vboot || !adv || !tdlamret || T <= 0 || n <= 0) return fail(DM_EINVAL, "dm_gae_boot: bad argument");
+  hipLaunchKernelGGL(dmp::k_gae_boot, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, rew, vpred, (const int*)isnew, nextvpred, vboot, adv,
+                     tdlamret, (int)T, (int)n, (float)gamma, (float)lam);
+  HIPCHK(hipGetLastError());
+  return DM_OK;
+}
 extern "C" int dm_episode_scan(const double* reward, const uint8_t* done, int32_t T, int32_t n, double* cur_ret, int64_t* cur_len, int32_t* count,
                                int32_t cap, int64_t* records, void* hip_stream) {
   if (!reward || !done || !cur_ret || !cur_len || !count || !records || T <= 0 || n <= 0 || cap < 0) return fail(DM_EINVAL, "dm_episode_scan: bad argument");

@@ -291,6 +291,30 @@ __global__ __launch_bounds__(256) void k_gae(const float* __restrict__ rew, cons
     vnext = v; nonterminal = 1.0f - (float)isnew[i];         // for row t - 1: new[t]
   }
 }
+// k_gae with a bootstrap value per row (dm_gae_boot): vboot[t] is the value of the state step t left where a time limit truncated the episode there,
+// 0 elsewhere: delta = rew + gamma * (vnext * nonterminal + vboot) - v.  With vboot = 0 the outputs must be k_gae's bit for bit, whatever the compiler
+// contracts into fused multiply-adds there: so the one-step target keeps k_gae's expression, rew + gamma * x * y - v, with x = vnext * nonterminal + vboot
+// (exact for vboot = 0: nonterminal is 0 or 1, adding 0.0f is exact) and y = a 1.0f the compiler cannot see through.  Both kernels then round
+// gamma * x once and add rew with the same instruction.
+__global__ __launch_bounds__(256) void k_gae_boot(const float* __restrict__ rew, const float* __restrict__ vpred, const int* __restrict__ isnew,
+                                                  const float* __restrict__ nextvpred, const float* __restrict__ vboot, float* __restrict__ adv,
+                                                  float* __restrict__ tdlamret, int T, int n, float gamma, float lam) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  float last = 0.0f, vnext = nextvpred[e];
+  float nonterminal = 1.0f;                                   // new[T] := 0
+  float one = 1.0f;
+  asm volatile("" : "+v"(one));
+  for (int t = T - 1; t >= 0; t--) {
+    const size_t i = (size_t)t * n + e;
+    const float v = vpred[i];
+    const float x = vnext * nonterminal + vboot[i];
+    const float delta = rew[i] + gamma * x * one - v;
+    last = delta + gamma * lam * nonterminal * last;
+    adv[i] = last; tdlamret[i] = last + v;
+    vnext = v; nonterminal = 1.0f - (float)isnew[i];         // for row t - 1: new[t]
+  }
+}
 // Episode bookkeeping of the generator (src/trpo.py:68-79: `cur_ep_ret += rew; cur_ep_len += 1; if new: ep_rets.append(...)`) for N environments
 // over a [T, N] segment: thread = env walks its column, adds rewards in float64 in step order (the sums a per-env host loop would form) and
 // appends a record {t << 32 | env, return (bits), length} of every episode that ends to a list — in arrival order; the host sorts the few

@@ -8,7 +8,8 @@
 //                     DM_OPT_MAX_EPISODE_STEPS): counts the episode's steps, tests the state the step left for a fall contact and the step
 //                     limit, and ends the episode where either fires — done, the reason, and with DM_OPT_AUTORESET the tail of the step
 //                     kernels' epilogue (reset_env, the fresh observation row, store_state).  The step kernels carry none of this: with both
-//                     options off the launch is not issued.
+//                     options off the launch is not issued.  With DM_OPT_TRUNCATION_LOG it first appends the state of an episode that the time
+//                     limit alone ends to the batch's truncation log (dm_batch_truncations).
 #pragma once
 
 #include "floor_contact.h"
@@ -20,6 +21,13 @@ struct TermArgs {
   unsigned fall_bodies;    // DM_OPT_FALL_BODIES
   int max_steps;           // DM_OPT_MAX_EPISODE_STEPS
   int first, count;        // the part's env range
+  // the truncation log (DM_OPT_TRUNCATION_LOG): the state an episode had when the time limit ALONE ended it, kept for the
+  // learner's value bootstrap before reset_env overwrites it.  log_cap = 0: off, nothing below is read.
+  int* log_count;          // [1] records appended since the log was cleared (keeps counting beyond log_cap: overflow is visible)
+  int* log_index;          // [log_cap, 4] {env, tick, frame_idx, frame_init}
+  double* log_qpos;        // [log_cap, 35]
+  double* log_qvel;        // [log_cap, 34]
+  int log_cap, tick;       // capacity in records; the batch's step calls since the log was cleared
 };
 
 // bit g (1..15) of the result: geom g touches the floor at the kinematics in `s` (wave-collective; the same value in every lane)
@@ -65,6 +73,16 @@ __global__ __launch_bounds__(64) void k_terminate(const DevModel<Real>* __restri
   if (!fall && !limit) {
     if (lane == 0) { T.steps[env] = steps; T.reason[env] = 0; }
     return;
+  }
+  if (T.log_cap > 0 && !fall) {                           // ended by the time limit alone: a truncation, not a failure — log the state the step left
+    int slot = 0;
+    if (lane == 0) slot = atomicAdd(T.log_count, 1);      // (device scope: pipelined parts on other streams share the counter)
+    slot = dmw::uniform(slot);
+    if (slot < T.log_cap) {
+      if (lane < 4) T.log_index[(size_t)slot * 4 + lane] = lane == 0 ? env : (lane == 1 ? T.tick : (lane == 2 ? B.frame_idx[env] : B.frame_init[env]));
+      if (lane < NQ) T.log_qpos[(size_t)slot * NQ + lane] = (double)s.qpos[lane];
+      if (lane < NV) T.log_qvel[(size_t)slot * NV + lane] = (double)s.qvel[lane];
+    }
   }
   if (lane == 0) { done[env] = 1; T.reason[env] = (fall ? DM_DONE_FALL : 0) | (limit ? DM_DONE_TIME_LIMIT : 0); T.steps[env] = 0; }
   if (B.autoreset) {                                      // the tail of env_step_impl's epilogue: the fresh episode's state and observation row

@@ -380,8 +380,11 @@ class DPVecEnv(object):
 
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
-                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0):
-        """fall_contact_bodies: DeepMimic's early termination by fall contact — a set name of termination.FALL_BODY_SETS ("deepmimic": every body but the two
+                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0):
+        """truncation_log: capacity in records of the truncation log (DM_OPT_TRUNCATION_LOG; 0: off): with `max_episode_steps`, the state of every episode that
+        the time limit alone ends is kept for `truncations()` before auto-reset overwrites it — a truncation is not a failure, and a learner bootstraps the
+        value there (rollout.SegmentCollector(bootstrap_time_limit=True) sizes and reads the log itself).
+        fall_contact_bodies: DeepMimic's early termination by fall contact — a set name of termination.FALL_BODY_SETS ("deepmimic": every body but the two
         ankles; "crawl": root, chest, neck), or body names / ids; None: off.  max_episode_steps: the episode's limit in env steps; 0: off.  While either is on,
         one more launch follows every step launch, ends the episodes of the environments that fell or ran out of steps (done = 1, `done_reason()` says why) and,
         with `autoreset`, starts their next episode as the step itself does on its own done; horizon launches and the step queue fall back to step launches.
@@ -460,6 +463,8 @@ class DPVecEnv(object):
             b.set_option(A.OPT_FALL_BODIES, self.fall_body_mask)
         if self.max_episode_steps:
             b.set_option(A.OPT_MAX_EPISODE_STEPS, self.max_episode_steps)
+        if int(truncation_log):
+            b.set_option(A.OPT_TRUNCATION_LOG, int(truncation_log))
         rowless = not (contacts or limits)          # no constraint rows: every wave costs the same, the packed kernel wins at any batch size
         auto = packed is None and batch_factory is None and (self.num_envs >= PACKED_FROM_ENVS or (rowless and self.num_envs >= 256)) and dtype == 64
         # a horizon launch (Batch.rollout, rollout.SegmentCollector) may use the packed kernel at ANY batch size: there a wave does not wait
@@ -497,6 +502,11 @@ class DPVecEnv(object):
         """int32 [N]: why the last step ended each environment's episode — bits termination.DONE_STEP (COM band, clip end), DONE_FALL, DONE_TIME_LIMIT; 0
         where it did not.  Maintained while `fall_contact_bodies` or `max_episode_steps` is on.  `out`: a numpy array or a device tensor."""
         return self._batch.get(A.F_DONE_REASON, out)
+
+    def truncations(self, clear=True, out=None):
+        """(count, index [C,4] {env, tick, frame_idx, frame_init}, qpos [C,35], qvel [C,34]) of the episodes the time limit alone ended since the log was
+        last cleared (`truncation_log=C`; Batch.truncations has the contract)."""
+        return self._batch.truncations(clear, out)
 
     def reset(self, mode="rsi", out=None):
         self._batch.reset(mode={"rsi": 0, "init": 1, "qpos0": 2}[mode], hard=1)

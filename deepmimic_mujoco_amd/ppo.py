@@ -227,16 +227,17 @@ class PpoLearner:
 
 
 def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print, group=None, log_dir=None,
-          fused=None, schedule="linear", **learner_kwargs):
+          fused=None, schedule="linear", bootstrap_time_limit=False, **learner_kwargs):
     """ppo1's `learn()` over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy, with trpo.learn's loop (train_loop.run),
     stopping rules (`max_iters`, `max_timesteps` env steps (global), `max_seconds`), multi-rank handling and output files (`log_dir`: rank 0
     writes progress.csv and monitor.csv).  Episode statistics over ppo1's window of the last 100 episodes.  schedule="linear" needs
     max_timesteps.  fused: the rollout's policy step inside the env step kernel (None: when possible).  Returns the per-iteration stats:
-    loss_pol_surr, loss_pol_entpen, loss_vf_loss, loss_kl, loss_ent, clipfrac, ev_tdlam_before, EpLenMean, EpRewMean, EpThisIter, ..."""
+    loss_pol_surr, loss_pol_entpen, loss_vf_loss, loss_kl, loss_ent, clipfrac, ev_tdlam_before, EpLenMean, EpRewMean, EpThisIter, ...
+    bootstrap_time_limit: as in trpo.learn (value bootstrap where the time limit ends an episode; adds TruncThisIter)."""
     from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = PpoLearner(pi, group=group, schedule=schedule, max_timesteps=max_timesteps, **learner_kwargs)
-    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused)
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit)
     steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
 
     def iterate(timesteps_so_far):
@@ -246,6 +247,7 @@ def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, ma
         if getattr(seg, "info", None):
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
+        train_loop.truncation_stat(stats, seg)
         return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
 
     def log_line(stats):

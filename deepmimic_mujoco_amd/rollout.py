@@ -59,25 +59,40 @@ def add_vtarg_and_adv(seg, gamma, lam):
     seg["rew"], seg["vpred"], seg["new"] are [T, N]; seg["nextvpred"] is [N].  Per env column this is the reference's
     reversed loop verbatim:  nonterminal = 1 - new[t+1];  delta = rew[t] + gamma * vpred[t+1] * nonterminal - vpred[t];
     adv[t] = delta + gamma * lam * nonterminal * adv[t+1];  tdlamret = adv + vpred  — float32 like the reference's
-    `np.empty(T, 'float32')`.  T sequential steps of N-wide vector ops on the tensors' device (no host round trip)."""
+    `np.empty(T, 'float32')`.  T sequential steps of N-wide vector ops on the tensors' device (no host round trip).
+
+    With seg["vboot"] [T, N] (SegmentCollector(bootstrap_time_limit=True)): vboot[t] is the value of the state step t left where a time limit
+    truncated the episode there, 0 elsewhere, and delta[t] gains gamma * vboot[t] — the truncated state is worth the critic's value, not 0;
+    the chain still cuts at new[t+1].  Without the key nothing changes."""
     import torch
     rew, vpred, new = seg["rew"], seg["vpred"], seg["new"]
     T = rew.shape[0]
+    vboot = seg["vboot"] if "vboot" in seg else None
     if (rew.is_cuda and rew.dim() == 2 and rew.dtype == torch.float32 and vpred.dtype == torch.float32 and new.dtype == torch.int32
             and rew.is_contiguous() and vpred.is_contiguous() and new.is_contiguous()):
-        # one launch of the k_gae kernel (csrc/policy_kernel.h) instead of T small ones
+        # one launch of the k_gae kernel (csrc/policy_kernel.h) instead of T small ones; k_gae_boot with bootstrap values
         from . import _abi as A
         L, p = A.load(), A.ptr
         nxt = seg["nextvpred"].to(torch.float32).contiguous()
         adv = torch.empty_like(rew); ret = torch.empty_like(rew)
-        A.check(L.dm_gae(p(rew), p(vpred), p(new), p(nxt), p(adv), p(ret), T, rew.shape[1], float(gamma), float(lam),
-                         A.stream(rew.device)), L)
+        if vboot is None:
+            A.check(L.dm_gae(p(rew), p(vpred), p(new), p(nxt), p(adv), p(ret), T, rew.shape[1], float(gamma), float(lam),
+                             A.stream(rew.device)), L)
+        else:
+            vb = vboot.to(device=rew.device, dtype=torch.float32).contiguous()
+            if tuple(vb.shape) != tuple(rew.shape):
+                raise ValueError("seg['vboot'] must have the shape of seg['rew']")
+            A.check(L.dm_gae_boot(p(rew), p(vpred), p(new), p(nxt), p(vb), p(adv), p(ret), T, rew.shape[1], float(gamma), float(lam),
+                                  A.stream(rew.device)), L)
         seg["adv"], seg["tdlamret"] = adv, ret
         return seg
     new1 = torch.cat([new.to(torch.float32), torch.zeros_like(new[:1], dtype=torch.float32)], 0)     # np.append(new, 0)
     vp1 = torch.cat([vpred.to(torch.float32), seg["nextvpred"].to(torch.float32)[None]], 0)          # np.append(vpred, nextvpred)
     nonterminal = 1.0 - new1[1:]
-    delta = rew.to(torch.float32) + gamma * vp1[1:] * nonterminal - vp1[:-1]
+    if vboot is None:
+        delta = rew.to(torch.float32) + gamma * vp1[1:] * nonterminal - vp1[:-1]
+    else:
+        delta = rew.to(torch.float32) + gamma * (vp1[1:] * nonterminal + vboot.to(torch.float32)) - vp1[:-1]
     decay = (gamma * lam) * nonterminal
     adv = torch.empty_like(delta)
     last = torch.zeros_like(delta[0])
@@ -126,8 +141,21 @@ class Segment(dict):
     pending_episodes = None
     pending_true = None                  # with a reward_giver: the env's own returns ("ep_true_rets"), also on their way to the host
     info = None                          # how the segment was produced (launch form, overflow rate of the packed path): diagnostics, not data
+    pending_trunc = None                 # bootstrap_time_limit: (pinned int32 [1], event) — the truncation log's count on its way to the host
+    _trunc = None
+
+    def trunc_count(self):
+        """Episodes the time limit alone truncated inside the segment (the truncation log's count); None without bootstrap_time_limit."""
+        if self.pending_trunc is not None:
+            h, ev = self.pending_trunc
+            if ev is not None:
+                ev.synchronize()
+            self._trunc = int(h[0])
+            self.pending_trunc = None
+        return self._trunc
 
     def finish_episode_stats(self):
+        self.trunc_count()
         if self.pending_episodes is not None:
             rets, lens = self.pending_episodes.result()
             self.pending_episodes = None
@@ -180,13 +208,17 @@ class SegmentCollector(object):
     fixed for the whole segment, so this is the reference's per-step `reward_giver.get_reward(ob, ac)` (:78).  seg["rew"] and
     "ep_rets" then come from it, "ep_true_rets" from the env's reward through a second episode scan with its own carry (:85-91)."""
 
-    def __init__(self, pi, env, horizon, stochastic=True, device=None, first_reset="rsi", stream=None, fused=False, reward_giver=None):
+    def __init__(self, pi, env, horizon, stochastic=True, device=None, first_reset="rsi", stream=None, fused=False, reward_giver=None,
+                 bootstrap_time_limit=False):
         import torch
         self.pi, self.env, self.T, self.stochastic, self.stream = pi, env, int(horizon), stochastic, stream
         n, T = env.num_envs, self.T
         self.n = n
         device = torch.device(pi.device if device is None else device)
         self.device = device
+        self.bootstrap = bool(bootstrap_time_limit)
+        if self.bootstrap:
+            self._init_bootstrap()
         f32, f64 = torch.float32, torch.float64
         self.ob_width = int(env.observation_space.shape[0]) if getattr(env, "obs_mode", "dp_env_v3") != "dp_env_v3" else 56
         self.ob64 = torch.zeros((T + 1, n, self.ob_width), dtype=f64, device=device)   # row t: observation the policy sees at step t
@@ -223,6 +255,64 @@ class SegmentCollector(object):
         with self._on_stream():
             env.reset(first_reset, out=self.as_buf(self.ob64[0]))                  # trpo.py:32 `ob = env.reset()` (RSI); later episodes: noisy init
 
+    def _init_bootstrap(self):
+        """bootstrap_time_limit: the env's truncation log sized to the segment, and the buffers its records are read into.  An environment is
+        truncated at most once per M steps, and a segment's first truncation may fall on any of its rows: at most T // M + 1 per environment, so a
+        log of n (T // M + 1) records never overflows."""
+        import torch
+        from . import _abi as A
+        env, n, T, dev = self.env, self.n, self.T, self.device
+        M = int(getattr(env, "max_episode_steps", 0) or 0)
+        if M <= 0:
+            raise ValueError("bootstrap_time_limit needs an env with a time limit (DPVecEnv(max_episode_steps=M), M > 0)")
+        C = n * (T // M + 1)
+        self._trunc_cap = C
+        env.batch.set_option(A.OPT_TRUNCATION_LOG, C)
+        self._trunc = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros((C, 4), dtype=torch.int32, device=dev),
+                       torch.zeros((C, A.NQ), dtype=torch.float64, device=dev), torch.zeros((C, A.NV), dtype=torch.float64, device=dev))
+        self._trunc_ob = torch.zeros((C, int(env.observation_space.shape[0]) if getattr(env, "obs_mode", "dp_env_v3") != "dp_env_v3" else 56), dtype=torch.float64, device=dev)
+        self._trunc_slot = torch.arange(C, device=dev, dtype=torch.int64)
+        self.vboot = torch.zeros((T, n), dtype=torch.float32, device=dev)
+        self._h_trunc = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)] if dev.type == "cuda" else None
+        self._h_trunc_k = 0
+
+    def _clear_truncations(self):
+        """the log's count and tick start again (stream-ordered, nothing is copied but the old count)"""
+        self.env.batch.truncations(clear=True, out=(self.as_buf(self._trunc[0]), None, None, None))
+
+    def _bootstrap_values(self, seg):
+        """seg["vboot"] [T, n] f32: the critic's value of every state the time limit cut off in this segment, at (tick, env); 0 elsewhere.  All C slots
+        of the log become observations and are evaluated (at most n rows for T <= M); the slots at or above the count are masked on the device, so
+        nothing waits for the count."""
+        import torch
+        from . import _abi as A
+        from .state_features import phase_of
+        env, b, T, n, as_buf = self.env, self.env.batch, self.T, self.n, self.as_buf
+        cnt, idx, qp, qv = self._trunc
+        b.truncations(clear=False, out=tuple(as_buf(x) for x in self._trunc))
+        if self._trunc_ob.shape[1] == 56:
+            torch.cat([qp[:, 7:], qv[:, 6:]], 1, out=self._trunc_ob)
+        else:
+            # the phase the features launch would have given this state had the episode gone on: from the cursors as the step left them
+            phase = phase_of(int(b.options.get(A.OPT_REWARD_MODE, 0)), idx[:, 2], idx[:, 3], b.n_frames).contiguous()
+            b.state_features(as_buf(self._trunc_ob), qpos=as_buf(qp), qvel=as_buf(qv), phase=as_buf(phase))
+        with torch.no_grad():
+            v = self.pi.forward_value(self._trunc_ob).to(torch.float32)
+        tick, e = idx[:, 1].to(torch.int64), idx[:, 0].to(torch.int64)
+        ok = (self._trunc_slot < cnt.to(torch.int64)) & (tick >= 0) & (tick < T) & (e >= 0) & (e < n)
+        flat = torch.where(ok, tick * n + e, torch.zeros_like(tick))
+        # (tick, env) is unique among the valid records, the others add 0 to row 0: the sum IS the scatter, whatever order the records arrived in
+        self.vboot.zero_()
+        self.vboot.view(-1).index_add_(0, flat, torch.where(ok, v, torch.zeros_like(v)))
+        seg["vboot"] = self.vboot.clone()
+        if self._h_trunc is not None:
+            h = self._h_trunc[self._h_trunc_k]; self._h_trunc_k ^= 1
+            h.copy_(cnt, non_blocking=True)
+            ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(self.device))
+            seg.pending_trunc = (h, ev)
+        else:
+            seg.pending_trunc = (cnt.clone(), None)
+
     def _on_stream(self):
         import contextlib
         import torch
@@ -240,6 +330,8 @@ class SegmentCollector(object):
             if self.stream is not None:
                 self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with self._on_stream(), torch.no_grad():                                    # (the learner may hold the parameters with requires_grad)
+            if self.bootstrap:
+                self._clear_truncations()                                           # tick 0 = this segment's first step
             if self.fused:
                 if not self.have_ac0:
                     pi.act(self.stochastic, ob64[0], out=ac64[0], vpred_out=vpreds[0])                   # very first step: :49
@@ -328,6 +420,10 @@ class SegmentCollector(object):
         import torch
         T, n, device = self.T, self.n, self.device
         f32 = torch.float32
+        seg = Segment()
+        if self.bootstrap:
+            with self._on_stream():                    # (on the stream the batch is on: reading its log there needs no change of stream)
+                self._bootstrap_values(seg)
         if self.stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         import os
@@ -348,7 +444,6 @@ class SegmentCollector(object):
         # episode statistics: return / length of every episode that ended inside the segment, in time-major order
         # (= the order in which a single-env loop would have appended them, :72-76)
         native_eps = device.type == "cuda" and rew64.dtype == torch.float64 and rew64.is_contiguous() and done8.is_contiguous()
-        seg = Segment()
         seg.info = {"packed": self._packed_now, "kernel_switches": self.kernel_switches, "redo_rate": getattr(self, "_last_redo_rate", None)}
         if native_eps:
             seg.pending_episodes = self._episodes_native(rew64, done8)
@@ -436,7 +531,7 @@ class SegmentCollector(object):
         return ep_rets, ep_lens
 
 
-def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None):
+def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None, bootstrap_time_limit=False):
     """Batched `traj_segment_generator` (src/trpo.py:27-80): N envs advance in lock step on the device.
 
     pi: policy.MlpPolicy; env: DPVecEnv created with autoreset="init" — the kernel then applies, on `done`, exactly what
@@ -454,21 +549,25 @@ def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first
     Nothing leaves the device or the stream.
 
     reward_giver (src/gail.py:27-92): the rewards are the discriminator's (see SegmentCollector); the segment also carries
-    "ep_true_rets", the env's returns of the same episodes."""
-    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver)
+    "ep_true_rets", the env's returns of the same episodes.
+
+    bootstrap_time_limit (env with max_episode_steps > 0): the segment also carries "vboot" [T,N] f32, the critic's value of every state the time
+    limit cut off (SegmentCollector._bootstrap_values), which `add_vtarg_and_adv` adds to the one-step target there."""
+    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver, bootstrap_time_limit=bootstrap_time_limit)
     while True:
         c.launch()
         yield c.collect()
 
 
-def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset="rsi", fused=False):
+def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset="rsi", fused=False, bootstrap_time_limit=False):
     """The same segments from SEVERAL env batches (e.g. two halves of a GPU's envs) stepped concurrently, each on its own CUDA
     stream: the whole T-step chain of every batch (policy forward -> env step -> policy forward ...) is enqueued without a host
     wait, so while one batch's env kernel drains its last, cheap workgroups the other batch's policy / env kernels fill the freed
     wave slots — the overlap `DM_OPT_PIPELINE` gives open-loop stepping, for the closed loop.  Yields one segment dict whose env
     axis is the concatenation of the batches (episode lists concatenated in batch order)."""
     import torch
-    cols = [SegmentCollector(pi, e, horizon, stochastic, None, first_reset, stream=torch.cuda.Stream(device=pi.device), fused=fused) for e in envs]
+    cols = [SegmentCollector(pi, e, horizon, stochastic, None, first_reset, stream=torch.cuda.Stream(device=pi.device), fused=fused,
+                             bootstrap_time_limit=bootstrap_time_limit) for e in envs]
     while True:
         if getattr(pi, "_dirty", False) or getattr(pi, "_packed", None) is None:
             pi.pack()                                  # once, on the current stream, before the side streams fork from it
@@ -477,8 +576,10 @@ def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset=
         segs = [c.collect() for c in cols]
         for sg in segs:
             sg.finish_episode_stats()                  # (the lists are concatenated below)
-        out = {}
-        for k in segs[0]:
+        out = Segment()
+        if bootstrap_time_limit:
+            out._trunc = sum(sg.trunc_count() for sg in segs)
+        for k in segs[0]:                              # ("vboot", when there, is [T, N] like "rew": it joins along the env axis)
             if k in ("ep_rets", "ep_lens"):
                 out[k] = [x for sg in segs for x in sg[k]]
             elif k == "nextvpred":

@@ -49,11 +49,17 @@ def obs_width(obs_mode):
 
 
 def phase_of(reward_mode, frame_idx, frame_init, n_frames):
-    """Phase in [0, 1) of the clip from a batch's cursor fields (ints or integer arrays); reward_mode: 0..4 or a name of
+    """Phase in [0, 1) of the clip from a batch's cursor fields (ints, integer arrays or torch tensors); reward_mode: 0..4 or a name of
     `dp_env.REWARD_MODES`."""
     if isinstance(reward_mode, str):
         from .dp_env import REWARD_MODES
         reward_mode = REWARD_MODES[reward_mode]
+    if type(frame_idx).__module__.startswith("torch"):      # tensors stay tensors, on their device (float64 like the numpy form)
+        import torch
+        k = frame_idx.to(torch.int64)
+        if int(reward_mode) in (2, 4):
+            k = k + torch.as_tensor(frame_init, device=k.device).to(torch.int64)
+        return (k % int(n_frames)).to(torch.float64) / float(n_frames)
     k = np.asarray(frame_idx, dtype=np.int64)
     if int(reward_mode) in (2, 4):
         k = k + np.asarray(frame_init, dtype=np.int64)

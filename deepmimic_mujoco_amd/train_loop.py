@@ -8,14 +8,23 @@ from collections import deque
 import torch
 
 
-def segments(pi, env, horizon, fused=None):
-    """-> (segment generator, this rank's env count) over a DPVecEnv, or a list of them (pipelined rollouts)."""
+def segments(pi, env, horizon, fused=None, bootstrap_time_limit=False):
+    """-> (segment generator, this rank's env count) over a DPVecEnv, or a list of them (pipelined rollouts).  bootstrap_time_limit: the segments carry
+    "vboot", the critic's value of the states a time limit cut off (rollout.SegmentCollector)."""
     from .rollout import can_fuse, pipelined_segment_generator, traj_segment_generator
     if isinstance(env, (list, tuple)):          # several env batches of this rank, stepped concurrently on their own streams
-        return pipelined_segment_generator(pi, list(env), horizon, stochastic=True), sum(e.num_envs for e in env)
+        return pipelined_segment_generator(pi, list(env), horizon, stochastic=True, bootstrap_time_limit=bootstrap_time_limit), sum(e.num_envs for e in env)
     # fused (default when possible): the policy step runs inside the env step kernel, one launch per rollout step
     use_fused = can_fuse(pi, env) if fused is None else bool(fused)
-    return traj_segment_generator(pi, env, horizon, stochastic=True, fused=use_fused), env.num_envs
+    return traj_segment_generator(pi, env, horizon, stochastic=True, fused=use_fused, bootstrap_time_limit=bootstrap_time_limit), env.num_envs
+
+
+def truncation_stat(stats, seg):
+    """TruncThisIter: the episodes the time limit alone truncated in `seg` (a bootstrap_time_limit segment; nothing is added otherwise)."""
+    count = getattr(seg, "trunc_count", None)
+    n = count() if count is not None else None
+    if n is not None:
+        stats["TruncThisIter"] = n
 
 
 def run(pi, iterate, *, window, columns, log_line, names, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print, group=None,

@@ -687,17 +687,19 @@ class TrpoLearner:
 
 
 def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print,
-          group=None, log_dir=None, fused=None, **learner_kwargs):
+          group=None, log_dir=None, fused=None, bootstrap_time_limit=False, **learner_kwargs):
     """`learn()` of src/trpo.py:97-319 over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy.  Stops after `max_iters`
     iterations, `max_timesteps` env steps (global) or `max_seconds`.  Returns the list of per-iteration stat dicts, with
     the reference's log keys (EpLenMean / EpRewMean over the last 40 episodes, EpThisIter, EpisodesSoFar, TimestepsSoFar,
     TimeElapsed, entropy, meankl, optimgain, surrgain, ev_tdlam_before).  With `log_dir`, rank 0 also writes the reference's
     files there: `progress.csv` (logger CSV, src/logger.py:101-135) and `monitor.json.monitor.csv` (bench.Monitor, one row per
-    finished episode of rank 0's envs) — readable by the reference's plot_curve.py / load_results."""
+    finished episode of rank 0's envs) — readable by the reference's plot_curve.py / load_results.
+    bootstrap_time_limit (the env has max_episode_steps > 0): a time-limit end is a truncation — the value target bootstraps from the critic's value of
+    the state the limit cut off (rollout.SegmentCollector), and the stats gain TruncThisIter, the number of such ends in the iteration's segment."""
     from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = TrpoLearner(pi, group=group, **learner_kwargs)
-    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused)
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit)
     steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
 
     def iterate(timesteps_so_far):
@@ -715,6 +717,7 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
         if getattr(seg, "info", None):
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
+        train_loop.truncation_stat(stats, seg)
         return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
 
     def log_line(stats):

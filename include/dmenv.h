@@ -173,7 +173,7 @@ enum {
   DM_OPT_FALL_BODIES = 9, /* DeepMimic's early termination by fall contact (--fall_contact_bodies).  A bit mask over model bodies, bit b for
                              body b = 1..13; 0 (default): off.  An environment FALLS when a geom of a body in the mask touches the floor
                              (dm_batch_floor_contacts has the rule) at the state the step left it in. */
-  DM_OPT_MAX_EPISODE_STEPS = 10 /* the episode time limit (--time_end_lim_max), in env steps.  0 (default): off.  M > 0: the episode ends on its
+  DM_OPT_MAX_EPISODE_STEPS = 10, /* the episode time limit (--time_end_lim_max), in env steps.  0 (default): off.  M > 0: the episode ends on its
                              M-th env step.
                              While either of the two options is non-zero, every per-step launch of dm_batch_step is followed on the same
                              stream (a pipelined part's: on that part's stream, over its env range) by one more launch, one wave per
@@ -190,6 +190,18 @@ enum {
                              dm_batch_rollout run as the plain step launch, the termination launch, then the launch behind dm_policy_act
                              on the returned observations (over the whole batch, after the parts of a pipelined step have joined): the
                              result of dm_batch_step followed by dm_policy_act, bit for bit. */
+  DM_OPT_TRUNCATION_LOG = 11 /* the truncation log's capacity C in records.  0 (default): off; negative: DM_EINVAL.  It has an effect only while
+                             DM_OPT_MAX_EPISODE_STEPS > 0.  A time limit truncates an infinite-horizon task: the state it cuts off is worth the
+                             critic's value, not 0 as after a fall, and with DM_OPT_AUTORESET the termination launch overwrites that state.  With
+                             C > 0 it first appends a record for every episode it ends by the time limit ALONE (DM_F_DONE_REASON exactly
+                             DM_DONE_TIME_LIMIT; not where the fall test fired as well, not where the step itself reported done), with or without
+                             auto-reset: an int32 row {env, tick, frame_idx, frame_init} and qpos [35] / qvel [34] (float64 in both libraries) as
+                             the step left them, the cursors as the step left them too.  tick = the batch's dm_batch_step calls (the steps of a
+                             dm_batch_rollout count one each) since the log was last cleared, 0 for the first.  Records beyond C are not
+                             stored but still counted, so an overflow shows in the count.  The order of the records is the order in which
+                             wavefronts arrived (the parts of a pipelined step share the one counter) and carries no meaning: key on
+                             (tick, env).  Setting the option (again) joins the batch, waits for its stream, reallocates and clears the log and the
+                             tick.  Off, the termination launch is bit for bit what it is without the option.  dm_batch_truncations reads it. */
 };
 /* bits of DM_F_DONE_REASON */
 #define DM_DONE_STEP 1       /* the step's own done: COM height outside (0.7, 2.0), or the end of a "Loop: none" clip */
@@ -259,6 +271,12 @@ enum {
                            DM_DONE_FALL | DM_DONE_TIME_LIMIT (both may be set); 0 where the env is not done */
 };
 int dm_batch_get(dm_batch* b, int32_t field, void* out, size_t bytes, int32_t ptr_kind);
+/* Read the truncation log (DM_OPT_TRUNCATION_LOG = C > 0).  Runs what is queued and joins the pipelined parts first, like dm_batch_join.  count [1]
+ * receives the number of records appended since the log was last cleared — it may exceed C (overflow); index [cap,4], qpos [cap,35], qvel [cap,34]
+ * (each may be NULL) receive the first min(cap, C) records, of which the first min(count, C) are valid.  With `clear` the count and the tick then start
+ * again from 0, on the batch's stream.  Device pointers: stream-ordered copies, no host wait; host pointers: one wait at the end.
+ * DM_EINVAL: null batch, null count, cap < 0, a bad ptr_kind, or the log is off. */
+int dm_batch_truncations(dm_batch* b, int32_t* count, int32_t* index, double* qpos, double* qvel, int32_t cap, int32_t clear, int32_t ptr_kind);
 int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t bytes, int32_t ptr_kind);
 
 /* One forward evaluation (mj_forward = sim.forward()) of environment `env` with every intermediate dumped:
@@ -386,6 +404,12 @@ int dm_batch_rollout(dm_batch* b, double* action, double* obs, double* reward, u
  * isnew [T, N] int32 (isnew[t] = the observation of step t starts an episode), nextvpred [N]; device pointers. */
 int dm_gae(const float* rew, const float* vpred, const int32_t* isnew, const float* nextvpred, float* adv, float* tdlamret,
            int32_t T, int32_t n, double gamma, double lam, void* hip_stream);
+/* The same with a bootstrap value per row (the time limit as a truncation: DM_OPT_TRUNCATION_LOG): vboot [T, N] float32, vboot[t] = the value of the
+ * state step t left where its episode was truncated there, 0 everywhere else.  The one-step target gains one term,
+ *   delta[t] = rew[t] + gamma * (vpred[t+1] * (1 - isnew[t+1]) + vboot[t]) - vpred[t],
+ * and the chain still cuts where isnew[t+1] = 1.  With vboot all zeros the outputs are dm_gae's bit for bit. */
+int dm_gae_boot(const float* rew, const float* vpred, const int32_t* isnew, const float* nextvpred, const float* vboot, float* adv, float* tdlamret,
+                int32_t T, int32_t n, double gamma, double lam, void* hip_stream);
 
 /* Replaces: the episode bookkeeping of the generator's loop (src/trpo.py:68-79) over a [T, N] segment that dm_batch_rollout / T dm_batch_step
  * calls wrote (reward f64, done u8).  cur_ret [N] f64 / cur_len [N] i64: return and length of every environment's open episode, read and

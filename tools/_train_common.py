@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --bootstrap-time-limit and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk")
     if reward_help:
         ap.add_argument("--reward", default="alive", help=reward_help)
@@ -22,11 +22,20 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
                     help="DeepMimic's early termination: the episode ends when a body of the set touches the floor.  deepmimic = every body except the two ankles; "
                          "crawl = root, chest, neck (the floor clips); none (default) = only the reference's centre-of-mass rule")
     ap.add_argument("--max-episode-steps", type=int, default=0,
-                    help="the episode's time limit in env steps (0 = none).  A time-limit done is a done like any other: the learners do not bootstrap the value there")
+                    help="the episode's time limit in env steps (0 = none).  Without --bootstrap-time-limit a time-limit done is a done like any other: the state it cuts off is worth 0")
+    ap.add_argument("--bootstrap-time-limit", action="store_true",
+                    help="treat a time-limit end as a truncation (DeepMimic's agent): the value target bootstraps from the critic's value of the state the limit cut off, "
+                         "where a fall keeps 0.  Needs --max-episode-steps")
     if autoreset_help:
         ap.add_argument("--autoreset", default="init", help=autoreset_help)
     if frame_skip_help:
         ap.add_argument("--frame-skip", default=None, help=frame_skip_help)
+
+
+def check_env_args(ap, args):
+    """Refuse flag combinations that cannot work, with the parser's own error message."""
+    if getattr(args, "bootstrap_time_limit", False) and not args.max_episode_steps > 0:
+        ap.error("--bootstrap-time-limit bootstraps the value where the time limit ends an episode: it needs --max-episode-steps M with M > 0")
 
 
 def env_kwargs(args):

@@ -10,10 +10,16 @@ profiles/term_kernels.md.  Modelled on tools/state_bench.py; two kinds of runs, 
                 hundred steps with termination on, nothing timed.  Their `*_kernel_stats.csv` files come back through `--stats N=file`; the
                 report then states k_terminate's time per launch and where a step's GPU time goes.
 
+`--truncation-log`: the cost of the truncation log (DM_OPT_TRUNCATION_LOG: one atomic and 73 stores per environment the time limit truncates) instead:
+the same two kinds of runs with the time limit on (`--limit` env steps; after the window's RSI reset every environment reaches it on the same step, the
+worst case for the log) and the log off / on alternating; `--trace N --truncation-log` is the profiled workload.  The report is APPENDED to `--out` as a
+section of its own.
+
 `--resources-before file.md`: the table tools/kernel_resources.py printed for the library BEFORE the feature; the report lists the step
 kernels' rows of both and says whether any pre-existing kernel changed.  `--ab file`: the alternating parent / this-build lines of the
 default benchmark (tools/ab_bench.sh's form), quoted in the report.
-usage: python tools/term_bench.py [--envs 4096 8192] [--steps 200] [--warmup 30] [--reps 5] [--stats N=csv ...] [--resources-before file.md]
+usage: python tools/term_bench.py --truncation-log [--limit 10] [--envs 4096 8192] [--stats N=csv ...] [--resources-before file.md] [--train-json file]
+       python tools/term_bench.py [--envs 4096 8192] [--steps 200] [--warmup 30] [--reps 5] [--stats N=csv ...] [--resources-before file.md]
                                   [--ab file] [--out profiles/term_kernels.md]
        rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python tools/term_bench.py --trace 4096"""
 import argparse
@@ -31,16 +37,21 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from state_bench import buffers, parse_before, read_stats, short  # noqa: E402
 
 
-def make_env(n, fall):
+def make_env(n, fall, limit=0, log=0):
     from deepmimic_mujoco_amd import DPVecEnv
-    return DPVecEnv(n, motion="walk", device=0, reward="imitation", autoreset="rsi", seed=1, fall_contact_bodies=fall)
+    return DPVecEnv(n, motion="walk", device=0, reward="imitation", autoreset="rsi", seed=1, fall_contact_bodies=fall, max_episode_steps=limit, truncation_log=log)
 
 
-def trace_run(n, steps, warmup):
-    """the workload of a rocprofv3 run: closed-loop steps with the "deepmimic" fall set; nothing is timed here"""
+def log_capacity(n, args):
+    """records a window can produce: every environment once per `--limit` steps, warm-up included (the log is cleared before every window)"""
+    return n * ((args.warmup + args.steps) // args.limit + 1)
+
+
+def trace_run(n, steps, warmup, args=None):
+    """the workload of a rocprofv3 run: closed-loop steps with the "deepmimic" fall set (--truncation-log: with the time limit and the log); nothing is timed here"""
     import torch
     dev = torch.device("cuda", 0)
-    env = make_env(n, "deepmimic")
+    env = make_env(n, None, args.limit, log_capacity(n, args)) if args is not None and args.truncation_log else make_env(n, "deepmimic")
     g = torch.Generator(device=dev); g.manual_seed(5)
     ac = torch.randn((n, 28), generator=g, dtype=torch.float64, device=dev) * 0.1
     out = buffers(n, 56, dev)
@@ -57,16 +68,22 @@ def measure(n, args):
     import torch
     from deepmimic_mujoco_amd import _abi as A
     dev = torch.device("cuda", 0)
-    envs = {"off": make_env(n, None), "on": make_env(n, "deepmimic")}
+    if args.truncation_log:
+        envs = {"off": make_env(n, None, args.limit), "on": make_env(n, None, args.limit, log_capacity(n, args))}
+    else:
+        envs = {"off": make_env(n, None), "on": make_env(n, "deepmimic")}
     out = buffers(n, 56, dev)
     g = torch.Generator(device=dev); g.manual_seed(5)
     ac = torch.randn((n, 28), generator=g, dtype=torch.float64, device=dev) * 0.1
     rates = {m: [] for m in envs}
     ended = {m: 0 for m in envs}
+    logged = 0
     for rep in range(args.reps):
         for m in ("off", "on") if rep % 2 == 0 else ("on", "off"):
             env = envs[m]
             env.reset("rsi")
+            if args.truncation_log and m == "on":
+                env.truncations(clear=True)
             for _ in range(args.warmup):
                 env.step(ac, out=out)
             torch.cuda.synchronize()
@@ -77,12 +94,58 @@ def measure(n, args):
             torch.cuda.synchronize()
             rates[m].append(n * args.steps / (time.perf_counter() - t0))
             ended[m] += int(env.batch.get(A.F_EPISODE).sum()) - ep0
+            if args.truncation_log and m == "on":
+                cnt = int(env.truncations(clear=False)[0][0])
+                assert 0 < cnt <= log_capacity(n, args), "the log overflowed or stayed empty: %d" % cnt
+                logged = logged + cnt if rep else cnt
     res = dict(envs=n, packed=bool(envs["on"].packed), frame_skip=envs["on"].frame_skip)
     for m in envs:
         res[m] = dict(median=float(np.median(rates[m])), min=float(min(rates[m])), max=float(max(rates[m])), episodes=ended[m])
         envs[m].close()
     res["ratio"] = res["on"]["median"] / res["off"]["median"]
+    if args.truncation_log:
+        res["records"] = logged
     return res
+
+
+def report_log(results, stats, args, device):
+    """the section `--truncation-log` appends to the report"""
+    L = ["", "# The truncation log: cost of `DM_OPT_TRUNCATION_LOG` (`tools/term_bench.py --truncation-log`)", "",
+         "Device: %s.  The workload of the sections above with `max_episode_steps=%d` and no fall set; the log off and on (capacity: every environment once per %d steps of a"
+         % (device, args.limit, args.limit),
+         "window, cleared before each) alternate in one process, %d windows of %d steps after %d warm-up steps.  Every window starts from an RSI reset of the whole batch, so all"
+         % (args.reps, args.steps, args.warmup),
+         "environments that the step does not end itself reach the limit on the same step: the log's worst case (one atomic on one counter and 73 stores per truncating environment).", "",
+         "| envs | step kernel when the run ended | log off env-steps/s (median, min .. max) | log on env-steps/s (median, min .. max) | on / off | records logged in the windows |",
+         "|---|---|---|---|---|---|"]
+    for r in results:
+        a, d = r["off"], r["on"]
+        L.append("| %d | %s | %.3f M (%.3f .. %.3f) | %.3f M (%.3f .. %.3f) | %.4f | %d |"
+                 % (r["envs"], "four envs per wave" if r["packed"] else "one env per wave", a["median"] / 1e6, a["min"] / 1e6, a["max"] / 1e6, d["median"] / 1e6, d["min"] / 1e6,
+                    d["max"] / 1e6, r["ratio"], r.get("records", 0)))
+    L += ["", "## `k_terminate` with the log on (`rocprofv3 --kernel-trace --stats`, a run of its own: `--trace N --truncation-log`)", ""]
+    if not stats:
+        L.append("not measured")
+    for n, path in stats:
+        rows = read_stats(path)
+        tot = sum(r[3] for r in rows)
+        term = [r for r in rows if "k_terminate" in r[0]]
+        if term:
+            L += ["%d envs: `k_terminate` %.2f us per launch (%d launches), %.2f %% of the run's GPU kernel time." % (n, term[0][2] / 1e3, term[0][1], 100 * term[0][3] / tot), ""]
+    if args.train_json and os.path.exists(args.train_json):
+        L += ["## Training (`tools/train_trpo.py`, 4 096 envs x 128 steps, `--max-episode-steps 600`, with and without `--bootstrap-time-limit`, alternating)", "", "```"]
+        L += [ln.rstrip() for ln in open(args.train_json).read().splitlines() if ln.strip()]
+        L += ["```", ""]
+    rows, before = resources(args.resources_before)
+    if "k_terminate" in rows:
+        r = rows["k_terminate"]
+        L += ["## Resources", "", "`k_terminate`: %d VGPR, %d SGPR, %d B LDS, %d B scratch, %d spilled VGPR." % (r["vgpr"], r["sgpr"], r["lds"], r["scratch"], r["vspill"]), ""]
+    if before is not None:
+        now = {k: (r["vgpr"], r["agpr"], r["sgpr"], r["vspill"], r["lds"], r["scratch"]) for k, r in rows.items()}
+        changed = sorted(k for k in before if k in now and now[k] != before[k])
+        L += ["Against the table of the library before the log: %d kernels then, %d now; new: %s; pre-existing kernels whose row changed: %s."
+              % (len(before), len(now), ", ".join("`%s`" % k for k in sorted(k for k in now if k not in before)) or "none", ", ".join("`%s`" % k for k in changed) or "none"), ""]
+    return "\n".join(L) + "\n"
 
 
 def resources(before_path):
@@ -162,14 +225,21 @@ def main():
     ap.add_argument("--stats", nargs="*", default=[])
     ap.add_argument("--resources-before", default=None)
     ap.add_argument("--ab", default=None)
+    ap.add_argument("--truncation-log", action="store_true", help="measure the truncation log (time limit on, the log off / on) and append the section to --out")
+    ap.add_argument("--limit", type=int, default=10, help="--truncation-log: max_episode_steps")
+    ap.add_argument("--train-json", default=None, help="--truncation-log: a file of training iteration times to quote")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "term_kernels.md"))
     args = ap.parse_args()
     if args.trace:
-        trace_run(args.trace, args.steps, args.warmup)
+        trace_run(args.trace, args.steps, args.warmup, args)
         return
     import torch
     results = [measure(n, args) for n in args.envs]
     stats = [(int(s.split("=")[0]), s.split("=", 1)[1]) for s in args.stats]
+    if args.truncation_log:
+        open(args.out, "a").write(report_log(results, stats, args, torch.cuda.get_device_name(0)))
+        print(json.dumps(dict(results=results, out=args.out)))
+        return
     txt = report(results, stats, args, torch.cuda.get_device_name(0))
     open(args.out, "w").write(txt)
     print(json.dumps(dict(results=results, out=args.out)))

@@ -59,6 +59,7 @@ def main():
     ap.add_argument("--BC-max-iter", dest="BC_max_iter", type=int, default=10000, help="--pretrained: BC iterations (the reference's --BC_max_iter)")
     ap.add_argument("--bc-save", default=None, help="--pretrained: write the cloned policy (x.npz or a checkpoint prefix) before GAIL")
     args = ap.parse_args()
+    common.check_env_args(ap, args)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if args.task in ("evaluate", "sample"):
@@ -81,7 +82,7 @@ def main():
     reward_giver = TransitionClassifier(ob_dim=env.observation_space.shape[0], hidden_size=args.adversary_hidden_size, entcoeff=args.adversary_entcoeff, device=dev, seed=args.seed)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     hist = learn(env, pi, reward_giver, expert, g_step=args.g_step, d_step=args.d_step, d_stepsize=args.d_stepsize, timesteps_per_batch=args.horizon,
-                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, algo=args.algo, **stop)
+                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, algo=args.algo, bootstrap_time_limit=args.bootstrap_time_limit, **stop)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump({"args": vars(args), "history": hist}, open(args.out, "w"))

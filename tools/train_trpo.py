@@ -51,6 +51,7 @@ def main():
     ap.add_argument("--save", default=None, help="write the trained policy: `x.npz` (reference variable names) or a checkpoint prefix -> "
                                                  "tf.train.Saver bundle (x.index + x.data-00000-of-00001) the reference's `--task evaluate --load_model_path x` restores")
     args = ap.parse_args()
+    common.check_env_args(ap, args)
     world, rank, lr, dev = common.init_device(args.dist_backend)
     kw = common.env_kwargs(args)
     if args.task == "evaluate":                     # src/trpo.py:480-487
@@ -78,7 +79,7 @@ def main():
     pi = MlpPolicy(ob_dim=(envs[0] if args.unfused else env).observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     hist = learn(env, pi, timesteps_per_batch=args.horizon, max_seconds=args.seconds if not args.iters else 0, max_iters=args.iters,
                  vf_batch_size=args.vf_batch, vf_stepsize=args.vf_stepsize, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir,
-                 fused=False if args.unfused else None, pg_native=False if args.no_pg_native else None)
+                 fused=False if args.unfused else None, pg_native=False if args.no_pg_native else None, bootstrap_time_limit=args.bootstrap_time_limit)
     if args.dump_params:
         os.makedirs(os.path.dirname(os.path.abspath(args.dump_params)), exist_ok=True)
         pi.save_npz("%s.rank%d.npz" % (args.dump_params, rank))
