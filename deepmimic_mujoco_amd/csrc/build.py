@@ -39,6 +39,14 @@ def hipcc():
 
 
 OUT32 = os.path.join(HERE, "libdmenv32.so")
+# The float32 library contracts a multiply and an add into an FMA only where they stand in ONE source expression (-ffp-contract=on; hipcc's default,
+# `fast`, lets the backend fuse across expressions wherever inlining brings a product and a sum together).  Its cross-lane and PGS primitives are
+# compiler-visible C++ (csrc/wave.h; the float64 forms are inline assembly), and the step is instantiated several times — lean / three-set, per-step /
+# horizon, the position stage once in the step and once in the 5-term reward — so under `fast` the instantiations rounded differently: results depended
+# on the launch form and on which environments shared a wave (tests/test_gpu_float32.py: 226 of 256 envs differed between the step queue's horizon
+# launch and unqueued packed steps in reward mode 3).  With `on` every copy of a formula is the same arithmetic and the packed forms agree bit for bit, as
+# include/dmenv.h promises.  The float64 library's commands are unchanged.
+FLOAT32_DEFS = ["-DDM_REAL_FLOAT", "-ffp-contract=on"]
 
 def _stale(out, srcs):
     return not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs)
@@ -67,12 +75,12 @@ def build_one(out, defs=(), extra=(), verbose=False, objdir=None):
 
 
 def build(force=False, verbose=False):
-    """libdmenv.so (float64 arithmetic: the parity build) and libdmenv32.so (-DDM_REAL_FLOAT: the same kernels in float32, the
+    """libdmenv.so (float64 arithmetic: the parity build) and libdmenv32.so (FLOAT32_DEFS: the same kernels in float32, the
     `dtype 32` batch), compiled side by side.  Returns the path of libdmenv.so."""
     import threading
     srcs = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(REPO, "include", "dmenv.h"), os.path.abspath(__file__)]      # (this file: the units' backend options)
     extra = os.environ.get("DM_BUILD_DEFINES", "").split()
-    todo = [(out, defs) for out, defs in ((OUT, []), (OUT32, ["-DDM_REAL_FLOAT"])) if force or _stale(out, srcs)]
+    todo = [(out, defs) for out, defs in ((OUT, []), (OUT32, FLOAT32_DEFS)) if force or _stale(out, srcs)]
     errs = []
 
     def run(out, defs):

@@ -9,48 +9,64 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
 
 MAXBODY, MAXJNT, MAXV, MAXQ, MAXU, MAXGEOM = 16, 32, 36, 40, 32, 20
 JNT_FREE, JNT_HINGE = 0, 3
 GEOM_PLANE, GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX = 0, 2, 3, 6
 
 
-class Spec(C.Structure):
-    """Mirror of `dmo_spec` (oracle/dm_oracle.h) for building small test rigs from Python."""
-    _fields_ = [
-        ("nbody", C.c_int), ("njnt", C.c_int), ("ngeom", C.c_int), ("nu", C.c_int),
-        ("body_parent", C.c_int * MAXBODY), ("body_pos", (C.c_double * 3) * MAXBODY),
-        ("jnt_type", C.c_int * MAXJNT), ("jnt_body", C.c_int * MAXJNT), ("jnt_limited", C.c_int * MAXJNT),
-        ("jnt_axis", (C.c_double * 3) * MAXJNT), ("jnt_range", (C.c_double * 2) * MAXJNT),
-        ("jnt_armature", C.c_double * MAXJNT), ("jnt_damping", C.c_double * MAXJNT),
-        ("geom_type", C.c_int * MAXGEOM), ("geom_body", C.c_int * MAXGEOM), ("geom_condim", C.c_int * MAXGEOM),
-        ("geom_contype", C.c_int * MAXGEOM), ("geom_conaffinity", C.c_int * MAXGEOM),
-        ("geom_has_fromto", C.c_int * MAXGEOM),
-        ("geom_size", (C.c_double * 3) * MAXGEOM), ("geom_pos", (C.c_double * 3) * MAXGEOM),
-        ("geom_fromto", (C.c_double * 6) * MAXGEOM),
-        ("geom_mass", C.c_double * MAXGEOM), ("geom_friction", (C.c_double * 3) * MAXGEOM),
-        ("geom_margin", C.c_double * MAXGEOM),
-        ("act_jnt", C.c_int * MAXU), ("act_gear", C.c_double * MAXU), ("act_ctrlrange", (C.c_double * 2) * MAXU),
-        ("nexclude", C.c_int), ("exclude", (C.c_int * 2) * 16),
-        ("timestep", C.c_double), ("gravity", C.c_double * 3), ("tolerance", C.c_double),
-        ("iterations", C.c_int),
-        ("solref", C.c_double * 2), ("solimp", C.c_double * 5),
-    ]
+_REAL = {64: (C.c_double, np.float64, "liboracle.so"), 32: (C.c_float, np.float32, "liboracle32.so")}
+_LIBS = {}
 
 
-def build(force=False):
-    so = os.path.join(_HERE, "liboracle.so")
+def _spec_type(real, name):
+    class _Spec(C.Structure):
+        """Mirror of `dmo_spec` (oracle/dm_oracle.h) for building small test rigs from Python."""
+        _fields_ = [
+            ("nbody", C.c_int), ("njnt", C.c_int), ("ngeom", C.c_int), ("nu", C.c_int),
+            ("body_parent", C.c_int * MAXBODY), ("body_pos", (real * 3) * MAXBODY),
+            ("jnt_type", C.c_int * MAXJNT), ("jnt_body", C.c_int * MAXJNT), ("jnt_limited", C.c_int * MAXJNT),
+            ("jnt_axis", (real * 3) * MAXJNT), ("jnt_range", (real * 2) * MAXJNT),
+            ("jnt_armature", real * MAXJNT), ("jnt_damping", real * MAXJNT),
+            ("geom_type", C.c_int * MAXGEOM), ("geom_body", C.c_int * MAXGEOM), ("geom_condim", C.c_int * MAXGEOM),
+            ("geom_contype", C.c_int * MAXGEOM), ("geom_conaffinity", C.c_int * MAXGEOM),
+            ("geom_has_fromto", C.c_int * MAXGEOM),
+            ("geom_size", (real * 3) * MAXGEOM), ("geom_pos", (real * 3) * MAXGEOM),
+            ("geom_fromto", (real * 6) * MAXGEOM),
+            ("geom_mass", real * MAXGEOM), ("geom_friction", (real * 3) * MAXGEOM),
+            ("geom_margin", real * MAXGEOM),
+            ("act_jnt", C.c_int * MAXU), ("act_gear", real * MAXU), ("act_ctrlrange", (real * 2) * MAXU),
+            ("nexclude", C.c_int), ("exclude", (C.c_int * 2) * 16),
+            ("timestep", real), ("gravity", real * 3), ("tolerance", real),
+            ("iterations", C.c_int),
+            ("solref", real * 2), ("solimp", real * 5),
+        ]
+    _Spec.__name__ = _Spec.__qualname__ = name
+    return _Spec
+
+
+Spec = _spec_type(C.c_double, "Spec")            # liboracle.so
+Spec32 = _spec_type(C.c_float, "Spec32")         # liboracle32.so (dmo_real = float)
+
+
+def build(force=False, dtype=64):
+    """Builds (when stale) and returns the path of the oracle of arithmetic type `dtype`: 64 -> liboracle.so, 32 -> liboracle32.so."""
+    so = os.path.join(_HERE, _REAL[int(dtype)][2])
     src = [os.path.join(_HERE, f) for f in ("dm_oracle.c", "dm_oracle.h")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
+        subprocess.check_call(["make", "-C", _HERE, "-s", os.path.basename(so)])
     return so
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        L = C.CDLL(build())
+def lib(dtype=64):
+    """The oracle library of arithmetic type `dtype` (64: the reference; 32: the same code evaluated in float32).  Its C API speaks its
+    own type; the wrappers below convert at the boundary, so callers pass and receive float64 numpy arrays either way."""
+    dtype = int(dtype)
+    if dtype not in _LIBS:
+        real, npreal, _so = _REAL[dtype]
+        L = C.CDLL(build(dtype=dtype))
+        assert L.dmo_sizeof_real() == C.sizeof(real)
+        L.dtype, L.real, L.npreal, L.rp = dtype, real, npreal, C.POINTER(real)
         L.dmo_model_new.restype = C.c_void_p
         L.dmo_model_new.argtypes = [C.c_void_p]
         L.dmo_model_free.argtypes = [C.c_void_p]
@@ -61,55 +77,73 @@ def lib():
         L.dmo_forward.argtypes = [C.c_void_p, C.c_void_p]
         L.dmo_step.argtypes = [C.c_void_p, C.c_void_p]
         L.dmo_humanoid_spec.argtypes = [C.c_void_p]
-        dp = C.POINTER(C.c_double)
+        dp = L.rp
         L.dmo_model_get.argtypes = [C.c_void_p, C.c_char_p, dp, C.c_int]
-        L.dmo_model_set.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+        L.dmo_model_set.argtypes = [C.c_void_p, C.c_char_p, real]
         L.dmo_data_get.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, dp, C.c_int]
         L.dmo_data_set.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, dp, C.c_int]
         L.dmo_get_obs.argtypes = [C.c_void_p, C.c_void_p, dp]
-        L.dmo_com_z.restype = C.c_double
+        L.dmo_com_z.restype = real
         L.dmo_com_z.argtypes = [C.c_void_p, C.c_void_p]
         L.dmo_is_done.argtypes = [C.c_void_p, C.c_void_p]
         L.dmo_set_state.argtypes = [C.c_void_p, C.c_void_p, dp, dp]
-        L.dmo_config_reward.restype = C.c_double
+        L.dmo_config_reward.restype = real
         L.dmo_config_reward.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_int, C.POINTER(C.c_int)]
         L.dmo_env_step.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_int, C.c_int, dp, C.c_int,
                                    C.POINTER(C.c_int), C.c_int, dp, dp, C.POINTER(C.c_int)]
         L.dmo_imitation_features.argtypes = [C.c_void_p, dp, dp, dp, dp]
-        L.dmo_imitation_reward.restype = C.c_double
-        L.dmo_imitation_reward.argtypes = [C.c_void_p, dp, dp, dp, C.c_double, C.c_double, dp]
+        L.dmo_imitation_reward.restype = real
+        L.dmo_imitation_reward.argtypes = [C.c_void_p, dp, dp, dp, real, real, dp]
         L.dmo_env_step_imitation.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), dp, dp, C.POINTER(C.c_int)]
         L.dmo_batch_step.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, dp, C.c_int, dp, dp,
                                      C.POINTER(C.c_ubyte), C.c_int]
         L.dmo_batch_step_imitation.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, dp, C.c_int, dp, C.c_int, dp,
                                                C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp, C.POINTER(C.c_ubyte), C.c_int]
-        L.dmo_v1_reward.restype = C.c_double
+        L.dmo_v1_reward.restype = real
         L.dmo_v1_reward.argtypes = [C.c_void_p, dp, dp, dp, dp, dp]
-        L.dmo_env_step_v1.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_int, dp, C.c_int, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, dp,
+        L.dmo_env_step_v1.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_int, dp, C.c_int, dp, real, C.POINTER(C.c_int), C.c_int, dp, dp,
                                       C.POINTER(C.c_int)]
         L.dmo_bench_rollout.restype = C.c_long
-        L.dmo_bench_rollout.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, C.c_double, C.c_ulonglong,
+        L.dmo_bench_rollout.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, real, C.c_ulonglong,
                                         C.c_int, C.POINTER(C.c_long), dp]
         L.dmo_narrow_cases.argtypes = [C.POINTER(C.c_longlong), C.c_int]
-        _LIB = L
-    return _LIB
+        _LIBS[dtype] = L
+    return _LIBS[dtype]
 
 
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+def _in(L, x):
+    """-> (array of the library's type — keep it alive over the call —, pointer)"""
+    a = np.ascontiguousarray(x, dtype=L.npreal)
+    return a, a.ctypes.data_as(L.rp)
 
 
-def humanoid_spec():
-    s = Spec()
-    lib().dmo_humanoid_spec(C.byref(s))
+def _out(L, *shape):
+    a = np.zeros(shape, dtype=L.npreal)
+    return a, a.ctypes.data_as(L.rp)
+
+
+def _f64(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def humanoid_spec(dtype=64):
+    s = (Spec32 if int(dtype) == 32 else Spec)()
+    lib(dtype).dmo_humanoid_spec(C.byref(s))
     return s
 
 
 class Model(object):
-    def __init__(self, spec=None):
+    def __init__(self, spec=None, dtype=64):
+        """dtype: the oracle build that owns the model (64, or 32: liboracle32.so); a `Spec32` selects the float32 build by itself."""
+        if isinstance(spec, Spec32):
+            dtype = 32
+        self.dtype = int(dtype)
+        self.L = lib(self.dtype)
+        if spec is not None and not isinstance(spec, Spec32 if self.dtype == 32 else Spec):
+            raise TypeError("oracle: a dtype=%d model takes a %s" % (self.dtype, "Spec32" if self.dtype == 32 else "Spec"))
         self._spec = spec
-        self.h = lib().dmo_model_new(C.byref(spec) if spec is not None else None)
+        self.h = self.L.dmo_model_new(C.byref(spec) if spec is not None else None)
         if not self.h:
             raise RuntimeError("oracle: model compile failed")
         self.nq = int(self.get("nq")[0]); self.nv = int(self.get("nv")[0]); self.nu = int(self.get("nu")[0])
@@ -117,17 +151,17 @@ class Model(object):
 
     def __del__(self):
         if getattr(self, "h", None) and lib is not None:      # `lib` is None during interpreter shutdown
-            lib().dmo_model_free(self.h); self.h = None
+            self.L.dmo_model_free(self.h); self.h = None
 
     def get(self, field, maxn=8192):
-        buf = np.zeros(maxn)
-        n = lib().dmo_model_get(self.h, field.encode(), _dp(buf), maxn)
+        buf, p = _out(self.L, maxn)
+        n = self.L.dmo_model_get(self.h, field.encode(), p, maxn)
         if n < 0:
             raise KeyError(field)
-        return buf[:n].copy()
+        return _f64(buf[:n])
 
     def set(self, field, value):
-        if lib().dmo_model_set(self.h, field.encode(), float(value)) != 0:
+        if self.L.dmo_model_set(self.h, field.encode(), float(value)) != 0:
             raise KeyError(field)
 
 
@@ -136,121 +170,124 @@ class Data(object):
 
     def __init__(self, model):
         self.m = model
-        self.h = lib().dmo_data_create(model.h)
+        self.L = model.L
+        self.h = self.L.dmo_data_create(model.h)
 
     def __del__(self):
         if getattr(self, "h", None) and lib is not None:      # `lib` is None during interpreter shutdown
-            lib().dmo_data_destroy(self.h); self.h = None
+            self.L.dmo_data_destroy(self.h); self.h = None
 
     def get(self, field, maxn=70000):
-        buf = np.zeros(maxn)
-        n = lib().dmo_data_get(self.m.h, self.h, field.encode(), _dp(buf), maxn)
+        buf, p = _out(self.L, maxn)
+        n = self.L.dmo_data_get(self.m.h, self.h, field.encode(), p, maxn)
         if n < 0:
             raise KeyError(field)
-        return buf[:n].copy()
+        return _f64(buf[:n])
 
     def set(self, field, value):
-        a = np.ascontiguousarray(np.atleast_1d(value), dtype=np.float64)
-        if lib().dmo_data_set(self.m.h, self.h, field.encode(), _dp(a), a.size) != 0:
+        a, p = _in(self.L, np.atleast_1d(value))
+        if self.L.dmo_data_set(self.m.h, self.h, field.encode(), p, a.size) != 0:
             raise KeyError(field)
 
     def reset(self):
-        lib().dmo_reset_data(self.m.h, self.h)
+        self.L.dmo_reset_data(self.m.h, self.h)
 
     def forward(self):
-        lib().dmo_forward(self.m.h, self.h)
+        self.L.dmo_forward(self.m.h, self.h)
 
     def step(self):
-        lib().dmo_step(self.m.h, self.h)
+        self.L.dmo_step(self.m.h, self.h)
 
     def set_state(self, qpos, qvel):
-        q = np.ascontiguousarray(qpos, dtype=np.float64); v = np.ascontiguousarray(qvel, dtype=np.float64)
-        lib().dmo_set_state(self.m.h, self.h, _dp(q), _dp(v))
+        (_q, qp), (_v, vp) = _in(self.L, qpos), _in(self.L, qvel)
+        self.L.dmo_set_state(self.m.h, self.h, qp, vp)
 
     def obs(self):
-        o = np.zeros(56); lib().dmo_get_obs(self.m.h, self.h, _dp(o)); return o
+        o, p = _out(self.L, 56); self.L.dmo_get_obs(self.m.h, self.h, p); return _f64(o)
 
     def com_z(self):
-        return lib().dmo_com_z(self.m.h, self.h)
+        return float(self.L.dmo_com_z(self.m.h, self.h))
 
     def is_done(self):
-        return bool(lib().dmo_is_done(self.m.h, self.h))
+        return bool(self.L.dmo_is_done(self.m.h, self.h))
 
     def config_reward(self, data_config, idx_curr):
-        cfg = np.ascontiguousarray(data_config, dtype=np.float64)
+        cfg, cp = _in(self.L, data_config)
         i = C.c_int(int(idx_curr))
-        r = lib().dmo_config_reward(self.m.h, self.h, _dp(cfg), cfg.shape[0], C.byref(i))
-        return r, i.value
+        r = self.L.dmo_config_reward(self.m.h, self.h, cp, cfg.shape[0], C.byref(i))
+        return float(r), i.value
 
     def env_step(self, action, n_substeps=1, reward_mode=0, data_config=None, idx_curr=0, idx_init=0):
-        a = np.ascontiguousarray(action, dtype=np.float64)
-        cfg = np.zeros((1, 35)) if data_config is None else np.ascontiguousarray(data_config, dtype=np.float64)
-        o = np.zeros(56); r = C.c_double(0); dn = C.c_int(0); ic = C.c_int(int(idx_curr))
-        rr = np.zeros(1)
-        lib().dmo_env_step(self.m.h, self.h, _dp(a), n_substeps, reward_mode, _dp(cfg), cfg.shape[0],
-                           C.byref(ic), int(idx_init), _dp(o), _dp(rr), C.byref(dn))
-        return o, float(rr[0]), bool(dn.value), ic.value
+        L = self.L
+        _a, ap = _in(L, action)
+        cfg, cp = _in(L, np.zeros((1, 35)) if data_config is None else data_config)
+        (o, op), (rr, rp) = _out(L, 56), _out(L, 1)
+        dn = C.c_int(0); ic = C.c_int(int(idx_curr))
+        L.dmo_env_step(self.m.h, self.h, ap, n_substeps, reward_mode, cp, cfg.shape[0], C.byref(ic), int(idx_init), op, rp, C.byref(dn))
+        return _f64(o), float(rr[0]), bool(dn.value), ic.value
 
 
 def imitation_features(model, qpos, qvel, params):
     """Feature row (112) of a state: code.md:1017-1143 reward inputs; layout in deepmimic_mujoco_amd/imitation.py."""
-    q = np.ascontiguousarray(qpos, dtype=np.float64); v = np.ascontiguousarray(qvel, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64); f = np.zeros(112)
-    lib().dmo_imitation_features(model.h, _dp(q), _dp(v), _dp(p), _dp(f))
-    return f
+    L = model.L
+    (_q, qp), (_v, vp), (_p, pp), (f, fp) = _in(L, qpos), _in(L, qvel), _in(L, params), _out(L, 112)
+    L.dmo_imitation_features(model.h, qp, vp, pp, fp)
+    return _f64(f)
 
 
 def imitation_reward(model, f0, f1, params, shift=(0.0, 0.0)):
-    a = np.ascontiguousarray(f0, dtype=np.float64); b = np.ascontiguousarray(f1, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64); t = np.zeros(5)
-    r = lib().dmo_imitation_reward(model.h, _dp(a), _dp(b), _dp(p), float(shift[0]), float(shift[1]), _dp(t))
-    return float(r), t
+    L = model.L
+    (_a, ap), (_b, bp), (_p, pp), (t, tp) = _in(L, f0), _in(L, f1), _in(L, params), _out(L, 5)
+    r = L.dmo_imitation_reward(model.h, ap, bp, pp, float(shift[0]), float(shift[1]), tp)
+    return float(r), _f64(t)
 
 
 def env_step_imitation(model, data, action, n_substeps, table, params, idx_curr, cycle):
     """-> (obs, reward, done, idx_curr, cycle)"""
-    a = np.ascontiguousarray(action, dtype=np.float64); tb = np.ascontiguousarray(table, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64)
-    o = np.zeros(56); rr = np.zeros(1); dn = C.c_int(0); ic = C.c_int(int(idx_curr)); cy = C.c_int(int(cycle))
-    lib().dmo_env_step_imitation(model.h, data.h, _dp(a), int(n_substeps), _dp(tb), tb.shape[0], _dp(p), C.byref(ic), C.byref(cy),
-                                 _dp(o), _dp(rr), C.byref(dn))
-    return o, float(rr[0]), bool(dn.value), ic.value, cy.value
+    L = model.L
+    (_a, ap), (tb, tbp), (_p, pp) = _in(L, action), _in(L, table), _in(L, params)
+    (o, op), (rr, rp) = _out(L, 56), _out(L, 1)
+    dn = C.c_int(0); ic = C.c_int(int(idx_curr)); cy = C.c_int(int(cycle))
+    L.dmo_env_step_imitation(model.h, data.h, ap, int(n_substeps), tbp, tb.shape[0], pp, C.byref(ic), C.byref(cy), op, rp, C.byref(dn))
+    return _f64(o), float(rr[0]), bool(dn.value), ic.value, cy.value
 
 
 def batch_step(model, datas, actions, n_substeps=1, nthreads=1):
+    L = model.L
     n = len(datas)
     arr = (C.c_void_p * n)(*[d.h for d in datas])
-    a = np.ascontiguousarray(actions, dtype=np.float64)
-    obs = np.zeros((n, 56)); rew = np.zeros(n); done = np.zeros(n, dtype=np.uint8)
-    lib().dmo_batch_step(model.h, arr, n, _dp(a), n_substeps, _dp(obs), _dp(rew),
-                         done.ctypes.data_as(C.POINTER(C.c_ubyte)), nthreads)
-    return obs, rew, done
+    _a, ap = _in(L, actions)
+    (obs, op), (rew, rp) = _out(L, n, 56), _out(L, n)
+    done = np.zeros(n, dtype=np.uint8)
+    L.dmo_batch_step(model.h, arr, n, ap, n_substeps, op, rp, done.ctypes.data_as(C.POINTER(C.c_ubyte)), nthreads)
+    return _f64(obs), _f64(rew), done
 
 
 def batch_step_imitation(model, datas, actions, n_substeps, table, params, idx_curr, cycle, nthreads=1):
     """OpenMP loop of `env_step_imitation`; `idx_curr` / `cycle` (int32 [n]) are advanced in place."""
+    L = model.L
     n = len(datas)
     arr = (C.c_void_p * n)(*[d.h for d in datas])
-    a = np.ascontiguousarray(actions, dtype=np.float64); tb = np.ascontiguousarray(table, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64)
+    (_a, ap), (tb, tbp), (_p, pp) = _in(L, actions), _in(L, table), _in(L, params)
     assert idx_curr.dtype == np.int32 and cycle.dtype == np.int32 and idx_curr.flags.c_contiguous and cycle.flags.c_contiguous
-    obs = np.zeros((n, 56)); rew = np.zeros(n); done = np.zeros(n, dtype=np.uint8)
-    lib().dmo_batch_step_imitation(model.h, arr, n, _dp(a), int(n_substeps), _dp(tb), tb.shape[0], _dp(p),
-                                   idx_curr.ctypes.data_as(C.POINTER(C.c_int)), cycle.ctypes.data_as(C.POINTER(C.c_int)),
-                                   _dp(obs), _dp(rew), done.ctypes.data_as(C.POINTER(C.c_ubyte)), int(nthreads))
-    return obs, rew, done
+    (obs, op), (rew, rp) = _out(L, n, 56), _out(L, n)
+    done = np.zeros(n, dtype=np.uint8)
+    L.dmo_batch_step_imitation(model.h, arr, n, ap, int(n_substeps), tbp, tb.shape[0], pp,
+                               idx_curr.ctypes.data_as(C.POINTER(C.c_int)), cycle.ctypes.data_as(C.POINTER(C.c_int)),
+                               op, rp, done.ctypes.data_as(C.POINTER(C.c_ubyte)), int(nthreads))
+    return _f64(obs), _f64(rew), done
 
 
 def bench_rollout(model, datas, steps, data_config, data_vel, table=None, params=None, sigma=0.9, seed=0, nthreads=1):
     """bench.py's cpu_baseline workload run entirely in C (see dmo_bench_rollout) -> (env_steps, episodes_ended, reward_sum)."""
+    L = model.L
     n = len(datas)
     arr = (C.c_void_p * n)(*[d.h for d in datas])
-    cfg = np.ascontiguousarray(data_config, dtype=np.float64); vel = np.ascontiguousarray(data_vel, dtype=np.float64)
-    tb = None if table is None else np.ascontiguousarray(table, dtype=np.float64)
-    p = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
-    nd = C.c_long(0); rs = np.zeros(1)
-    tot = lib().dmo_bench_rollout(model.h, arr, n, int(steps), _dp(cfg), _dp(vel), cfg.shape[0], None if tb is None else _dp(tb),
-                                  None if p is None else _dp(p), float(sigma), int(seed), int(nthreads), C.byref(nd), _dp(rs))
+    (cfg, cp), (_v, vp) = _in(L, data_config), _in(L, data_vel)
+    _tb, tbp = (None, None) if table is None else _in(L, table)
+    _p, pp = (None, None) if params is None else _in(L, params)
+    nd = C.c_long(0); rs, rsp = _out(L, 1)
+    tot = L.dmo_bench_rollout(model.h, arr, n, int(steps), cp, vp, cfg.shape[0], tbp, pp, float(sigma), int(seed), int(nthreads), C.byref(nd), rsp)
     return int(tot), int(nd.value), float(rs[0])
 
 
@@ -259,24 +296,24 @@ NARROW_CASES = ("box-box: separated", "box-box: edge-edge, 1 contact", "box-box:
                 "capsule-box: 1 contact, one end within reach", "capsule-box: 1 contact, both ends within reach", "capsule-box: 1 contact, axis through the interior")
 
 
-def narrow_cases(mode=-1):
+def narrow_cases(mode=-1, dtype=64):
     """Tallies of the narrow-phase cases of the oracle's two own routines (dm_oracle.c): mode 1 = reset + on, 0 = off, -1 = read."""
     out = (C.c_longlong * 10)()
-    lib().dmo_narrow_cases(out, int(mode))
+    lib(dtype).dmo_narrow_cases(out, int(mode))
     return np.array(list(out), dtype=np.int64)
 
 
 def v1_reward(model, f0, f1, f1v, params):
-    a = np.ascontiguousarray(f0, dtype=np.float64); b = np.ascontiguousarray(f1, dtype=np.float64); c = np.ascontiguousarray(f1v, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64); t = np.zeros(3)
-    return float(lib().dmo_v1_reward(model.h, _dp(a), _dp(b), _dp(c), _dp(p), _dp(t))), t
+    L = model.L
+    (_a, ap), (_b, bp), (_c, cp), (_p, pp), (t, tp) = _in(L, f0), _in(L, f1), _in(L, f1v), _in(L, params), _out(L, 3)
+    return float(L.dmo_v1_reward(model.h, ap, bp, cp, pp, tp)), _f64(t)
 
 
 def env_step_v1(model, data, action, n_substeps, table, params, mocap_dt, idx_curr, idx_init):
     """dp_env_v1's step (reward mode 4) -> (obs, reward, done, idx_curr)"""
-    a = np.ascontiguousarray(action, dtype=np.float64); tb = np.ascontiguousarray(table, dtype=np.float64)
-    p = np.ascontiguousarray(params, dtype=np.float64)
-    o = np.zeros(56); rr = np.zeros(1); dn = C.c_int(0); ic = C.c_int(int(idx_curr))
-    lib().dmo_env_step_v1(model.h, data.h, _dp(a), int(n_substeps), _dp(tb), tb.shape[0], _dp(p), float(mocap_dt), C.byref(ic), int(idx_init),
-                          _dp(o), _dp(rr), C.byref(dn))
-    return o, float(rr[0]), bool(dn.value), ic.value
+    L = model.L
+    (_a, ap), (tb, tbp), (_p, pp) = _in(L, action), _in(L, table), _in(L, params)
+    (o, op), (rr, rp) = _out(L, 56), _out(L, 1)
+    dn = C.c_int(0); ic = C.c_int(int(idx_curr))
+    L.dmo_env_step_v1(model.h, data.h, ap, int(n_substeps), tbp, tb.shape[0], pp, float(mocap_dt), C.byref(ic), int(idx_init), op, rp, C.byref(dn))
+    return _f64(o), float(rr[0]), bool(dn.value), ic.value
