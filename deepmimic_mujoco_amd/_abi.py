@@ -11,6 +11,7 @@ import numpy as np
 ABI_VERSION = 9
 NBODY, NJNT, NQ, NV, NU, NGEOM, NOBS, MAXEFC = 14, 29, 35, 34, 28, 16, 56, 64
 NSTATE = 171   # DM_NSTATE: DeepMimic's state features (state_features.py has the layout)
+NTERMS = 28    # DM_NTERMS: the imitation reward's terms (imitation.py has the column offsets)
 DEBUG_DOUBLES = 34 * 34 + 34 * 3 + 42 + 3 + MAXEFC * (34 + 6)
 PTR_HOST, PTR_DEVICE = 0, 1
 FLAG_NO_CONTACT, FLAG_NO_LIMIT = 1, 2
@@ -116,7 +117,7 @@ LIB_PATH = os.environ.get("DMENV_LIB") or os.path.join(_HERE, "csrc", "libdmenv.
 EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_destroy", "dm_batch_create",
            "dm_batch_destroy", "dm_batch_set_stream", "dm_batch_set_option", "dm_batch_set_state", "dm_batch_reset",
            "dm_batch_step", "dm_batch_get_obs", "dm_batch_get", "dm_batch_set", "dm_batch_debug_forward",
-           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_truncations", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
+           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_imitation_terms", "dm_batch_truncations", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
            "dm_device_count"]
 _LIB = None
 
@@ -190,6 +191,7 @@ def load(dtype=64):
     L.dm_batch_render.argtypes = [vp, vp, vp, i32, C.POINTER(RenderDesc), vp, vp, vp, vp, i32]
     L.dm_batch_state_features.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32]
     L.dm_batch_floor_contacts.argtypes = [vp, vp, vp, i32, vp, i32]
+    L.dm_batch_imitation_terms.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32]
     L.dm_batch_truncations.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32]
     L.dm_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]
     L.dm_episode_scan.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]

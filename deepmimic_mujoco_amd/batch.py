@@ -19,7 +19,7 @@ _TORCH_DTYPE = {np.float64: "float64", np.float32: "float32", np.int32: "int32",
 
 
 def _view_args(ptr, n_batch, device, state, env_ids, outs, who):
-    """The arrays of a read-only view call (Batch.render, state_features, floor_contacts).  ptr: Batch._ptr; state: the optional explicit
+    """The arrays of a read-only view call (Batch.render, state_features, floor_contacts, imitation_terms).  ptr: Batch._ptr; state: the optional explicit
     state as (value, dtype, shape after n) entries, all given or all None; env_ids [n] or None; outs: the requested outputs as (given or None,
     dtype, shape after n).  n comes from the explicit state, else from env_ids, else it is the batch's.  One tensor among them makes the
     call a device call: missing outputs are then allocated on cuda:<device> and numpy inputs moved there; otherwise everything is numpy.
@@ -371,6 +371,23 @@ class Batch(object):
         n, (qp, ip), (op,), kind, _keep, (out,) = _view_args(self._ptr, self.n, self.device, [(qpos, np.float64, (A.NQ,))], env_ids, [(out, np.int32, ())],
                                                              "floor_contacts")
         A.check(self._L.dm_batch_floor_contacts(self._h, qp, ip, n, op, kind), self._L)
+        return out
+
+    def imitation_terms(self, qpos=None, qvel=None, frame=None, cycle=None, env_ids=None, out=None):
+        """The five terms of the "imitation" reward through dm_batch_imitation_terms (one launch; imitation.py has the columns): [n, 28] float64 —
+        the errors [0:5], the weighted terms [5:10], their sum (the reward) [10], each joint group's share of the pose error [11:24], each end
+        effector's squared distance [24:28].  Default: the batch's current state and cursors of every environment, or of `env_ids` [n] — reward mode 3
+        only; right after a step column 10 is that step's reward, except where the step reset the environment (the row is then the fresh episode's).
+        With qpos [n,35], qvel [n,34] and frame [n] int32 (all three; cycle [n] int32 optional, env_ids must then be None): those states against
+        those rows of the imitation table, in any reward mode; a frame outside the table raises for numpy arrays and gives a row of NaN for device
+        tensors.  Arrays as for `state_features`.  Reads the batch, changes nothing."""
+        explicit = [x is not None for x in (qpos, qvel, frame)]
+        if (any(explicit) or cycle is not None) and not all(explicit):
+            raise ValueError("an explicit state needs qpos, qvel and frame")
+        f64, i32 = np.float64, np.int32
+        n, (qp, vp, fp, cp, ip), (op,), kind, _keep, (out,) = _view_args(self._ptr, self.n, self.device, [(qpos, f64, (A.NQ,)), (qvel, f64, (A.NV,)), (frame, i32, ()),
+                                                                          (cycle, i32, ())], env_ids, [(out, f64, (A.NTERMS,))], "imitation_terms")
+        A.check(self._L.dm_batch_imitation_terms(self._h, qp, vp, fp, cp, ip, n, op, kind), self._L)
         return out
 
     def truncations(self, clear=True, out=None, device=None):

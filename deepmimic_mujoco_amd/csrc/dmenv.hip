@@ -19,7 +19,9 @@ using namespace dm;
 #include "render_kernel.h"
 #include "state_kernel.h"
 #include "term_kernel.h"
+#include "terms_kernel.h"
 static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
+static_assert(DM_NTERMS == IMIT_NTERMS, "include/dmenv.h documents the terms row: keep it in step with env_step.h imitation_reward");
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
               DM_PACKED_MAXCAND == SLOT_MAXCAND, "include/dmenv.h documents the packed path's capacities: keep it in step with slot_kernel.h");
 // ============================================ kernels ======================================================

@@ -306,8 +306,11 @@ DM_DEV R quat_diff_theta(const R* q0, const R* q1) {
 // axes in the parent frame): lane 0 root, lanes 1..12 joint groups; lanes 13..16 end effectors; lanes 0..33 again one dof
 // each for the linear momentum  p = sum_d qvel_d (m_sub(d) lin_d + ang_d x S_sub(d))  with the subtree mass / first moment the
 // composite-inertia pass has just left in LDS.  One acos, one exp per lane; no other transcendental.
-template <class R>
-DM_DEV R imitation_reward(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int lane, const LaneTopo& lt, const R* ref, R shx, R shy) {
+// PARTS (terms_kernel.h, the read-only view): the lanes also leave the row of include/dmenv.h DM_NTERMS in `parts` (LDS, 28 numbers; the caller
+// syncs before it reads them).  The step kernels instantiate PARTS = false, whose code is what it was before the flag existed.
+constexpr int IMIT_NTERMS = 28, IMIT_O_ERR = 0, IMIT_O_TERM = 5, IMIT_O_SUM = 10, IMIT_O_JOINT = 11, IMIT_O_EE = 24;
+template <class R, bool PARTS = false>
+DM_DEV R imitation_reward(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int lane, const LaneTopo& lt, const R* ref, R shx, R shy, R* parts = nullptr) {
   R qloc[4], aloc[3][3];
   stage_kinematics(M, s, lane, lt, qloc, aloc);          // ends with a sync
   const R* P = B.imit_pdev;                               // device copy of the parameter block (per-lane indexing)
@@ -365,6 +368,10 @@ DM_DEV R imitation_reward(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
     cross3(axs, cd, cb + 6);
     mx = qd * (ms * cd[3] + axs[0]); my = qd * (ms * cd[4] + axs[1]); mz = qd * (ms * cd[5] + axs[2]);
   }
+  if constexpr (PARTS) {                                  // weight-slot order: the 12 joint groups, then the root; then the four end effectors
+    if (lane < 13) parts[IMIT_O_JOINT + (lane == 0 ? 12 : lane - 1)] = pose;
+    else if (lane < 17) parts[IMIT_O_EE + (lane - 13)] = eff;
+  }
   pose = dmw::wave_sum(pose); vel = dmw::wave_sum(vel); eff = dmw::wave_sum(eff) / 4; root = dmw::bcast(root, 0);
   mx = dmw::wave_sum(mx) / M.total_mass; my = dmw::wave_sum(my) / M.total_mass; mz = dmw::wave_sum(mz) / M.total_mass;
   const R dc[3] = {ref[109] - mx, ref[110] - my, ref[111] - mz};
@@ -374,6 +381,12 @@ DM_DEV R imitation_reward(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
   const R wgt = lane == 0 ? R(0.5) : lane == 1 ? R(0.05) : lane == 2 ? R(0.15) : lane == 3 ? R(0.2) : R(0.1);
   R term = 0;
   if (lane < 5) term = wgt * exp_once(arg);
+  if constexpr (PARTS) {
+    if (lane < 5) { parts[IMIT_O_ERR + lane] = lane == 0 ? pose : lane == 1 ? vel : lane == 2 ? eff : lane == 3 ? root : com; parts[IMIT_O_TERM + lane] = term; }
+    const R sum = dmw::wave_sum(term);
+    if (lane == 0) parts[IMIT_O_SUM] = sum;
+    return sum;
+  }
   return dmw::wave_sum(term);
 }
 

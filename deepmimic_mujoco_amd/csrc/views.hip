@@ -1,6 +1,6 @@
-// views.hip — read-only views of a batch's environments: images (dm_batch_render), DeepMimic's state features (dm_batch_state_features) and the
-// floor-contact query (dm_batch_floor_contacts), DESIGN.md section 9.  Host side only: the kernels (render_kernel.h, state_kernel.h, term_kernel.h)
-// are compiled in dmenv.hip's unit, which see.  Every view is: view_args, its own argument rules, view_enter, the arrays it declares on a Stage,
+// views.hip — read-only views of a batch's environments: images (dm_batch_render), DeepMimic's state features (dm_batch_state_features), the
+// floor-contact query (dm_batch_floor_contacts) and the imitation reward's terms (dm_batch_imitation_terms), DESIGN.md section 9.  Host side only: the
+// kernels (render_kernel.h, state_kernel.h, term_kernel.h, terms_kernel.h) are compiled in dmenv.hip's unit, which see.  Every view is: view_args, its own argument rules, view_enter, the arrays it declares on a Stage,
 // commit(), its launches on ptr(index), finish().
 #define DM_NO_LAUNCH_KERNELS
 #include <cmath>
@@ -21,6 +21,9 @@ __global__ void k_render_rays(const dmr::ViewRec* __restrict__ rec, dmr::Params 
 __global__ void k_state_features(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const double* __restrict__ qpos_ext,
                                  const double* __restrict__ qvel_ext, const double* __restrict__ phase_ext, const int* __restrict__ env_ids,
                                  Ext* __restrict__ out);
+__global__ void k_imitation_terms(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const double* __restrict__ qpos_ext,
+                                  const double* __restrict__ qvel_ext, const int* __restrict__ frame_ext, const int* __restrict__ cycle_ext,
+                                  const int* __restrict__ env_ids, Ext* __restrict__ out);
 __global__ void k_floor_contacts(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos, const double* __restrict__ qpos_ext,
                                  const int* __restrict__ env_ids, int* __restrict__ out);
 
@@ -151,6 +154,29 @@ extern "C" int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const in
   if ((rc = st.commit())) return rc;
   hipLaunchKernelGGL(k_floor_contacts, dim3(n), dim3(64), 0, b->stream, b->d_model, (const Real*)b->B.qpos, st.ptr<const double>(i_q),
                      st.ptr<const int>(i_id), st.ptr<int>(i_o));
+  HIPCHK(hipGetLastError());
+  return st.finish();
+}
+
+// ------------------------------------------------------------------ the imitation reward's five terms (terms_kernel.h)
+extern "C" int dm_batch_imitation_terms(dm_batch* b, const double* qpos, const double* qvel, const int32_t* frame, const int32_t* cycle,
+                                        const int32_t* env_ids, int32_t n, double* out, int32_t kind) {
+  const char* who = "dm_batch_imitation_terms";
+  int rc;
+  const bool explicit_state = qpos || qvel || frame || cycle;
+  if ((rc = view_args(b, out != nullptr, kind, n, explicit_state, "a state", env_ids, who))) return rc;
+  if (explicit_state && !(qpos && qvel && frame)) return fail(DM_EINVAL, "dm_batch_imitation_terms: an explicit state needs qpos, qvel and frame");
+  if (!b->B.imit_table) return fail(DM_EINVAL, "dm_batch_imitation_terms: the mocap has no imitation table (dm_mocap_set_imitation)");
+  if (!explicit_state && b->B.reward_mode != REW_IMITATION) return fail(DM_EINVAL, "dm_batch_imitation_terms: the batch's own cursors name the compared row in reward mode 3 only");
+  if (explicit_state && kind == DM_PTR_HOST)
+    for (int i = 0; i < n; i++) if (frame[i] < 0 || frame[i] >= b->B.n_frames) return fail(DM_EINVAL, "dm_batch_imitation_terms: frame out of range");
+  if ((rc = view_enter(b, env_ids, n, kind == DM_PTR_HOST, who))) return rc;
+  Stage st(b, kind, who);
+  const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_f = st.in(frame, (size_t)n * sizeof(int32_t));
+  const int i_c = st.in(cycle, (size_t)n * sizeof(int32_t)), i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NTERMS * sizeof(double));
+  if ((rc = st.commit())) return rc;
+  hipLaunchKernelGGL(k_imitation_terms, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                     st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());
   return st.finish();
 }

@@ -191,6 +191,35 @@ class DPEnv(object):
     def close(self):
         if self._batch is not None:
             self._batch.close(); self._batch = None
+        if getattr(self, "_terms_batch", None) is not None:
+            self._terms_batch.close(); self._terms_batch = None
+
+    def reward_terms(self, frame=None, cycle=0):
+        """The 5-term imitation reward (imitation.py) of the current state against mocap frame `frame` (default: the frame the cursor is at, as the
+        "deepmimic" observation's phase counts it), the reference's root advanced by `cycle` completed cycles, by name: the five errors under
+        imitation.TERM_NAMES, "reward", and the dicts "terms" (the weighted terms), "joints" (each joint group's share of the pose error, by body
+        name, and "root") and "end_effectors" (squared distances).  This class steps with the reference's rewards, so the call is the explicit form of
+        Batch.imitation_terms on a one-env batch of its own that carries the clip's feature table, made on the first call."""
+        from .imitation import END_EFFECTORS, TERM_NAMES, ImitationSpec, O_TERM_ERR, O_TERM_VALUE, O_TERM_REWARD, O_TERM_JOINT, O_TERM_ENDEFF
+        if getattr(self, "_terms_batch", None) is None or self._terms_clip is not self.mocap.data_config:
+            if getattr(self, "_terms_batch", None) is not None:
+                self._terms_batch.close()
+            self._terms_spec = ImitationSpec(self._cm)
+            self._terms_batch = Batch(self._cm, self.mocap.data_config, self.mocap.data_vel, 1, device=self._device, mocap_dt=float(self.mocap_dt),
+                                      imitation=self._terms_spec.table_for(self.mocap))
+            self._terms_clip = self.mocap.data_config
+        if frame is None:
+            shifted = self._reward_mode in (REWARD_MODES["v2-pose"], REWARD_MODES["v1-quat"])
+            frame = (max(self.idx_curr, 0) + (self.idx_init if shifted else 0)) % self.mocap_data_len
+        row = self._terms_batch.imitation_terms(qpos=self._batch.get(A.F_QPOS), qvel=self._batch.get(A.F_QVEL), frame=np.array([int(frame)], dtype=np.int32),
+                                                cycle=np.array([int(cycle)], dtype=np.int32))[0]
+        out = {name: float(row[O_TERM_ERR + k]) for k, name in enumerate(TERM_NAMES)}
+        out["reward"] = float(row[O_TERM_REWARD])
+        out["terms"] = {name: float(row[O_TERM_VALUE + k]) for k, name in enumerate(TERM_NAMES)}
+        names = [self._cm.body_names[b] for b in self._terms_spec.bodies] + ["root"]
+        out["joints"] = {name: float(row[O_TERM_JOINT + k]) for k, name in enumerate(names)}
+        out["end_effectors"] = {name: float(row[O_TERM_ENDEFF + k]) for k, (name, _off) in enumerate(END_EFFECTORS)}
+        return out
 
     def render(self, mode="human", width=500, height=500, camera_name=None):
         """gym MujocoEnv.render: "rgb_array" -> uint8 [height, width, 3], "depth_array" -> float32 [height, width] (distance
@@ -380,8 +409,14 @@ class DPVecEnv(object):
 
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
-                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0):
-        """truncation_log: capacity in records of the truncation log (DM_OPT_TRUNCATION_LOG; 0: off): with `max_episode_steps`, the state of every episode that
+                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False):
+        """reward_terms (reward="imitation" only, else ValueError): after every `step` one more launch (Batch.imitation_terms) takes the reward the step
+        returned apart, and `last_reward_terms` is the [N, 28] float64 rows (imitation.py has the columns: the five errors, the five weighted terms, their
+        sum — the step's reward —, the joint groups' shares of the pose error, the end effectors' distances), numpy or device tensor like the step's
+        outputs and overwritten by the next step.  With `autoreset`, the row of an environment the step ended is NaN: the step kernel has already
+        replaced that state by the fresh episode's.  Off (default): nothing is launched or allocated and `last_reward_terms` stays None;
+        `reward_terms()` queries the current states either way.
+        truncation_log: capacity in records of the truncation log (DM_OPT_TRUNCATION_LOG; 0: off): with `max_episode_steps`, the state of every episode that
         the time limit alone ends is kept for `truncations()` before auto-reset overwrites it — a truncation is not a failure, and a learner bootstraps the
         value there (rollout.SegmentCollector(bootstrap_time_limit=True) sizes and reads the log itself).
         fall_contact_bodies: DeepMimic's early termination by fall contact — a set name of termination.FALL_BODY_SETS ("deepmimic": every body but the two
@@ -418,6 +453,11 @@ class DPVecEnv(object):
         self.obs_mode = obs_mode
         self._obs_width = obs_width(obs_mode)
         self._ob56 = None
+        if reward_terms and reward != "imitation":
+            raise ValueError("reward_terms=True takes the \"imitation\" reward apart: it needs reward=\"imitation\", not %r" % (reward,))
+        self._reward_terms = bool(reward_terms)
+        self._autoreset = autoreset not in (None, "none")
+        self.last_reward_terms = None
         self.mocap = MocapDM()
         self.mocap.load_mocap(motion)
         self.mocap_dt = self.mocap.dt
@@ -536,6 +576,30 @@ class DPVecEnv(object):
             b.step(actions, self.frame_skip, (o56, rew, done))
         return b.state_features(obs), rew, done
 
+    def _step_terms(self, rew, done):
+        """reward_terms=True: the rows of the step that has just run, into a buffer of the kind of the step's outputs; NaN where the step reset the env"""
+        buf = self.last_reward_terms
+        on_device = type(rew).__module__.startswith("torch")
+        if buf is None or type(buf) is not type(rew) or getattr(buf, "device", None) != getattr(rew, "device", None):
+            if on_device:
+                import torch
+                buf = torch.empty((self.num_envs, A.NTERMS), dtype=torch.float64, device=rew.device)
+            else:
+                buf = np.empty((self.num_envs, A.NTERMS))
+        self._batch.imitation_terms(out=buf)
+        if self._autoreset:
+            if on_device:
+                buf.masked_fill_(done.to(dtype=buf.dtype)[:, None] != 0, float("nan"))
+            else:
+                buf[np.asarray(done) != 0] = np.nan
+        self.last_reward_terms = buf
+
+    def reward_terms(self, env_ids=None, out=None):
+        """[n, 28] float64: the "imitation" reward's terms (imitation.py has the columns) of the environments' CURRENT states against the frame their
+        cursors name — after a step, the step's reward taken apart; for an environment the step reset, the fresh episode's state against the frame it
+        was drawn at.  env_ids [n]: a subset (default: all).  reward="imitation" only (Batch.imitation_terms)."""
+        return self._batch.imitation_terms(env_ids=env_ids, out=out)
+
     def step_async(self, actions):
         self._pending = actions
 
@@ -547,6 +611,8 @@ class DPVecEnv(object):
         self._pending = None
         if getattr(self._batch, "_queue_refs", None) is not None:
             self._batch.join()      # OPT_STEP_QUEUE: the call was only queued, and what this method returns is read in stream order
+        if self._reward_terms:
+            self._step_terms(rew, done)
         # `infos`: one dict per env (src/utils/vec_env/dummy_vec_env.py:45-56).  This env never puts anything into them, so the list is
         # built once and handed out again while every dict is still empty (building 4 096 dicts per step cost more than the step's
         # launch); a caller that writes into one (bench/monitor.py:73-74 does, at episode ends) gets fresh dicts from the next step on.

@@ -256,7 +256,7 @@ class ExpertDataset:
 def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4, timesteps_per_batch=1024, max_iters=0, max_timesteps=0,
           max_seconds=0, entcoeff=0.0, max_kl=0.01, cg_iters=10, cg_damping=0.1, gamma=0.995, lam=0.97, vf_iters=5, vf_stepsize=1e-3,
           callback=None, log=print, group=None, log_dir=None, fused=None, seed=0, algo="trpo", ppo_kwargs=None, bootstrap_time_limit=False,
-          **learner_kwargs):
+          log_reward_terms=False, **learner_kwargs):
     """`learn()` of src/gail.py:112-343 (hyper-parameters as its `train()` passes them) over a DPVecEnv (autoreset="init") and an MlpPolicy.
     One iteration: g_step times a segment rewarded by `reward_giver` and a TRPO update on it (trpo.TrpoLearner), then the D update on the
     LAST segment's (ob, ac): one `expert.get_next_batch(len(ob))` whose result is dropped, then for each of the d_step minibatches of
@@ -268,7 +268,9 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
     algo="ppo" (the reference's --algo, src/gail.py:394): the G updates are ppo.PpoLearner's, with gamma, lam, entcoeff, seed and `ppo_kwargs`
     (its linear schedule over max_timesteps when that is the stopping rule, else a constant one); the TRPO arguments are then unused.
     bootstrap_time_limit: as in trpo.learn — the value bootstrap where the time limit ends an episode, on the discriminator's rewards like every other
-    row; adds TruncThisIter (of the last segment, like the episode statistics)."""
+    row; adds TruncThisIter (of the last segment, like the episode statistics).
+    log_reward_terms (the env has reward="imitation"): as in trpo.learn — ErrPose, ErrVel, ErrEndEff, ErrRoot, ErrCom of the states the last segment ends in,
+    after the keys above; off: keys and columns unchanged."""
     from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     from .rollout import can_fuse, traj_segment_generator
@@ -286,7 +288,7 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
     d_adam.sync()
     use_fused = can_fuse(pi, env) if fused is None else bool(fused)
     seg_gen = traj_segment_generator(pi, env, timesteps_per_batch, stochastic=True, fused=use_fused, reward_giver=reward_giver,
-                                     bootstrap_time_limit=bootstrap_time_limit)
+                                     bootstrap_time_limit=bootstrap_time_limit, reward_terms=log_reward_terms)
     d_gen = torch.Generator(device=pi.device)
     d_gen.manual_seed(int(seed) + 1)
 
@@ -319,6 +321,7 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
             stats[name] = val
         # ---- episode statistics of the last segment (:345-364); the monitor file gets every segment's ----
         train_loop.truncation_stat(stats, seg)
+        train_loop.reward_terms_stat(stats, seg, group)
         episodes = {"EpLenMean": list(seg["ep_lens"]), "EpRewMean": list(seg["ep_rets"]), "EpTrueRewMean": list(seg["ep_true_rets"])}
         return stats, episodes, [(list(s["ep_true_rets"]), list(s["ep_lens"])) for s in segs], None
 
@@ -331,4 +334,5 @@ def learn(env, pi, reward_giver, expert, *, g_step=3, d_step=1, d_stepsize=3e-4,
                           max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir, empty_mean=float("nan"),
                           len_mean_iter=False,
                           columns=("optimgain", "meankl", "entloss", "surrgain", "entropy", "ev_tdlam_before") + LOSS_NAMES
-                          + ("EpLenMean", "EpRewMean", "EpTrueRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed"))
+                          + ("EpLenMean", "EpRewMean", "EpTrueRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed")
+                          + (train_loop.ERR_KEYS if log_reward_terms else ()))

@@ -40,6 +40,23 @@ END_EFFECTORS = (("right_ankle", (0.0, 0.0, 0.0)), ("left_ankle", (0.0, 0.0, 0.0
 # term weights and scales: code.md:1019-1037
 TERM_W = np.array([0.5, 0.05, 0.15, 0.2, 0.1])
 TERM_SCALE = np.array([2.0, 0.1, 40.0, 5.0, 10.0])
+# The terms row of `Batch.imitation_terms` (include/dmenv.h DM_NTERMS): the five errors, the five weighted terms w_k exp(-s_k e_k), their sum
+# (the reward of mode "imitation"), each joint group's share of the pose error (the 12 joint groups in model body order, then the root), each end
+# effector's squared distance to the reference's (END_EFFECTORS order)
+TERM_NAMES = ("pose", "velocity", "end_effector", "root", "com")
+NTERMS = 28
+O_TERM_ERR, O_TERM_VALUE, O_TERM_REWARD, O_TERM_JOINT, O_TERM_ENDEFF = 0, 5, 10, 11, 24
+
+
+def reward_from_errors(errors, weights=TERM_W, scales=TERM_SCALE):
+    """sum_k weights_k exp(-scales_k errors[..., k]): the reward from columns [0..5) of a terms row under a caller's own weights and scales
+    (the defaults give column 10 back).  errors: a numpy array or a torch tensor [..., 5]."""
+    if type(errors).__module__.startswith("torch"):
+        import torch
+        w = torch.as_tensor(np.asarray(weights, dtype=np.float64), dtype=errors.dtype, device=errors.device)
+        s = torch.as_tensor(np.asarray(scales, dtype=np.float64), dtype=errors.dtype, device=errors.device)
+        return (w * torch.exp(-s * errors)).sum(-1)
+    return (np.asarray(weights) * np.exp(-np.asarray(scales) * np.asarray(errors))).sum(-1)
 
 
 def quat_mul(a, b):

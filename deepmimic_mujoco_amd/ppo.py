@@ -227,17 +227,18 @@ class PpoLearner:
 
 
 def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print, group=None, log_dir=None,
-          fused=None, schedule="linear", bootstrap_time_limit=False, **learner_kwargs):
+          fused=None, schedule="linear", bootstrap_time_limit=False, log_reward_terms=False, **learner_kwargs):
     """ppo1's `learn()` over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy, with trpo.learn's loop (train_loop.run),
     stopping rules (`max_iters`, `max_timesteps` env steps (global), `max_seconds`), multi-rank handling and output files (`log_dir`: rank 0
     writes progress.csv and monitor.csv).  Episode statistics over ppo1's window of the last 100 episodes.  schedule="linear" needs
     max_timesteps.  fused: the rollout's policy step inside the env step kernel (None: when possible).  Returns the per-iteration stats:
     loss_pol_surr, loss_pol_entpen, loss_vf_loss, loss_kl, loss_ent, clipfrac, ev_tdlam_before, EpLenMean, EpRewMean, EpThisIter, ...
-    bootstrap_time_limit: as in trpo.learn (value bootstrap where the time limit ends an episode; adds TruncThisIter)."""
+    bootstrap_time_limit: as in trpo.learn (value bootstrap where the time limit ends an episode; adds TruncThisIter).
+    log_reward_terms: as in trpo.learn (adds ErrPose, ErrVel, ErrEndEff, ErrRoot, ErrCom after the keys above; off: keys and columns unchanged)."""
     from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = PpoLearner(pi, group=group, schedule=schedule, max_timesteps=max_timesteps, **learner_kwargs)
-    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit)
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit, log_reward_terms)
     steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
 
     def iterate(timesteps_so_far):
@@ -248,6 +249,7 @@ def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, ma
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
         train_loop.truncation_stat(stats, seg)
+        train_loop.reward_terms_stat(stats, seg, group)
         return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
 
     def log_line(stats):
@@ -259,4 +261,5 @@ def learn(env, pi, *, timesteps_per_batch=2048, max_iters=0, max_timesteps=0, ma
     return train_loop.run(pi, iterate, window=100, log_line=log_line, names=locals(), max_iters=max_iters, max_timesteps=max_timesteps,
                           max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir,
                           columns=("loss_pol_surr", "loss_pol_entpen", "loss_vf_loss", "loss_kl", "loss_ent", "clipfrac", "ev_tdlam_before",
-                                   "EpLenMean", "EpRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed"))
+                                   "EpLenMean", "EpRewMean", "EpThisIter", "EpisodesSoFar", "TimestepsSoFar", "TimeElapsed")
+                          + (train_loop.ERR_KEYS if log_reward_terms else ()))

@@ -142,6 +142,8 @@ class Segment(dict):
     pending_true = None                  # with a reward_giver: the env's own returns ("ep_true_rets"), also on their way to the host
     info = None                          # how the segment was produced (launch form, overflow rate of the packed path): diagnostics, not data
     pending_trunc = None                 # bootstrap_time_limit: (pinned int32 [1], event) — the truncation log's count on its way to the host
+    err_sums = None                      # reward_terms: float64 [6] on the device — the imitation reward's five errors summed over the envs whose last step
+                                         # of the segment was not done, then their number (train_loop.reward_terms_stat takes the mean)
     _trunc = None
 
     def trunc_count(self):
@@ -209,13 +211,21 @@ class SegmentCollector(object):
     "ep_rets" then come from it, "ep_true_rets" from the env's reward through a second episode scan with its own carry (:85-91)."""
 
     def __init__(self, pi, env, horizon, stochastic=True, device=None, first_reset="rsi", stream=None, fused=False, reward_giver=None,
-                 bootstrap_time_limit=False):
+                 bootstrap_time_limit=False, reward_terms=False):
+        """reward_terms (an env with reward="imitation"): one dm_batch_imitation_terms call per segment, on the states the segment ends in, behind the
+        horizon's launches — the segment then carries `err_sums` (Segment); nothing is added to a step."""
         import torch
         self.pi, self.env, self.T, self.stochastic, self.stream = pi, env, int(horizon), stochastic, stream
         n, T = env.num_envs, self.T
         self.n = n
         device = torch.device(pi.device if device is None else device)
         self.device = device
+        self._terms = None
+        if reward_terms:
+            from . import _abi as A
+            if int(getattr(env.batch, "options", {}).get(A.OPT_REWARD_MODE, 0)) != 3:
+                raise ValueError("reward_terms needs an env with reward=\"imitation\" (the batch's cursors name the compared frame in that mode only)")
+            self._terms = torch.zeros((n, A.NTERMS), dtype=torch.float64, device=device)
         self.bootstrap = bool(bootstrap_time_limit)
         if self.bootstrap:
             self._init_bootstrap()
@@ -424,6 +434,11 @@ class SegmentCollector(object):
         if self.bootstrap:
             with self._on_stream():                    # (on the stream the batch is on: reading its log there needs no change of stream)
                 self._bootstrap_values(seg)
+        if self._terms is not None:
+            with self._on_stream():                    # behind the horizon's launches, before the next segment's: the states the segment ends in
+                self.env.batch.imitation_terms(out=self.as_buf(self._terms))
+                keep = (self.done8[-1] == 0).to(torch.float64)          # an env the last step reset shows its fresh episode's row: left out
+                seg.err_sums = torch.cat([(self._terms[:, :5] * keep[:, None]).sum(0), keep.sum()[None]])
         if self.stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         import os
@@ -531,7 +546,8 @@ class SegmentCollector(object):
         return ep_rets, ep_lens
 
 
-def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None, bootstrap_time_limit=False):
+def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None, bootstrap_time_limit=False,
+                           reward_terms=False):
     """Batched `traj_segment_generator` (src/trpo.py:27-80): N envs advance in lock step on the device.
 
     pi: policy.MlpPolicy; env: DPVecEnv created with autoreset="init" — the kernel then applies, on `done`, exactly what
@@ -552,14 +568,17 @@ def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first
     "ep_true_rets", the env's returns of the same episodes.
 
     bootstrap_time_limit (env with max_episode_steps > 0): the segment also carries "vboot" [T,N] f32, the critic's value of every state the time
-    limit cut off (SegmentCollector._bootstrap_values), which `add_vtarg_and_adv` adds to the one-step target there."""
-    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver, bootstrap_time_limit=bootstrap_time_limit)
+    limit cut off (SegmentCollector._bootstrap_values), which `add_vtarg_and_adv` adds to the one-step target there.
+
+    reward_terms (env with reward="imitation"): the segment also carries `err_sums` (Segment), from one terms launch per segment."""
+    c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver, bootstrap_time_limit=bootstrap_time_limit,
+                         reward_terms=reward_terms)
     while True:
         c.launch()
         yield c.collect()
 
 
-def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset="rsi", fused=False, bootstrap_time_limit=False):
+def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset="rsi", fused=False, bootstrap_time_limit=False, reward_terms=False):
     """The same segments from SEVERAL env batches (e.g. two halves of a GPU's envs) stepped concurrently, each on its own CUDA
     stream: the whole T-step chain of every batch (policy forward -> env step -> policy forward ...) is enqueued without a host
     wait, so while one batch's env kernel drains its last, cheap workgroups the other batch's policy / env kernels fill the freed
@@ -567,7 +586,7 @@ def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset=
     axis is the concatenation of the batches (episode lists concatenated in batch order)."""
     import torch
     cols = [SegmentCollector(pi, e, horizon, stochastic, None, first_reset, stream=torch.cuda.Stream(device=pi.device), fused=fused,
-                             bootstrap_time_limit=bootstrap_time_limit) for e in envs]
+                             bootstrap_time_limit=bootstrap_time_limit, reward_terms=reward_terms) for e in envs]
     while True:
         if getattr(pi, "_dirty", False) or getattr(pi, "_packed", None) is None:
             pi.pack()                                  # once, on the current stream, before the side streams fork from it
@@ -579,6 +598,8 @@ def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset=
         out = Segment()
         if bootstrap_time_limit:
             out._trunc = sum(sg.trunc_count() for sg in segs)
+        if reward_terms:
+            out.err_sums = sum(sg.err_sums for sg in segs)
         for k in segs[0]:                              # ("vboot", when there, is [T, N] like "rew": it joins along the env axis)
             if k in ("ep_rets", "ep_lens"):
                 out[k] = [x for sg in segs for x in sg[k]]

@@ -8,15 +8,36 @@ from collections import deque
 import torch
 
 
-def segments(pi, env, horizon, fused=None, bootstrap_time_limit=False):
+def segments(pi, env, horizon, fused=None, bootstrap_time_limit=False, reward_terms=False):
     """-> (segment generator, this rank's env count) over a DPVecEnv, or a list of them (pipelined rollouts).  bootstrap_time_limit: the segments carry
-    "vboot", the critic's value of the states a time limit cut off (rollout.SegmentCollector)."""
+    "vboot", the critic's value of the states a time limit cut off (rollout.SegmentCollector).  reward_terms: they carry `err_sums` (reward_terms_stat)."""
     from .rollout import can_fuse, pipelined_segment_generator, traj_segment_generator
     if isinstance(env, (list, tuple)):          # several env batches of this rank, stepped concurrently on their own streams
-        return pipelined_segment_generator(pi, list(env), horizon, stochastic=True, bootstrap_time_limit=bootstrap_time_limit), sum(e.num_envs for e in env)
+        return pipelined_segment_generator(pi, list(env), horizon, stochastic=True, bootstrap_time_limit=bootstrap_time_limit,
+                                           reward_terms=reward_terms), sum(e.num_envs for e in env)
     # fused (default when possible): the policy step runs inside the env step kernel, one launch per rollout step
     use_fused = can_fuse(pi, env) if fused is None else bool(fused)
-    return traj_segment_generator(pi, env, horizon, stochastic=True, fused=use_fused, bootstrap_time_limit=bootstrap_time_limit), env.num_envs
+    return traj_segment_generator(pi, env, horizon, stochastic=True, fused=use_fused, bootstrap_time_limit=bootstrap_time_limit, reward_terms=reward_terms), env.num_envs
+
+
+# learn(log_reward_terms=True): the imitation reward's five errors (imitation.TERM_NAMES) of the states each segment ends in, logged after the learner's own keys
+ERR_KEYS = ("ErrPose", "ErrVel", "ErrEndEff", "ErrRoot", "ErrCom")
+
+
+def reward_terms_stat(stats, seg, group=None):
+    """ErrPose .. ErrCom: the mean over the environments (of every rank) whose last step of `seg` was not done of the imitation reward's five errors at
+    the state the segment ends in (a segment of segments(reward_terms=True); nothing is added otherwise).  One small copy to the host per segment."""
+    sums = getattr(seg, "err_sums", None)
+    if sums is None:
+        return
+    import torch.distributed as dist
+    from .trpo import _world
+    if _world(group) > 1:
+        sums = sums.clone()
+        dist.all_reduce(sums, group=group)
+    v = sums.tolist()
+    for k, x in zip(ERR_KEYS, v[:5]):
+        stats[k] = x / max(1.0, v[5])
 
 
 def truncation_stat(stats, seg):

@@ -687,7 +687,7 @@ class TrpoLearner:
 
 
 def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max_seconds=0, callback=None, log=print,
-          group=None, log_dir=None, fused=None, bootstrap_time_limit=False, **learner_kwargs):
+          group=None, log_dir=None, fused=None, bootstrap_time_limit=False, log_reward_terms=False, **learner_kwargs):
     """`learn()` of src/trpo.py:97-319 over a DPVecEnv (autoreset="init"; or a list of them: pipelined rollouts) and an MlpPolicy.  Stops after `max_iters`
     iterations, `max_timesteps` env steps (global) or `max_seconds`.  Returns the list of per-iteration stat dicts, with
     the reference's log keys (EpLenMean / EpRewMean over the last 40 episodes, EpThisIter, EpisodesSoFar, TimestepsSoFar,
@@ -695,11 +695,14 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
     files there: `progress.csv` (logger CSV, src/logger.py:101-135) and `monitor.json.monitor.csv` (bench.Monitor, one row per
     finished episode of rank 0's envs) — readable by the reference's plot_curve.py / load_results.
     bootstrap_time_limit (the env has max_episode_steps > 0): a time-limit end is a truncation — the value target bootstraps from the critic's value of
-    the state the limit cut off (rollout.SegmentCollector), and the stats gain TruncThisIter, the number of such ends in the iteration's segment."""
+    the state the limit cut off (rollout.SegmentCollector), and the stats gain TruncThisIter, the number of such ends in the iteration's segment.
+    log_reward_terms (the env has reward="imitation"): the stats and progress.csv gain ErrPose, ErrVel, ErrEndEff, ErrRoot, ErrCom after the keys above —
+    the imitation reward's five errors at the states each segment ends in, averaged over the environments whose last step was not done: one
+    `Batch.imitation_terms` launch per segment behind the horizon's, nothing per step.  Off (default): keys and columns are unchanged."""
     from . import train_loop
     assert sum([max_iters > 0, max_timesteps > 0, max_seconds > 0]) >= 1
     learner = TrpoLearner(pi, group=group, **learner_kwargs)
-    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit)
+    seg_gen, n_envs_local = train_loop.segments(pi, env, timesteps_per_batch, fused, bootstrap_time_limit, log_reward_terms)
     steps_per_iter = timesteps_per_batch * n_envs_local * _world(group)
 
     def iterate(timesteps_so_far):
@@ -718,6 +721,7 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
             stats["rollout"] = dict(seg.info)
         lens, rets = seg["ep_lens"], seg["ep_rets"]
         train_loop.truncation_stat(stats, seg)
+        train_loop.reward_terms_stat(stats, seg, group)
         return stats, {"EpLenMean": lens, "EpRewMean": rets}, [(rets, lens)], steps_per_iter
 
     def log_line(stats):
@@ -729,11 +733,11 @@ def learn(env, pi, *, timesteps_per_batch=256, max_iters=0, max_timesteps=0, max
     return train_loop.run(pi, iterate, window=40, log_line=log_line, names=locals(), max_iters=max_iters, max_timesteps=max_timesteps,
                           max_seconds=max_seconds, callback=callback, log=log, group=group, log_dir=log_dir,
                           columns=("EpRewMean", "EpThisIter", "TimestepsSoFar", "EpisodesSoFar", "surrgain", "optimgain", "TimeElapsed", "meankl",
-                                   "entloss", "ev_tdlam_before", "entropy", "EpLenMean"))
+                                   "entloss", "ev_tdlam_before", "entropy", "EpLenMean") + (train_loop.ERR_KEYS if log_reward_terms else ()))
 
 
 def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print, save_sample=None, frames=None, render_size=(500, 500),
-           render_camera="side"):
+           render_camera="side", reward_terms=False):
     """`runner()` + `traj_1_generator()` of src/trpo.py:356-436 (`--task evaluate`), one trajectory per env of the batch at once: from
     `env.reset(); env.reset_model_init()` each env runs `pi.act(stochastic, ob)` -> `env.step(ac)` until its first `done` or until
     `timesteps_per_batch + 1` steps.  Returns (average length, average return) as the reference prints them, plus the per-trajectory
@@ -742,7 +746,9 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
     trajectory has the same length, else object arrays of N (L_i, ...) arrays, lens, rets; and the same returns as `ep_rets`, the key the
     GAIL expert reader (src/utils/mujoco_dset.py) reads.  gail.ExpertDataset accepts the file.
     frames: a render.FrameWriter — trajectory 0 is rendered (dm_batch_render, `render_camera`, render_size = (width, height)) from its
-    first state and after every step it survives: what the reference's `env.render()` after each step (:421) shows."""
+    first state and after every step it survives: what the reference's `env.render()` after each step (:421) shows.
+    reward_terms (an env with reward="imitation"): one `Batch.imitation_terms` call after every step; each trajectory's mean of the reward's five errors
+    over the steps it survived is logged (the step that ends a trajectory has no row: the env has reset it) and kept in `runner.last_err_means` [N, 5]."""
     n = env.num_envs
 
     def snap():
@@ -757,6 +763,10 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         ep_len = torch.zeros(n, dtype=torch.int64, device=dev); ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
         obs_hist, acs_hist = [], []
+        if reward_terms:
+            from . import _abi as A
+            terms = torch.zeros((n, A.NTERMS), dtype=torch.float64, device=dev)
+            err_sum = torch.zeros((n, 5), dtype=torch.float64, device=dev); err_cnt = torch.zeros(n, dtype=torch.float64, device=dev)
         if frames is not None:
             snap()
         for t in range(int(timesteps_per_batch) + 1):
@@ -768,6 +778,9 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
             rew = torch.as_tensor(res[1], dtype=torch.float64, device=dev); done = torch.as_tensor(res[2], device=dev).to(torch.bool)
             ep_ret += torch.where(alive, rew, torch.zeros_like(rew)); ep_len += alive.to(torch.int64)
             alive &= ~done
+            if reward_terms:
+                env.batch.imitation_terms(out=terms if terms.is_cuda else terms.numpy())
+                err_sum += torch.where(alive[:, None], terms[:, :5], torch.zeros_like(terms[:, :5])); err_cnt += alive.to(torch.float64)
             if frames is not None and bool(alive[0]):
                 snap()
             if not bool(alive.any()):
@@ -785,4 +798,11 @@ def runner(env, pi, timesteps_per_batch=1024, stochastic_policy=False, log=print
     log("stochastic policy:" if stochastic_policy else "deterministic policy:")
     log("Average length: %s" % (lens.sum() / len(lens)))
     log("Average return: %s" % (rets.sum() / len(rets)))
+    if reward_terms:
+        from .imitation import TERM_NAMES
+        means = (err_sum / err_cnt.clamp(min=1.0)[:, None]).cpu().numpy()
+        runner.last_err_means = means
+        log("mean imitation errors per trajectory (%s):" % ", ".join(TERM_NAMES))
+        for e in range(n):
+            log("  trajectory %d: %s" % (e, "  ".join("%.6g" % x for x in means[e])))
     return float(lens.mean()), float(rets.mean()), lens, rets

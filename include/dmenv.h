@@ -33,6 +33,7 @@ extern "C" {
 #define DM_NGEOM 16
 #define DM_NOBS 56
 #define DM_NSTATE 171 /* DeepMimic's state features (dm_batch_state_features): 1 + 1 + 13 * 7 + 13 * 6 */
+#define DM_NTERMS 28  /* the imitation reward's terms (dm_batch_imitation_terms): 5 + 5 + 1 + 13 + 4 */
 #define DM_MAXPAIR 128
 #define DM_MAXEFC 64   /* lanes of the per-env wavefront = stride of the per-row arrays */
 #define DM_MAXROWS 63  /* constraint rows per environment held on chip (one lane each; the 64th lane carries the smooth force);
@@ -353,6 +354,33 @@ int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel,
  * explicit states; env_ids must then be NULL.  out [n] int32.  One launch on the batch's stream, one wave per state; argument checks,
  * stream ordering, settle-first behaviour and ptr_kind as for dm_batch_state_features.  Read-only: changes no batch state. */
 int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const int32_t* env_ids, int32_t n, int32_t* out, int32_t ptr_kind);
+
+/* The five terms of reward mode 3 at n humanoid states: what dm_batch_step adds up and returns as one number,
+ *   r = 0.5 e^(-2 pose) + 0.05 e^(-0.1 vel) + 0.15 e^(-40 eff) + 0.2 e^(-5 root) + 0.1 e^(-10 com),
+ * taken apart.  out [n, DM_NTERMS] float64, one row per state, each state compared with one row of the mocap's imitation table:
+ *   [0..5)    the errors e_k: pose sum_j w_j theta_j^2, velocity sum_j w_j |dw_j|^2, end effector sum_e |dp_e|^2 / 4,
+ *             root |dp|^2 + 0.1 theta_root^2 + 0.01 |dv|^2 + 0.001 |dw|^2, centre of mass 0.1 |dv_com|^2
+ *   [5..10)   the weighted terms w_k exp(-s_k e_k), w = (0.5, 0.05, 0.15, 0.2, 0.1), s = (2, 0.1, 40, 5, 10)
+ *   [10]      their sum: the reward of mode 3
+ *   [11..24)  each joint group's share w_j theta_j^2 of the pose error, in the weight-slot order of the parameter block: the 12 joint
+ *             groups in model body order, then the root (slot 12); they sum to [0]
+ *   [24..28)  each end effector's squared distance |dp_e|^2 to the reference's, in the parameter block's order; their sum / 4 is [2]
+ * The arithmetic is the library's (float64, or float32 in libdmenv32.so) and the step kernels' own lane code; a caller re-weights the reward
+ * from [0..5) alone.
+ * qpos [n,35] non-NULL: explicit states — qvel [n,34] and frame [n] (the table row each state is compared with) must be given too,
+ * cycle [n] may be (NULL: 0; the reference's root is shifted by cycle completed cycles), and env_ids must be NULL.  Works in any reward
+ * mode.  Host-pointer frames outside [0, n_frames) are DM_EINVAL; device-pointer frames are not read back: such a row is written as
+ * DM_NTERMS NaNs and the table is not read out of range.
+ * qpos == NULL (qvel, frame and cycle must then be NULL too): the batch's current states and cursors (frame_idx, cycle) of
+ * env_ids[0..n) (env_ids NULL: envs 0..n-1, n <= the batch size).  Reward mode 3 only (DM_EINVAL otherwise): only there do the cursors name
+ * the row the last step compared the state with, so that right after a step [10] is the reward that step returned — except for an
+ * environment the step reset (done with DM_OPT_AUTORESET on): its state and cursors are the fresh episode's, like its observation, and
+ * its row is that state against the frame it was drawn at.
+ * One launch on the batch's stream, one wave per state; argument checks, stream ordering (device env_ids are read back and
+ * range-checked, nothing else waits), settle-first behaviour and ptr_kind as for dm_batch_state_features.  Read-only: changes no batch
+ * state.  DM_EINVAL also when the mocap has no imitation table (dm_mocap_set_imitation was not called) and for a partial explicit state. */
+int dm_batch_imitation_terms(dm_batch* b, const double* qpos, const double* qvel, const int32_t* frame, const int32_t* cycle,
+                             const int32_t* env_ids, int32_t n, double* out /* [n, DM_NTERMS] */, int32_t ptr_kind);
 
 /* kernel timing of the last dm_batch_step launch, measured with HIP events on the batch's stream (ms) */
 int dm_batch_last_step_ms(dm_batch* b, float* ms);

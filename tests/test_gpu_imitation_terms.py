@@ -1,0 +1,327 @@
+"""dm_batch_imitation_terms on the GPU (csrc/terms_kernel.h): the imitation reward's terms row against the float64 restatement
+(tests/terms_numpy.py) and the oracle for explicit states, against the step's own reward for the batch's states, the argument rules, that
+the call changes nothing, the float32 library, `DPVecEnv(reward_terms=True)` and the learners' `log_reward_terms`.
+
+Bars.  float64 library: 1e-9 absolute on every column.  float32 library: the per-column bars of tests/test_imitation_terms.py
+(FLOAT_MARGIN times the largest difference between the float32 and the float64 oracle over the same states)."""
+import numpy as np
+import pytest
+import torch
+
+from deepmimic_mujoco_amd import _abi as A
+from deepmimic_mujoco_amd import Batch, DPVecEnv, MlpPolicy
+from deepmimic_mujoco_amd._abi import DmenvError
+from deepmimic_mujoco_amd.train_loop import ERR_KEYS
+from tests import helpers as H
+from tests import test_imitation_terms as TI
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda", 0)
+TOL64 = 1e-9
+
+
+def make_batch(n, dtype=64, imitation=True, clip="walk"):
+    mc = H.mocap(clip)
+    c = TI.cases(clip)
+    return Batch(H.compiled_model(), mc.data_config, mc.data_vel, n, device=0, mocap_dt=float(mc.dt), dtype=dtype,
+                 imitation=(c["table"], c["params"]) if imitation else None)
+
+
+def picks(n):
+    """the states of the explicit-form tests: indices into tests/test_imitation_terms.cases()"""
+    c = TI.cases()
+    names = c["names"]
+    if n == 1:
+        return np.array([names.index("perturbed") + 2])
+    if n == 5:
+        return np.array([0, names.index("next row") + 3, names.index("perturbed") + 5, names.index("negated root quaternion"), names.index("cycle 2")])
+    return np.arange(len(names) - n, len(names))            # 66: the tail — next-row frames, all 32 perturbations, the five special states
+
+
+# ---- explicit states ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 5, 66])
+def test_explicit_states_match_the_restatement_and_the_oracle(n):
+    c = TI.cases()
+    i = picks(n)
+    assert len(i) == n
+    q, v, f, cy, ref = c["qpos"][i], c["qvel"][i], c["frame"][i], c["cycle"][i], c["ref"][i]
+    b = make_batch(4)
+    got = b.imitation_terms(qpos=q, qvel=v, frame=f, cycle=cy)
+    err = np.abs(got - ref)
+    print("explicit n=%d float64: worst error %.3e (column %d)" % (n, err.max(), int(err.max(0).argmax())))
+    assert got.shape == (n, 28) and err.max() <= TOL64
+    assert np.abs(got[:, TI.ORACLE_COLS] - TI.oracle_rows(64)[i]).max() <= TOL64
+    tq, tv, tf, tc = (torch.as_tensor(x, device=DEV) for x in (q, v, f, cy))
+    out = torch.zeros((n, 28), dtype=torch.float64, device=DEV)
+    assert b.imitation_terms(qpos=tq, qvel=tv, frame=tf, cycle=tc, out=out) is out
+    np.testing.assert_array_equal(out.cpu().numpy(), got)                      # host and device pointers: the same launch
+    if not cy.any():                                                           # cycle is optional: NULL means 0
+        np.testing.assert_array_equal(b.imitation_terms(qpos=q, qvel=v, frame=f), got)
+    b.set_option(A.OPT_REWARD_MODE, 1)                                         # the explicit form works in any reward mode
+    np.testing.assert_array_equal(b.imitation_terms(qpos=q, qvel=v, frame=f, cycle=cy), got)
+    b.close()
+
+
+def test_a_frame_outside_the_table():
+    c = TI.cases()
+    i = picks(5)
+    q, v, cy, F = c["qpos"][i], c["qvel"][i], c["cycle"][i], c["n_frames"]
+    b = make_batch(2)
+    good = b.imitation_terms(qpos=q, qvel=v, frame=c["frame"][i], cycle=cy)
+    for bad_value in (F, -1, 2 ** 30):
+        f = c["frame"][i].copy(); f[2] = bad_value
+        with pytest.raises(DmenvError, match="frame out of range"):          # host pointers: checked on the host
+            b.imitation_terms(qpos=q, qvel=v, frame=f, cycle=cy)
+        out = b.imitation_terms(qpos=torch.as_tensor(q, device=DEV), qvel=torch.as_tensor(v, device=DEV), frame=torch.as_tensor(f, device=DEV),
+                                cycle=torch.as_tensor(cy, device=DEV)).cpu().numpy()
+        assert np.isnan(out[2]).all()                                          # device pointers: not read back, a NaN row ...
+        np.testing.assert_array_equal(np.delete(out, 2, 0), np.delete(good, 2, 0))     # ... and its neighbours are right
+    b.close()
+
+
+# ---- the batch's own states -----------------------------------------------------------------------------------------------------------
+def start(b, n, seed):
+    """mocap frames with a little noise; some environments start two frames before the clip wraps (cycle 0 -> 1)"""
+    mc = H.mocap()
+    F = len(mc.data_config)
+    rng = np.random.RandomState(seed)
+    idx = rng.randint(0, F - 1, size=n).astype(np.int32)
+    idx[::3] = F - 3
+    q = mc.data_config[idx].copy(); v = mc.data_vel[idx].copy()
+    q[:, 7:] += 0.02 * rng.randn(n, 28)
+    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
+    b.set_state(q, v, frame_idx=idx)
+    return rng
+
+
+def imitation_batch(n, packed, pipeline=0, dtype=64):
+    b = make_batch(n, dtype)
+    b.set_option(A.OPT_REWARD_MODE, 3); b.set_option(A.OPT_AUTORESET, 0); b.set_option(A.OPT_PACKED, 1 if packed else 0)
+    if pipeline:
+        b.set_option(A.OPT_PIPELINE, pipeline)
+    return b
+
+
+def substeps():
+    mc = H.mocap()
+    return max(1, int(float(mc.dt) / float(H.compiled_model().timestep)))
+
+
+@pytest.mark.parametrize("variant", ["plain", "pipelined", "env_ids"])
+@pytest.mark.parametrize("n,packed", [(6, False), (66, True)])
+def test_batch_rows_are_the_steps_reward_taken_apart(n, packed, variant):
+    b = imitation_batch(n, packed, pipeline=2 if variant == "pipelined" else 0)
+    rng = start(b, n, seed=n)
+    ids = None
+    if variant == "env_ids":
+        ids = np.random.RandomState(7).permutation(n)[:max(3, n // 2)].astype(np.int32)
+    sel = np.arange(n) if ids is None else ids
+    worst, wrapped = 0.0, 0
+    ob = torch.zeros((n, A.NOBS), dtype=torch.float64, device=DEV); rew = torch.zeros(n, dtype=torch.float64, device=DEV)
+    done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    for t in range(8):
+        b.step(torch.as_tensor(rng.randn(n, 28) * 0.9, device=DEV), substeps(), (ob, rew, done))
+        rows = b.imitation_terms(env_ids=ids)                                  # (joins the pipelined parts first)
+        r = rew.cpu().numpy()
+        worst = max(worst, float(np.abs(rows[:, 10] - r[sel]).max()))
+        assert np.abs(rows[:, 10] - r[sel]).max() <= TOL64, (t, worst)
+        q, v, f, cy = b.get(A.F_QPOS), b.get(A.F_QVEL), b.get(A.F_FRAME_IDX), b.get(A.F_CYCLE)
+        wrapped += int((cy > 0).sum())
+        np.testing.assert_array_equal(b.imitation_terms(qpos=q[sel], qvel=v[sel], frame=f[sel], cycle=cy[sel]), rows)     # bit for bit
+        dev_rows = b.imitation_terms(env_ids=None if ids is None else torch.as_tensor(ids, device=DEV), out=torch.zeros((len(sel), 28), dtype=torch.float64, device=DEV))
+        np.testing.assert_array_equal(dev_rows.cpu().numpy(), rows)
+    print("batch form n=%d packed=%s %s: column 10 against the step's reward, worst %.3e; %d env-steps past a wrap" % (n, packed, variant, worst, wrapped))
+    assert wrapped > 0
+    b.close()
+
+
+def test_batch_form_argument_rules():
+    n = 6
+    b = make_batch(n)
+    out = np.zeros((n, 28))
+    with pytest.raises(DmenvError, match="reward mode 3"):                    # mode 0: the cursors do not name the compared row
+        b.imitation_terms(out=out)
+    b.set_option(A.OPT_REWARD_MODE, 3)
+    assert b.imitation_terms(out=out) is out and np.isfinite(out).all()
+    with pytest.raises(DmenvError, match="out of range"):
+        b.imitation_terms(env_ids=np.array([0, n], dtype=np.int32))
+    with pytest.raises(DmenvError, match="exceeds the batch"):
+        b.imitation_terms(env_ids=np.zeros(n + 1, dtype=np.int32))
+    L = b._L
+    p = lambda a: a.ctypes.data
+    q, v, f = np.zeros((n, A.NQ)), np.zeros((n, A.NV)), np.zeros(n, dtype=np.int32)
+    for args, word in (((None, p(v), None, None, None), "needs qpos, qvel and frame"), ((None, None, None, p(f), None), "needs qpos, qvel and frame"),
+                       ((p(q), p(v), None, None, None), "needs qpos, qvel and frame"), ((p(q), p(v), p(f), None, p(f)), "env_ids must be NULL")):
+        assert L.dm_batch_imitation_terms(b._h, *args, n, p(out), A.PTR_HOST) == -1 and word in L.dm_last_error().decode(), L.dm_last_error()
+    assert L.dm_batch_imitation_terms(b._h, None, None, None, None, None, n, None, A.PTR_HOST) == -1
+    assert L.dm_batch_imitation_terms(b._h, None, None, None, None, None, n, p(out), 7) == -1
+    b.close()
+    bare = make_batch(n, imitation=False)                                     # no imitation table: neither form works
+    c = TI.cases()
+    with pytest.raises(DmenvError, match="no imitation table"):
+        bare.imitation_terms(qpos=c["qpos"][:2], qvel=c["qvel"][:2], frame=c["frame"][:2])
+    with pytest.raises(DmenvError, match="no imitation table"):
+        bare.imitation_terms()
+    bare.close()
+
+
+def test_the_call_changes_no_batch_state():
+    n = 66
+    fields = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE, A.F_CTRL, A.F_NEFC)
+    a, twin = imitation_batch(n, True), imitation_batch(n, True)
+    ra, rb = start(a, n, seed=4), start(twin, n, seed=4)
+    ids = np.arange(0, n, 5, dtype=np.int32)
+    for t in range(8):
+        act = ra.randn(n, 28) * 0.9
+        assert np.array_equal(act, rb.randn(n, 28) * 0.9)
+        a.imitation_terms(); a.imitation_terms(env_ids=torch.as_tensor(ids, device=DEV))
+        ra_out, rb_out = a.step(act, substeps()), twin.step(act, substeps())
+        a.imitation_terms(env_ids=ids)
+        for x, y in zip(ra_out, rb_out):
+            np.testing.assert_array_equal(x, y)
+        for f in fields:
+            np.testing.assert_array_equal(a.get(f), twin.get(f))
+    a.close(); twin.close()
+
+
+# ---- the float32 library ----------------------------------------------------------------------------------------------------------------
+def test_float32_library_stays_inside_the_oracle_derived_bars():
+    c = TI.cases()
+    bar = TI.float_bars()
+    i = picks(5)
+    b = imitation_batch(6, False, dtype=32)
+    got = b.imitation_terms(qpos=c["qpos"][i], qvel=c["qvel"][i], frame=c["frame"][i], cycle=c["cycle"][i])
+    ratio = (np.abs(got - c["ref"][i]) / bar).max(0) * TI.FLOAT_MARGIN
+    print("float32 library, explicit n=5: worst error per column as a multiple of the oracles' own difference (bar %g):\n%s" % (TI.FLOAT_MARGIN, np.array2string(ratio, precision=3)))
+    assert (ratio <= TI.FLOAT_MARGIN).all(), ratio
+    rng = start(b, 6, seed=2)
+    worst = 0.0
+    for t in range(8):
+        _o, rew, _d = b.step(rng.randn(6, 28) * 0.9, substeps())
+        worst = max(worst, float(np.abs(b.imitation_terms()[:, 10] - rew).max()))
+    print("float32 library, batch form: column 10 against the step's reward, worst %.3e (bar %.3e)" % (worst, bar[10]))
+    assert worst <= bar[10]
+    b.close()
+
+
+# ---- DPVecEnv(reward_terms=True) ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("device_buffers", [False, True])
+def test_dpvecenv_reward_terms(device_buffers):
+    n, steps = 64, 64
+    env = DPVecEnv(n, motion="walk", reward="imitation", autoreset="rsi", seed=5, reward_terms=True)
+    off = DPVecEnv(n, motion="walk", reward="imitation", autoreset="rsi", seed=5)
+    host = lambda x: x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    env.reset("rsi"); off.reset("rsi")
+    assert env.last_reward_terms is None
+    rng = np.random.RandomState(1)
+    n_done = n_live = 0
+    for t in range(steps):
+        a = rng.randn(n, 28) * 1.5
+        _ob, rew, done, _ = env.step(torch.as_tensor(a, device=DEV) if device_buffers else a)
+        _ob0, rew0, done0, _ = off.step(a)
+        rows, rew, done = host(env.last_reward_terms), host(rew), host(done).astype(bool)
+        assert torch.is_tensor(env.last_reward_terms) == device_buffers and rows.shape == (n, 28)
+        np.testing.assert_array_equal(rew, rew0); np.testing.assert_array_equal(done, np.asarray(done0).astype(bool))     # the option changes no step
+        assert np.isnan(rows[done]).all() and np.isfinite(rows[~done]).all()
+        assert np.abs(rows[~done, 10] - rew[~done]).max() <= TOL64 if (~done).any() else True
+        n_done += int(done.sum()); n_live += int((~done).sum())
+    assert n_done >= 1 and n_live >= 1, (n_done, n_live)
+    assert off.last_reward_terms is None
+    q = env.reward_terms(env_ids=np.array([3, 1], dtype=np.int32))            # the query of the current states
+    np.testing.assert_array_equal(q, env.batch.imitation_terms()[[3, 1]])
+    env.close(); off.close()
+    with pytest.raises(ValueError):
+        DPVecEnv(4, motion="walk", reward="v3-config", reward_terms=True)
+
+
+# ---- the learners ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("algo", ["trpo", "ppo", "gail"])
+def test_learners_log_the_five_errors(algo):
+    n, T = 64, 16
+
+    def run(flag):
+        env = DPVecEnv(n, motion="walk", reward="imitation", autoreset="init", seed=3)
+        pi = MlpPolicy(device=DEV, seed=1); pi.seed(1)
+        kw = dict(timesteps_per_batch=T, max_iters=1, log=None, seed=1, log_reward_terms=flag)
+        if algo == "trpo":
+            from deepmimic_mujoco_amd.trpo import learn
+            hist = learn(env, pi, **kw)
+        elif algo == "ppo":
+            from deepmimic_mujoco_amd.ppo import learn
+            hist = learn(env, pi, schedule="constant", optim_epochs=1, optim_batchsize=64, **kw)
+        else:
+            from deepmimic_mujoco_amd.gail import ExpertDataset, TransitionClassifier, learn
+            rng = np.random.RandomState(0)
+            expert = ExpertDataset(dict(obs=rng.randn(4, 40, 56).astype(np.float32), acs=rng.randn(4, 40, 28).astype(np.float32), ep_rets=np.ones(4), lens=np.full(4, 40)),
+                                   seed=0, device=DEV)
+            hist = learn(env, pi, TransitionClassifier(device=DEV, seed=1), expert, g_step=1, d_step=1, **kw)
+        env.close()
+        assert len(hist) == 1
+        return hist[0]
+    on, off = run(True), run(False)
+    assert all(k in on and np.isfinite(on[k]) and on[k] >= 0 for k in ERR_KEYS), on
+    assert not any(k in off for k in ERR_KEYS)
+    assert [k for k in on if k not in ERR_KEYS] == list(off)                  # the flag adds the five keys and moves nothing else
+    assert ERR_KEYS == ("ErrPose", "ErrVel", "ErrEndEff", "ErrRoot", "ErrCom")
+
+
+def test_flag_needs_the_imitation_reward():
+    from deepmimic_mujoco_amd.rollout import SegmentCollector
+    env = DPVecEnv(8, motion="walk", autoreset="init", seed=3)
+    with pytest.raises(ValueError):
+        SegmentCollector(MlpPolicy(device=DEV, seed=1), env, 4, reward_terms=True)
+    env.close()
+
+
+# ---- the evaluate task and the single env -----------------------------------------------------------------------------------------------------
+def test_runner_reports_each_trajectorys_mean_errors():
+    from deepmimic_mujoco_amd.trpo import runner
+    n = 4
+    env = DPVecEnv(n, motion="walk", reward="imitation", autoreset="init", seed=2)
+    pi = MlpPolicy(device=DEV, seed=1); pi.seed(1)
+    lines = []
+    _len, _ret, lens, _rets = runner(env, pi, timesteps_per_batch=12, log=lines.append, reward_terms=True)
+    means = runner.last_err_means
+    assert means.shape == (n, 5) and np.isfinite(means).all() and (means >= 0).all() and (means[lens > 1] > 0).any()
+    assert sum(ln.startswith("  trajectory ") for ln in lines) == n and any("pose, velocity, end_effector, root, com" in ln for ln in lines)
+    quiet = []
+    runner(env, pi, timesteps_per_batch=4, log=quiet.append)
+    assert not any("trajectory" in ln for ln in quiet)
+    env.close()
+
+
+def test_dpenv_reward_terms_by_name():
+    import random
+    from deepmimic_mujoco_amd import DPEnv
+    from deepmimic_mujoco_amd import imitation as IM
+    from tests import terms_numpy as TN
+    random.seed(3)
+    env = DPEnv(motion="walk", reward="v3-config")
+    env.seed(1); env.reset()
+    rng = np.random.RandomState(0)
+    for _ in range(3):
+        env.step(rng.randn(28) * 0.5)
+    d = env.reward_terms()
+    c = TI.cases()
+    ref = TN.terms(TI.spec(), c["table"], c["params"], env.sim.data.qpos, env.sim.data.qvel, env.idx_curr % env.mocap_data_len)
+    assert set(IM.TERM_NAMES) <= set(d) and set(d["terms"]) == set(IM.TERM_NAMES) and len(d["joints"]) == 13 and "root" in d["joints"] and len(d["end_effectors"]) == 4
+    got = np.array([d[k] for k in IM.TERM_NAMES] + [d["terms"][k] for k in IM.TERM_NAMES] + [d["reward"]])
+    assert np.abs(got - ref[:11]).max() <= TOL64
+    assert abs(sum(d["joints"].values()) - d["pose"]) <= 1e-12 and abs(sum(d["end_effectors"].values()) / 4 - d["end_effector"]) <= 1e-12
+    far = env.reward_terms(frame=(env.idx_curr + 10) % env.mocap_data_len)
+    assert far["pose"] > 0 and far["reward"] != d["reward"]
+    env.close()
+
+
+def test_pipelined_generator_adds_the_batches_error_sums():
+    from deepmimic_mujoco_amd.rollout import pipelined_segment_generator
+    T = 6
+    envs = [DPVecEnv(n, motion="walk", reward="imitation", autoreset="init", seed=4 + k) for k, n in enumerate((6, 10))]
+    pi = MlpPolicy(device=DEV, seed=3); pi.seed(4)
+    seg = next(pipelined_segment_generator(pi, envs, T, reward_terms=True))
+    sums = seg.err_sums.cpu().numpy()
+    assert sums.shape == (6,) and np.isfinite(sums).all() and (sums[:5] >= 0).all() and 0 <= sums[5] <= 16 == seg["new"].shape[1]
+    rows = np.concatenate([e.batch.imitation_terms() for e in envs])       # nothing has stepped since: the states the segment ended in
+    assert sums[5] >= 1 and (sums[:5] <= rows[:, :5].sum(0) + 1e-9).all()
+    for e in envs:
+        e.close()

@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --bootstrap-time-limit and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk")
     if reward_help:
         ap.add_argument("--reward", default="alive", help=reward_help)
@@ -26,6 +26,9 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
     ap.add_argument("--bootstrap-time-limit", action="store_true",
                     help="treat a time-limit end as a truncation (DeepMimic's agent): the value target bootstraps from the critic's value of the state the limit cut off, "
                          "where a fall keeps 0.  Needs --max-episode-steps")
+    ap.add_argument("--log-reward-terms", action="store_true",
+                    help="--reward imitation: log the reward's five errors (ErrPose, ErrVel, ErrEndEff, ErrRoot, ErrCom) of the states each segment ends in, "
+                         "from one more launch per segment")
     if autoreset_help:
         ap.add_argument("--autoreset", default="init", help=autoreset_help)
     if frame_skip_help:
@@ -36,6 +39,8 @@ def check_env_args(ap, args):
     """Refuse flag combinations that cannot work, with the parser's own error message."""
     if getattr(args, "bootstrap_time_limit", False) and not args.max_episode_steps > 0:
         ap.error("--bootstrap-time-limit bootstraps the value where the time limit ends an episode: it needs --max-episode-steps M with M > 0")
+    if getattr(args, "log_reward_terms", False) and getattr(args, "reward", None) != "imitation":
+        ap.error("--log-reward-terms takes the imitation reward apart: it needs --reward imitation")
 
 
 def env_kwargs(args):

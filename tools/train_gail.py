@@ -82,7 +82,8 @@ def main():
     reward_giver = TransitionClassifier(ob_dim=env.observation_space.shape[0], hidden_size=args.adversary_hidden_size, entcoeff=args.adversary_entcoeff, device=dev, seed=args.seed)
     stop = dict(max_iters=args.iters) if args.iters else dict(max_timesteps=args.num_timesteps) if args.num_timesteps else dict(max_seconds=args.seconds)
     hist = learn(env, pi, reward_giver, expert, g_step=args.g_step, d_step=args.d_step, d_stepsize=args.d_stepsize, timesteps_per_batch=args.horizon,
-                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, algo=args.algo, bootstrap_time_limit=args.bootstrap_time_limit, **stop)
+                 entcoeff=args.policy_entcoeff, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir, algo=args.algo, bootstrap_time_limit=args.bootstrap_time_limit,
+                 log_reward_terms=args.log_reward_terms, **stop)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump({"args": vars(args), "history": hist}, open(args.out, "w"))

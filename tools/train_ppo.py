@@ -64,7 +64,8 @@ def main():
     schedule = args.schedule or ("linear" if "max_timesteps" in stop else "constant")
     hist = learn(env, pi, timesteps_per_batch=args.horizon, clip_param=args.clip_param, entcoeff=args.entcoeff, optim_epochs=args.optim_epochs,
                  optim_stepsize=args.optim_stepsize, optim_batchsize=args.optim_batchsize or None, gamma=args.gamma, lam=args.lam,
-                 adam_epsilon=args.adam_epsilon, schedule=schedule, seed=args.seed, log_dir=args.log_dir, native=False if args.no_native else None, bootstrap_time_limit=args.bootstrap_time_limit, **stop)
+                 adam_epsilon=args.adam_epsilon, schedule=schedule, seed=args.seed, log_dir=args.log_dir, native=False if args.no_native else None, bootstrap_time_limit=args.bootstrap_time_limit,
+                 log_reward_terms=args.log_reward_terms, **stop)
     if rank == 0:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -62,7 +62,7 @@ def main():
             from deepmimic_mujoco_amd.render import FrameWriter
             writer = FrameWriter(args.render_out, fps=1.0 / (env.frame_skip * float(env._cm.timestep)))
         runner(env, pi, timesteps_per_batch=1024, stochastic_policy=args.stochastic_policy, save_sample=args.save_sample, frames=writer,
-               render_size=(args.width, args.height), render_camera=args.camera)
+               render_size=(args.width, args.height), render_camera=args.camera, reward_terms=args.reward == "imitation")
         if writer is not None:
             print("wrote %d frames of trajectory 0 to %s" % (len(writer.frames), writer.close()))
         return
@@ -79,7 +79,8 @@ def main():
     pi = MlpPolicy(ob_dim=(envs[0] if args.unfused else env).observation_space.shape[0], device=dev, seed=args.seed); pi.seed(args.seed + 10000 * rank)
     hist = learn(env, pi, timesteps_per_batch=args.horizon, max_seconds=args.seconds if not args.iters else 0, max_iters=args.iters,
                  vf_batch_size=args.vf_batch, vf_stepsize=args.vf_stepsize, max_kl=args.max_kl, seed=args.seed, log_dir=args.log_dir,
-                 fused=False if args.unfused else None, pg_native=False if args.no_pg_native else None, bootstrap_time_limit=args.bootstrap_time_limit)
+                 fused=False if args.unfused else None, pg_native=False if args.no_pg_native else None, bootstrap_time_limit=args.bootstrap_time_limit,
+                 log_reward_terms=args.log_reward_terms)
     if args.dump_params:
         os.makedirs(os.path.dirname(os.path.abspath(args.dump_params)), exist_ok=True)
         pi.save_npz("%s.rank%d.npz" % (args.dump_params, rank))
