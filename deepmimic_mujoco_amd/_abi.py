@@ -23,6 +23,8 @@ OPT_FALL_BODIES, OPT_MAX_EPISODE_STEPS = 9, 10
 DONE_STEP, DONE_FALL, DONE_TIME_LIMIT = 1, 2, 4
 # the truncation log's capacity in records (0 = off): the states the time limit alone cut off, kept for the value bootstrap (dm_batch_truncations)
 OPT_TRUNCATION_LOG = 11
+# 1: early termination runs inside the horizon launch and the step queue (k_rollout_packed_term) instead of sending them back to step launches
+OPT_HORIZON_TERMINATION = 12
 # DM_OPT_ACTION_MODE values (include/dmenv.h): 3 and 4 make the action a PD target pose under a stable PD controller evaluated per substep
 ACTION_RAW, ACTION_P_CONTROL, ACTION_PD, ACTION_SPD_TARGET, ACTION_SPD_MOCAP = 0, 1, 2, 3, 4
 MAX_PIPELINE = 8

@@ -293,7 +293,8 @@ class Batch(object):
     def rollout(self, action, out, n_substeps=1, weights=None, vpred=None, stochastic=True, seed=0, counter=0):
         """T steps in one call (dm_batch_rollout), device tensors only: action [T + 1, n, 28] f64 (row t feeds step t; with `weights` — the
         packed policy block — rows 1..T are written by the policy), out = (obs [T, n, 56] f64, rew [T, n] f64, done [T, n] u8), vpred [T, n]
-        f32 (with weights).  Same results as T `step` / `step_act` calls; on the packed path (option 105) one launch for the horizon."""
+        f32 (with weights).  Same results as T `step` / `step_act` calls; on the packed path (option 105) one launch for the horizon — with early
+        termination on (OPT_FALL_BODIES, OPT_MAX_EPISODE_STEPS) only under OPT_HORIZON_TERMINATION, else T step launches with their termination launches."""
         import torch
         obs, rew, done = out
         T, n = int(obs.shape[0]), self.n

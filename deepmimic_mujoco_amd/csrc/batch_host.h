@@ -41,6 +41,8 @@ struct dm_batch {
   unsigned char* d_rbuf = nullptr; size_t rbuf_bytes = 0;
   // early termination (DM_OPT_FALL_BODIES, DM_OPT_MAX_EPISODE_STEPS; term_kernel.h): k_terminate follows every per-step launch while either is non-zero
   unsigned fall_bodies = 0; int max_episode_steps = 0; int *d_ep_steps = nullptr, *d_done_reason = nullptr;   // [N] DM_F_EPISODE_STEPS, DM_F_DONE_REASON
+  // DM_OPT_HORIZON_TERMINATION: the horizon launch and the step queue run with termination inside (k_rollout_packed_term) instead of falling back to step launches
+  bool horizon_term = false;
   // the truncation log (DM_OPT_TRUNCATION_LOG, dm_batch_truncations): trunc_cap records, allocated when the option is set; trunc_tick = step calls since it was cleared
   int trunc_cap = 0, trunc_tick = 0; int *d_trunc_count = nullptr, *d_trunc_index = nullptr; double *d_trunc_qpos = nullptr, *d_trunc_qvel = nullptr;
 };

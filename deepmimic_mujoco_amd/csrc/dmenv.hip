@@ -397,6 +397,9 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
       }
       break;
     }
+    case DM_OPT_HORIZON_TERMINATION:
+      if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_HORIZON_TERMINATION must be 0 or 1");
+      b->horizon_term = v != 0; break;
     case DM_OPT_PIPELINE: {
       if (v < 1 || v > DM_MAX_PIPELINE) return fail(DM_EINVAL, "pipeline depth must be 1..DM_MAX_PIPELINE");
       HIPCHK(hipSetDevice(b->device));
@@ -466,7 +469,8 @@ extern "C" int dm_batch_reset(dm_batch* b, int32_t mode, int32_t hard, const uin
 }
 
 // the packed path covers this batch's configuration (reward modes alive / v3-config / v2-pose / imitation, the two-tier kernel family)
-// early termination is on: k_terminate follows every per-step launch; the horizon launch and the step queue carry no termination code
+// early termination is on: k_terminate follows every per-step launch; the horizon launch and the step queue carry no termination code, unless
+// DM_OPT_HORIZON_TERMINATION asks for the horizon kernel that does (k_rollout_packed_term)
 static bool term_on(const dm_batch* b) { return b->fall_bodies != 0u || b->max_episode_steps > 0; }
 static bool packed_covers(const dm_batch* b) { return b->packed && b->B.reward_mode <= 4 && b->two_tier; }
 // a dm_batch_step call may be queued: device pointers, no fused policy step, no per-stage profiling, and a configuration for which ONE launch
@@ -477,9 +481,9 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
   // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches;
-  //  so do those of a batch with early termination on)
+  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && b->B.action_mode <= 2 && !term_on(b) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -494,10 +498,18 @@ static int ensure_rows(dm_batch* b, int T) {
   b->rows_cap = cap;
   return DM_OK;
 }
-// T steps of every environment in ONE launch (k_rollout_packed) on the batch's stream; b->d_rows[0 .. T) has been written on that stream
+// T steps of every environment in ONE launch (k_rollout_packed) on the batch's stream; b->d_rows[0 .. T) has been written on that stream.
+// With early termination on (rollout_as_one_launch: DM_OPT_HORIZON_TERMINATION then) the launch is k_rollout_packed_term, whose steps count as T
+// step calls on the truncation log's clock: step t's records carry the tick a dm_batch_step call in its place would have had.
 static int launch_horizon(dm_batch* b, int T, int nsub, const dmp::PolicyArgs& pa) {
   hipLaunchKernelGGL(k_put_batch, dim3(1), dim3(64), 0, b->stream, b->B, b->d_B);
   if (b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+  if (term_on(b)) {
+    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, 0, b->n,
+                      b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->trunc_cap, b->trunc_tick};
+    if (b->trunc_cap > 0) b->trunc_tick += T;
+    hipLaunchKernelGGL(k_rollout_packed_term, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->d_rows, (int)nsub, 0, b->n, (int)T, pa, b->prof ? b->d_prof : (long long*)nullptr, ta);
+  } else
   hipLaunchKernelGGL(k_rollout_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->d_rows, (int)nsub, 0, b->n, (int)T, pa, b->prof ? b->d_prof : (long long*)nullptr);
   if (b->timing) { HIPCHK(hipEventRecord(b->ev1, b->stream)); b->ev_pending = true; }
   // dispatch order for the next launch: environments with similar row counts share a wave (and, for per-step launches, longest first)

@@ -527,9 +527,16 @@ struct StepRow { const double* action; double* obs; double* reward; unsigned cha
 // population / the judged line, M env-steps/s): margin 3 (30 rows): 9.45 / 17.95, 1.4 % of env-steps still re-stepped (a foot landing takes an env from 28 to
 // 33 rows in one step); margin 9 (24 rows): 9.68 / 17.94, 0.26 %; margin 15 (18 rows): 9.74 / 17.76, 0.05 %; round 4's kernel: 6.98 / 17.83, 13.9 %.
 constexpr int EXT_MARGIN = DM_EXT_MARGIN;
-template <class R, int NR, class POLICY>
+// TERM: the compile-time switch for early termination inside the loop (slot_term.h SlotTermination, k_rollout_packed_term).  NoTermination — every other
+// caller's — compiles no trace of it: the phase's call stands under `if constexpr` and the functor is an empty object nobody reads.
+struct NoTermination { static constexpr bool on = false; };
+template <class T> struct TermSwitch { static constexpr bool on = T::on; };
+template <class T> struct TermSwitch<T&> : TermSwitch<T> {};
+template <class T> struct TermSwitch<const T> : TermSwitch<T> {};
+template <class R, int NR, class POLICY, class TERM = NoTermination>
 DM_DEV void slot_rollout(const DevModel<R>& M_in, const Batch<R>& B, SlotShared<R>* sh, SlotTables& tb, Shared<R>& one_s, StepScratch<R>& one_x,
-                         int env, int lane, bool live, const StepRow* rows, int n_substeps, int T, POLICY&& policy, long long* prof_acc = 0, bool policy_clobbers_kin = false) {
+                         int env, int lane, bool live, const StepRow* rows, int n_substeps, int T, POLICY&& policy, long long* prof_acc = 0, bool policy_clobbers_kin = false,
+                         TERM&& term = TERM()) {
   const int slot = lane >> 4, sl = lane & 15;
   int carry = 0;                              // the slots' LDS is what this wave's previous step left (no in-wave re-step overwrote it): slot_env_step kin_carry
   // rows the slot's environment held after its last step: decides which instantiation of the step this wave calls next (wave-uniform: the largest of the four)
@@ -572,6 +579,9 @@ DM_DEV void slot_rollout(const DevModel<R>& M_in, const Batch<R>& B, SlotShared<
       if (lane == 0) dmw::global_counter_next(B.redo_why);       // running total (dm_batch_redo_total)
       dmw::sync_mem();
     }
+    // early termination (DM_OPT_HORIZON_TERMINATION): on the state the step and its re-steps left, ahead of the policy, which acts on the observation
+    // of the episode termination leaves (step -> k_terminate -> policy of the step launches)
+    if constexpr (TermSwitch<TERM>::on) term(&M, &B, &sh[slot], t, env, sl, lane, live, any, o_t, d_t DM_CALL_SLOT_ARG);
     if (any) {                                                   // the slots' LDS may have been overwritten: the policy's inputs again
 #pragma unroll
       for (int c = 0; c < (NOBS + SW - 1) / SW; c++) {

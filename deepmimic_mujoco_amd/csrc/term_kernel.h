@@ -30,6 +30,7 @@ struct TermArgs {
   int log_cap, tick;       // capacity in records; the batch's step calls since the log was cleared
 };
 
+#ifndef DM_TERM_ARGS_ONLY      // (slot_term.h — the horizon launch's termination phase, a unit of its own — wants the struct alone)
 // bit g (1..15) of the result: geom g touches the floor at the kinematics in `s` (wave-collective; the same value in every lane)
 DM_DEV unsigned floor_touch_mask(const DevModel<Real>& M, const Shared<Real>& s, int lane) {
   bool t = false;
@@ -100,3 +101,4 @@ __global__ void k_zero_masked(int* __restrict__ v, const unsigned char* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && (!mask || mask[i])) v[i] = 0;
 }
+#endif  // DM_TERM_ARGS_ONLY

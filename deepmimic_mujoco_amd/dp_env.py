@@ -409,7 +409,8 @@ class DPVecEnv(object):
 
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
-                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False):
+                 step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False,
+                 horizon_termination=False):
         """reward_terms (reward="imitation" only, else ValueError): after every `step` one more launch (Batch.imitation_terms) takes the reward the step
         returned apart, and `last_reward_terms` is the [N, 28] float64 rows (imitation.py has the columns: the five errors, the five weighted terms, their
         sum — the step's reward —, the joint groups' shares of the pose error, the end effectors' distances), numpy or device tensor like the step's
@@ -423,6 +424,11 @@ class DPVecEnv(object):
         ankles; "crawl": root, chest, neck), or body names / ids; None: off.  max_episode_steps: the episode's limit in env steps; 0: off.  While either is on,
         one more launch follows every step launch, ends the episodes of the environments that fell or ran out of steps (done = 1, `done_reason()` says why) and,
         with `autoreset`, starts their next episode as the step itself does on its own done; horizon launches and the step queue fall back to step launches.
+        horizon_termination (DM_OPT_HORIZON_TERMINATION; needs `fall_contact_bodies` or `max_episode_steps`): keep the one-launch horizon instead — `Batch.rollout`,
+        the fused collector and the step queue run a horizon kernel with the termination rule inside every wavefront's loop (step, termination, then the
+        policy's step), with the step launches' results.  The flag takes effect where `Batch.rollout` uses one launch per horizon at all (a packed batch: `packed=True` / 2, the automatic choice, or a collector that
+        picks the packed horizon — `horizon_packed_ok`); on a one-env batch it changes nothing.  ValueError for the two combinations that never have a horizon launch: the
+        "spd-target" / "spd-mocap" action modes and obs_mode="deepmimic".
         reward="imitation": the 5-term reward of code.md:1017-1143 (imitation.py) against the frame after the current one.
         frame_skip: sim steps per env step (src/dp_env_v3.py:108-112 hard-codes 1); "mocap" = floor(mocap_dt / timestep), the
         commented intent of :107-110, so that one env step spans one mocap frame.  Default (None): 1, except "mocap" for the
@@ -450,6 +456,14 @@ class DPVecEnv(object):
         the fresh episode's features — the convention of the 56-wide observation.  The features call runs queued steps first, so with `step_queue`
         every `step` is executed at once, as in the closed loop."""
         self.num_envs = int(num_envs)
+        self.horizon_termination = bool(horizon_termination)
+        if self.horizon_termination:               # (refused before anything touches a device)
+            if not (fall_body_mask(fall_contact_bodies) or int(max_episode_steps)):
+                raise ValueError("horizon_termination=True runs early termination inside the horizon launch: it needs fall_contact_bodies or max_episode_steps")
+            if action_mode in ("spd-target", "spd-mocap"):
+                raise ValueError("horizon_termination=True: action_mode=%r runs on the per-step kernels, there is no horizon launch to terminate in" % (action_mode,))
+            if obs_mode == "deepmimic":
+                raise ValueError("horizon_termination=True: obs_mode=\"deepmimic\" takes a features launch after every step, there is no horizon launch to terminate in")
         self.obs_mode = obs_mode
         self._obs_width = obs_width(obs_mode)
         self._ob56 = None
@@ -505,12 +519,15 @@ class DPVecEnv(object):
             b.set_option(A.OPT_MAX_EPISODE_STEPS, self.max_episode_steps)
         if int(truncation_log):
             b.set_option(A.OPT_TRUNCATION_LOG, int(truncation_log))
+        if self.horizon_termination:
+            b.set_option(A.OPT_HORIZON_TERMINATION, 1)
         rowless = not (contacts or limits)          # no constraint rows: every wave costs the same, the packed kernel wins at any batch size
         auto = packed is None and batch_factory is None and (self.num_envs >= PACKED_FROM_ENVS or (rowless and self.num_envs >= 256)) and dtype == 64
         # a horizon launch (Batch.rollout, rollout.SegmentCollector) may use the packed kernel at ANY batch size: there a wave does not wait
         # for the slowest wave of every step
-        # (with early termination on there is no horizon launch: a horizon is step launches, for which the per-step choice above holds)
-        self.horizon_packed_ok = packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64 and not (self.fall_body_mask or self.max_episode_steps)
+        # (with early termination on there is no horizon launch unless `horizon_termination`: a horizon is step launches, for which the per-step choice above holds)
+        self.horizon_packed_ok = (packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64
+                                  and (self.horizon_termination or not (self.fall_body_mask or self.max_episode_steps)))
         if packed or auto:
             b.set_option(A.OPT_PACKED, 2 if (packed is not True and packed == 2) else 1)     # (packed=2: per-step launches with the three-set code, see the docstring)
         if auto:

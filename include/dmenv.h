@@ -186,12 +186,12 @@ enum {
                              hard: time and warm start zeroed, the episode counter, the frame cursors and DM_F_CYCLE as there) and writes
                              the fresh episode's observation row.  Host-pointer steps copy out after this launch.  The step kernels carry
                              no termination code: with both options 0 nothing is launched and nothing changes.  Neither do the horizon
-                             launch and the step queue: while an option is on, dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches
+                             launch and the step queue, unless DM_OPT_HORIZON_TERMINATION: while an option is on and that one is not, dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches
                              (as for action modes 3 and 4; dm_batch_queue_stats stays 0), and dm_batch_step_act and the policy rows of
                              dm_batch_rollout run as the plain step launch, the termination launch, then the launch behind dm_policy_act
                              on the returned observations (over the whole batch, after the parts of a pipelined step have joined): the
                              result of dm_batch_step followed by dm_policy_act, bit for bit. */
-  DM_OPT_TRUNCATION_LOG = 11 /* the truncation log's capacity C in records.  0 (default): off; negative: DM_EINVAL.  It has an effect only while
+  DM_OPT_TRUNCATION_LOG = 11, /* the truncation log's capacity C in records.  0 (default): off; negative: DM_EINVAL.  It has an effect only while
                              DM_OPT_MAX_EPISODE_STEPS > 0.  A time limit truncates an infinite-horizon task: the state it cuts off is worth the
                              critic's value, not 0 as after a fall, and with DM_OPT_AUTORESET the termination launch overwrites that state.  With
                              C > 0 it first appends a record for every episode it ends by the time limit ALONE (DM_F_DONE_REASON exactly
@@ -203,6 +203,29 @@ enum {
                              wavefronts arrived (the parts of a pipelined step share the one counter) and carries no meaning: key on
                              (tick, env).  Setting the option (again) joins the batch, waits for its stream, reallocates and clears the log and the
                              tick.  Off, the termination launch is bit for bit what it is without the option.  dm_batch_truncations reads it. */
+  DM_OPT_HORIZON_TERMINATION = 12 /* 0 (default): as described under DM_OPT_MAX_EPISODE_STEPS — while early termination is on, dm_batch_rollout and
+                             DM_OPT_STEP_QUEUE issue step launches, each followed by the termination launch.  1: early termination no longer keeps a
+                             batch from the one-launch horizon.  Where dm_batch_rollout would use one launch per horizon without termination
+                             (DM_OPT_PACKED on, action modes 0..2, constraint rows, at most two packed waves per SIMD — the conditions are unchanged)
+                             it does so with it, and DM_OPT_STEP_QUEUE queues again (dm_batch_queue_stats counts): the launch is a second horizon
+                             kernel (k_rollout_packed_term) with the termination rule inside every wavefront's loop.  Order within a step of the
+                             horizon: the step (with its in-wave re-steps), then termination on the state it left, then — dm_batch_rollout with
+                             weights — the policy's step, which therefore acts on the observation of the episode termination leaves; the result is
+                             that of dm_batch_step, the termination launch and dm_policy_act step after step.  done, DM_F_DONE_REASON,
+                             DM_F_EPISODE_STEPS, the reset under DM_OPT_AUTORESET, the fresh observation row and the truncation log follow the
+                             termination launch's rule to the letter (the step's own done only records its reason; the reward row is left alone; a
+                             record for an episode the time limit ALONE ends); as for a step-launch rollout only the last step's reasons remain in
+                             DM_F_DONE_REASON.  Ticks: step t of a horizon launch that starts at tick k logs with tick k + t, and the launch advances
+                             the batch's tick by its T steps, so a record's tick is the step call's index since the log was cleared whichever way
+                             the steps were launched.  The fall test runs on the four-per-wavefront kinematics, which differ from the termination
+                             launch's in the last bits: a geom within rounding of the touch boundary may be decided differently.  Apart from that the
+                             result is bit for bit the step launches' where both forms run the same step code: DM_OPT_PACKED 2, or DM_OPT_PACKED 1
+                             while no environment holds 33..40 constraint rows.  An env-step at 33..40 rows stays on the packed three-set code in any
+                             horizon launch while DM_OPT_PACKED 1's step launches hand it to the one-env code, whose float64 sums differ in the last
+                             bits (with or without termination; measured 1e-14 on observations): done flags, reasons, counters, cursors and the
+                             records' ticks and environments stay equal, float rows and state agree to rounding.  Values other than 0 and 1: DM_EINVAL.  Without early termination, and for
+                             everything that is not a horizon launch (dm_batch_step unqueued, dm_batch_step_act, action modes 3 and 4), the option
+                             changes nothing.  Measured on an MI355X (profiles/term_horizon.md): a 128-step fused rollout 1.66x faster at 4096 envs, 1.38x at 8192. */
 };
 /* bits of DM_F_DONE_REASON */
 #define DM_DONE_STEP 1       /* the step's own done: COM height outside (0.7, 2.0), or the end of a "Loop: none" clip */

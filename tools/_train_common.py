@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk")
     if reward_help:
         ap.add_argument("--reward", default="alive", help=reward_help)
@@ -23,6 +23,9 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
                          "crawl = root, chest, neck (the floor clips); none (default) = only the reference's centre-of-mass rule")
     ap.add_argument("--max-episode-steps", type=int, default=0,
                     help="the episode's time limit in env steps (0 = none).  Without --bootstrap-time-limit a time-limit done is a done like any other: the state it cuts off is worth 0")
+    ap.add_argument("--horizon-termination", action="store_true",
+                    help="run early termination inside the horizon launch (DM_OPT_HORIZON_TERMINATION) instead of a termination launch behind every step launch: "
+                         "needs --fall-contact or --max-episode-steps, and an action / observation mode with a horizon launch (not spd-*, not --obs-mode deepmimic)")
     ap.add_argument("--bootstrap-time-limit", action="store_true",
                     help="treat a time-limit end as a truncation (DeepMimic's agent): the value target bootstraps from the critic's value of the state the limit cut off, "
                          "where a fall keeps 0.  Needs --max-episode-steps")
@@ -39,6 +42,11 @@ def check_env_args(ap, args):
     """Refuse flag combinations that cannot work, with the parser's own error message."""
     if getattr(args, "bootstrap_time_limit", False) and not args.max_episode_steps > 0:
         ap.error("--bootstrap-time-limit bootstraps the value where the time limit ends an episode: it needs --max-episode-steps M with M > 0")
+    if getattr(args, "horizon_termination", False):
+        if args.fall_contact == "none" and not args.max_episode_steps > 0:
+            ap.error("--horizon-termination runs early termination inside the horizon launch: it needs --fall-contact or --max-episode-steps")
+        if args.action_mode in ("spd-target", "spd-mocap") or args.obs_mode == "deepmimic":
+            ap.error("--horizon-termination: --action-mode spd-* and --obs-mode deepmimic have no horizon launch")
     if getattr(args, "log_reward_terms", False) and getattr(args, "reward", None) != "imitation":
         ap.error("--log-reward-terms takes the imitation reward apart: it needs --reward imitation")
 
@@ -48,7 +56,8 @@ def env_kwargs(args):
     fs = getattr(args, "frame_skip", None)
     return dict(motion=args.motion, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
                 frame_skip=fs if fs in (None, "mocap") else int(fs),
-                fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps)
+                fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps,
+                horizon_termination=bool(getattr(args, "horizon_termination", False)))
 
 
 def init_device(dist_backend):

@@ -18,7 +18,10 @@ section of its own.
 `--resources-before file.md`: the table tools/kernel_resources.py printed for the library BEFORE the feature; the report lists the step
 kernels' rows of both and says whether any pre-existing kernel changed.  `--ab file`: the alternating parent / this-build lines of the
 default benchmark (tools/ab_bench.sh's form), quoted in the report.
-usage: python tools/term_bench.py --truncation-log [--limit 10] [--envs 4096 8192] [--stats N=csv ...] [--resources-before file.md] [--train-json file]
+`--horizon`: DM_OPT_HORIZON_TERMINATION (termination inside the horizon launch) off against on, and against the horizon launch without termination: one
+fused-policy dm_batch_rollout per window, the legs alternating in one process; one JSON line per size (profiles/term_horizon.md quotes them).
+usage: python tools/term_bench.py --horizon [--envs 4096 8192] [--steps 128] [--reps 5]
+       python tools/term_bench.py --truncation-log [--limit 10] [--envs 4096 8192] [--stats N=csv ...] [--resources-before file.md] [--train-json file]
        python tools/term_bench.py [--envs 4096 8192] [--steps 200] [--warmup 30] [--reps 5] [--stats N=csv ...] [--resources-before file.md]
                                   [--ab file] [--out profiles/term_kernels.md]
        rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python tools/term_bench.py --trace 4096"""
@@ -215,10 +218,62 @@ def report(results, stats, args, device):
     return "\n".join(L) + "\n"
 
 
+def horizon_bench(args):
+    """--horizon: DM_OPT_HORIZON_TERMINATION off against on.  A window is one `--steps`-step dm_batch_rollout with the fused policy step (walk, 5-term
+    reward, RSI auto-reset, the "deepmimic" fall set) closed by a device synchronise; the option's two values ALTERNATE in one process, `--reps` windows
+    each after a warm-up rollout per value.  A third leg, `plain`, is the horizon launch WITHOUT termination on the same workload: on / plain is the
+    cost of the termination phase plus the shift in episode lengths.  Prints one JSON line per size; the report is profiles/term_horizon.md's."""
+    import torch
+    from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
+    dev = torch.device("cuda", 0)
+    T = args.steps
+    lines = []
+    for n in args.envs:
+        pol = MlpPolicy(device=dev, seed=2); pol.seed(5)
+        W = pol.pack()
+        ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=dev)
+        out = (torch.zeros((T, n, 56), dtype=torch.float64, device=dev), torch.zeros((T, n), dtype=torch.float64, device=dev), torch.zeros((T, n), dtype=torch.uint8, device=dev))
+        vp = torch.zeros((T, n), dtype=torch.float32, device=dev)
+        legs = {"off": dict(fall_contact_bodies="deepmimic", horizon_termination=False), "on": dict(fall_contact_bodies="deepmimic", horizon_termination=True), "plain": {}}
+        envs = {k: DPVecEnv(n, motion="walk", device=0, reward="imitation", autoreset="rsi", seed=1, packed=True, **kw) for k, kw in legs.items()}
+        ms = {k: [] for k in legs}
+        dones, redo = {}, {}
+        for rep in range(args.reps + 1):                                 # (window 0 of every leg is its warm-up)
+            for k, env in envs.items():
+                b = env.batch
+                env.reset("rsi")
+                r0 = b.redo_total()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                b.rollout(ac, out, env.frame_skip, W, vp, True, 5, 7)
+                b.join(); torch.cuda.synchronize()
+                if rep:
+                    ms[k].append(1e3 * (time.perf_counter() - t0))
+                dones[k] = int(out[2].sum().item()); redo[k] = b.redo_total() - r0
+        stats = envs["on"].batch.queue_stats()
+        for env in envs.values():
+            env.close()
+        row = dict(envs=n, steps=T, device=torch.cuda.get_device_name(0))
+        for k in legs:
+            v = sorted(ms[k])
+            row[k] = dict(median_ms=round(float(np.median(v)), 3), min_ms=round(v[0], 3), max_ms=round(v[-1], 3),
+                          menv_steps_per_s=round(n * T / float(np.median(v)) / 1e3, 3), episodes_ended=dones[k], restepped_env_steps=redo[k])
+        row["on_over_off"] = round(row["off"]["median_ms"] / row["on"]["median_ms"], 3)
+        row["on_over_plain_time"] = round(row["on"]["median_ms"] / row["plain"]["median_ms"], 3)
+        # the phase reuses a wave's carried kinematics unless one of its environments was re-stepped in that step (5-term reward): at most one wave-step per re-stepped env-step recomputes
+        row["wave_steps"] = (n + 3) // 4 * T
+        row["wave_steps_recomputed_at_most"] = redo["on"]
+        row["queue_stats_on"] = stats
+        print(json.dumps(row)); sys.stdout.flush()
+        lines.append(row)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--horizon", action="store_true", help="DM_OPT_HORIZON_TERMINATION off / on / the horizon launch without termination, alternating (--steps = the horizon, default 128)")
     ap.add_argument("--envs", type=int, nargs="*", default=[4096, 8192])
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="steps per window (default 200; --horizon: the horizon, default 128)")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace", type=int, default=0)
@@ -230,6 +285,11 @@ def main():
     ap.add_argument("--train-json", default=None, help="--truncation-log: a file of training iteration times to quote")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "term_kernels.md"))
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 128 if args.horizon else 200
+    if args.horizon:
+        horizon_bench(args)
+        return
     if args.trace:
         trace_run(args.trace, args.steps, args.warmup, args)
         return
