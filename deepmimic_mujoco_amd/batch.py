@@ -56,11 +56,25 @@ def _view_args(ptr, n_batch, device, state, env_ids, outs, who):
     return n, in_ptrs, out_ptrs, kinds.pop(), keep, objs
 
 
+def batch_option(batch, opt, default=0):
+    """Option `opt` as last set on `batch`.  The one place that tolerates batches that are not `Batch` (DPVecEnv(batch_factory=...): the emulator's
+    and the host tests' batches keep no `options`): they read as `default`."""
+    return int(getattr(batch, "options", {}).get(int(opt), default))
+
+
 class Batch(object):
     def __init__(self, compiled_model, data_config, data_vel, n_envs, device=0, flags=0, mocap_dt=0.0, imitation=None, dtype=64):
         """dtype: arithmetic / device-state type of the kernels, 64 (default: the parity path) or 32 (the float32 build of the same
         source, libdmenv32.so: faster; per step ~4e-7 of the observation scale at the median and ~4e-6 at worst against a float64 evaluation
         of the same float32-rounded state, the error of any float32 evaluation: DESIGN.md section 5).  Buffers are float64 either way."""
+        # the Python side's own state, all of it
+        self.options = {}                  # what set_option has set, by option number
+        self._stream_handle = None         # the stream the library was last told to use (None: its own; no device tensor seen yet)
+        self._render_descs = {}            # render(): camera descriptions by (size, model camera, visual table)
+        self._queue_refs = None            # OPT_STEP_QUEUE: the tensors of the steps that may still be queued
+        self._auto = False                 # the per-step kernel chooser (enable_auto_packed) and its window
+        self._auto_ctr = self._redo_last = self._redo_rows_last = self._calm_checks = 0
+        self.auto_switches = None          # (None: this batch never had a chooser)
         L = A.load(dtype)
         self.dtype = int(dtype)
         self._L = L
@@ -115,7 +129,7 @@ class Batch(object):
             # device buffers are ordered on the batch's stream: follow torch's current stream so that kernels producing
             # the tensor (e.g. the policy, torch.randn) and our launch are serialised without extra synchronisation
             cur = torch.cuda.current_stream(x.device).cuda_stream
-            if cur != getattr(self, "_stream_handle", None):
+            if cur != self._stream_handle:
                 self.set_stream(cur)
             return C.c_void_p(x.data_ptr()), A.PTR_DEVICE, x
         a = x if out else np.ascontiguousarray(x, dtype=dtype)
@@ -123,11 +137,9 @@ class Batch(object):
             raise ValueError("array must be C-contiguous %s of shape %s" % (np.dtype(dtype), shape))
         return C.c_void_p(a.ctypes.data), A.PTR_HOST, a
 
-    _queue_refs = None
-
     def set_option(self, opt, value):
         A.check(self._L.dm_batch_set_option(self._h, int(opt), int(value)), self._L)
-        self.__dict__.setdefault("options", {})[int(opt)] = int(value)
+        self.options[int(opt)] = int(value)
         if int(opt) == A.OPT_STEP_QUEUE:
             self._queue_refs = [] if int(value) > 0 else None
 
@@ -140,8 +152,7 @@ class Batch(object):
     @property
     def can_step_act(self):
         """dm_batch_step_act needs the two-tier kernel (option 102, default on) and no per-stage profiling (option 101)."""
-        o = self.__dict__.get("options", {})
-        return o.get(102, 1) != 0 and o.get(101, 0) == 0
+        return self.options.get(102, 1) != 0 and self.options.get(101, 0) == 0
 
     def set_stream(self, stream_handle):
         A.check(self._L.dm_batch_set_stream(self._h, C.c_void_p(int(stream_handle))), self._L)
@@ -177,16 +188,27 @@ class Batch(object):
         self._redo_last = r[0]; self._redo_rows_last = r[4]
         self._calm_checks = 0
 
+    def suspend_auto(self):
+        """Switch the chooser off for a caller that picks the kernel itself for a while (rollout.HorizonKernelChoice); its counters stay.
+        -> whether it was on.  With `resume_auto` the only way anything outside this class touches the chooser."""
+        was, self._auto = self._auto, False
+        return was
+
+    def resume_auto(self):
+        """the chooser on again after `suspend_auto`, its window starting where the redo counters stand now"""
+        self._auto = True
+        self.rebaseline_auto()
+
     def _adapt(self):
         self._auto_ctr += 1
         if self._auto_ctr % self.ADAPT_EVERY:
             return
-        mode = int(self.__dict__.get("options", {}).get(A.OPT_PACKED, 0))
+        mode = self.options.get(A.OPT_PACKED, 0)
         if mode:
             reasons = self.redo_reasons()
             redo = reasons[0]
             rate = (redo - self._redo_last) / float(self.ADAPT_EVERY * self.n)
-            rows_share = (reasons[4] - self.__dict__.get("_redo_rows_last", 0)) / float(max(1, redo - self._redo_last))
+            rows_share = (reasons[4] - self._redo_rows_last) / float(max(1, redo - self._redo_last))
             self._redo_last = redo; self._redo_rows_last = reasons[4]
             if rate > self.REDO_RATE_MAX:
                 self._calm_checks = 0
@@ -206,6 +228,22 @@ class Batch(object):
                 self.rebaseline_auto()
 
     # ---- the hot path -------------------------------------------------------------------------------
+    def _out_ptrs(self, out, lead, kind, error):
+        """out = (obs, rew, done) with the leading shape `lead` -> their three pointers, every one of pointer kind `kind`: else ValueError(error)"""
+        obs, rew, done = out
+        op, k1, _ = self._ptr(obs, np.float64, lead + (A.NOBS,), out=True)
+        rp, k2, _ = self._ptr(rew, np.float64, lead, out=True)
+        dp, k3, _ = self._ptr(done, np.uint8, lead, out=True)
+        if not (kind == k1 == k2 == k3):
+            raise ValueError(error)
+        return op, rp, dp
+
+    def _weights_ptr(self, weights):
+        import torch
+        if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == self._L.dm_policy_weight_count()):
+            raise ValueError("weights: the packed float32 policy block (MlpPolicy.pack()) on the device")
+        return C.c_void_p(weights.data_ptr())
+
     def _step_device(self, action, n_substeps, out):
         """`step` for device tensors with every buffer given: the same checks as `_ptr`, written out once (the generic path costs ~10 us
         of Python per call — 4 % of a 250 us step).  Returns None when the arguments are not of that form."""
@@ -224,7 +262,7 @@ class Batch(object):
         if (dev.index or 0) != self.device or obs.device != dev or rew.device != dev or done.device != dev:
             return None
         cur = torch.cuda.current_stream(dev).cuda_stream
-        if cur != getattr(self, "_stream_handle", None):
+        if cur != self._stream_handle:
             self.set_stream(cur)
         rc = self._L.dm_batch_step(self._h, action.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr(), int(n_substeps), A.PTR_DEVICE)
         if rc:
@@ -236,7 +274,7 @@ class Batch(object):
         return out
 
     def step(self, action, n_substeps=1, out=None):
-        if self.__dict__.get("_auto"):
+        if self._auto:
             self._adapt()
         if out is not None:
             r = self._step_device(action, n_substeps, out)
@@ -253,11 +291,7 @@ class Batch(object):
             else:
                 out = (np.empty((n, A.NOBS)), np.empty(n), np.empty(n, dtype=np.uint8))
         obs, rew, done = out
-        op, k1, _ = self._ptr(obs, np.float64, (n, A.NOBS), out=True)
-        rp, k2, _ = self._ptr(rew, np.float64, (n,), out=True)
-        dp, k3, _ = self._ptr(done, np.uint8, (n,), out=True)
-        if not (kind == k1 == k2 == k3):
-            raise ValueError("action and output buffers must all be host arrays or all be device tensors")
+        op, rp, dp = self._out_ptrs(out, (n,), kind, "action and output buffers must all be host arrays or all be device tensors")
         A.check(self._L.dm_batch_step(self._h, ap, op, rp, dp, int(n_substeps), kind), self._L)
         if self._queue_refs is not None and kind == A.PTR_DEVICE:
             # OPT_STEP_QUEUE: the call may only have been queued — its tensors must outlive the flush (any other entry point of the batch)
@@ -270,24 +304,21 @@ class Batch(object):
         """`step` followed, inside the step kernel, by the policy's step on the new observations (dm_batch_step_act): device tensors
         only.  action [n, 28] f64 -> out = (obs [n, 56] f64, rew [n] f64, done [n] u8); next_action [n, 28] f64 and next_vpred [n] f32
         receive the action / value for those observations; `weights` is MlpPolicy.pack()'s float32 block."""
-        if self.__dict__.get("_auto"):
+        if self._auto:
             self._adapt()
         n = self.n
         ap, kind, _ka = self._ptr(action, np.float64, (n, A.NU))
-        obs, rew, done = out
-        op, k1, _ = self._ptr(obs, np.float64, (n, A.NOBS), out=True)
-        rp, k2, _ = self._ptr(rew, np.float64, (n,), out=True)
-        dp, k3, _ = self._ptr(done, np.uint8, (n,), out=True)
         np_, k4, _ = self._ptr(next_action, np.float64, (n, A.NU), out=True)
-        if not (kind == k1 == k2 == k3 == k4 == A.PTR_DEVICE):
+        if not (kind == k4 == A.PTR_DEVICE):
             raise ValueError("step_act works on device tensors")
+        op, rp, dp = self._out_ptrs(out, (n,), A.PTR_DEVICE, "step_act works on device tensors")
+        wp = self._weights_ptr(weights)
         import torch
-        if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == self._L.dm_policy_weight_count()):
-            raise ValueError("weights: the packed float32 policy block (MlpPolicy.pack()) on the device")
         if not (next_vpred.is_cuda and next_vpred.dtype == torch.float32 and next_vpred.is_contiguous() and next_vpred.numel() == n):
             raise ValueError("next_vpred: float32 [n] on the device")
-        A.check(self._L.dm_batch_step_act(self._h, ap, op, rp, dp, int(n_substeps), C.c_void_p(weights.data_ptr()), np_,
+        A.check(self._L.dm_batch_step_act(self._h, ap, op, rp, dp, int(n_substeps), wp, np_,
                                           C.c_void_p(next_vpred.data_ptr()), 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), int(counter)), self._L)
+        obs, rew, done = out
         return obs, rew, done
 
     def rollout(self, action, out, n_substeps=1, weights=None, vpred=None, stochastic=True, seed=0, counter=0):
@@ -299,18 +330,15 @@ class Batch(object):
         obs, rew, done = out
         T, n = int(obs.shape[0]), self.n
         ap, k0, _ = self._ptr(action, np.float64, (T + 1, n, A.NU), out=True)
-        op, k1, _ = self._ptr(obs, np.float64, (T, n, A.NOBS), out=True)
-        rp, k2, _ = self._ptr(rew, np.float64, (T, n), out=True)
-        dp, k3, _ = self._ptr(done, np.uint8, (T, n), out=True)
-        if not (k0 == k1 == k2 == k3 == A.PTR_DEVICE):
+        if k0 != A.PTR_DEVICE:
             raise ValueError("rollout works on device tensors")
+        op, rp, dp = self._out_ptrs(out, (T, n), A.PTR_DEVICE, "rollout works on device tensors")
         wp = vp = None
         if weights is not None:
-            if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == self._L.dm_policy_weight_count()):
-                raise ValueError("weights: the packed float32 policy block (MlpPolicy.pack()) on the device")
+            wp = self._weights_ptr(weights)
             if vpred is None or not (vpred.is_cuda and vpred.dtype == torch.float32 and vpred.is_contiguous() and tuple(vpred.shape) == (T, n)):
                 raise ValueError("vpred: float32 [T, n] on the device")
-            wp, vp = C.c_void_p(weights.data_ptr()), C.c_void_p(vpred.data_ptr())
+            vp = C.c_void_p(vpred.data_ptr())
         A.check(self._L.dm_batch_rollout(self._h, ap, op, rp, dp, T, int(n_substeps), wp, vp, 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), int(counter)), self._L)
         return obs, rew, done
 
@@ -339,7 +367,7 @@ class Batch(object):
                                                          [(out.get(k),) + spec[k] for k in want], "render")
         ptrs = dict(zip(want, ps))
         key = (W, H, camera, id(visual)) if isinstance(camera, str) else None      # (model cameras: resolved once per size and visual table)
-        cache = self.__dict__.setdefault("_render_descs", {})
+        cache = self._render_descs
         desc = cache[key][0] if key in cache else None
         if desc is None:
             desc = R.make_desc(self.compiled_model, W, H, camera, visual)
@@ -399,10 +427,10 @@ class Batch(object):
         the last clear) then start again.  out: the four buffers, each of index / qpos / qvel optional (None: not copied), all numpy arrays (host:
         count is an int32 [1] array, the call waits once) or all tensors on the batch's device (count an int32 [1] tensor; stream-ordered, nothing
         waits).  Without `out`: device tensors when the batch has been stepped with device tensors (or device=True), else numpy arrays."""
-        C_ = int(self.__dict__.get("options", {}).get(A.OPT_TRUNCATION_LOG, 0))
+        C_ = self.options.get(A.OPT_TRUNCATION_LOG, 0)
         if out is None:
             if device is None:
-                device = getattr(self, "_stream_handle", None) is not None
+                device = self._stream_handle is not None
             if device:
                 import torch
                 where = "cuda:%d" % self.device

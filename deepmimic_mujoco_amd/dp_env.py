@@ -24,7 +24,7 @@ import random
 import numpy as np
 
 from . import _abi as A
-from .batch import Batch
+from .batch import Batch, batch_option
 from .config import Config
 from .humanoid import humanoid_spec, humanoid_visual
 from .mjcf import load_mjcf, load_visual
@@ -139,6 +139,7 @@ class DPEnv(object):
         171 state features (state_features.py) of the batch's state; their phase comes from the batch's cursor fields, which this class then writes from
         `idx_curr` / `idx_init` before every features call — for reward "alive" too, whose cursor never advances: its phase is the RSI draw."""
         self.mocap = MocapDM()
+        self._terms_batch = None                          # reward_terms(): a one-env batch of its own, made on the first call
         obs_width(obs_mode)
         self.obs_mode = obs_mode
         self._action_mode = action_mode
@@ -191,7 +192,7 @@ class DPEnv(object):
     def close(self):
         if self._batch is not None:
             self._batch.close(); self._batch = None
-        if getattr(self, "_terms_batch", None) is not None:
+        if self._terms_batch is not None:
             self._terms_batch.close(); self._terms_batch = None
 
     def reward_terms(self, frame=None, cycle=0):
@@ -201,8 +202,8 @@ class DPEnv(object):
         name, and "root") and "end_effectors" (squared distances).  This class steps with the reference's rewards, so the call is the explicit form of
         Batch.imitation_terms on a one-env batch of its own that carries the clip's feature table, made on the first call."""
         from .imitation import END_EFFECTORS, TERM_NAMES, ImitationSpec, O_TERM_ERR, O_TERM_VALUE, O_TERM_REWARD, O_TERM_JOINT, O_TERM_ENDEFF
-        if getattr(self, "_terms_batch", None) is None or self._terms_clip is not self.mocap.data_config:
-            if getattr(self, "_terms_batch", None) is not None:
+        if self._terms_batch is None or self._terms_clip is not self.mocap.data_config:
+            if self._terms_batch is not None:
                 self._terms_batch.close()
             self._terms_spec = ImitationSpec(self._cm)
             self._terms_batch = Batch(self._cm, self.mocap.data_config, self.mocap.data_vel, 1, device=self._device, mocap_dt=float(self.mocap_dt),
@@ -550,7 +551,7 @@ class DPVecEnv(object):
     @property
     def packed(self):
         """True while the batch steps four environments per wavefront (DM_OPT_PACKED; may change over a run with packed=None)"""
-        return bool(getattr(self._batch, "options", {}).get(A.OPT_PACKED, 0))
+        return bool(batch_option(self._batch, A.OPT_PACKED))
 
     def seed(self, seed):
         self._batch.set_option(A.OPT_SEED, int(seed))

@@ -1,57 +1,16 @@
-"""Multi-GPU sharding of the environment index range and the per-horizon rollout exchange.
+"""Device-resident rollouts: the batched form of the reference's `traj_segment_generator` and what it is made of.
 
-Environments are independent, so the only collective is the one the learner needs: every `horizon` steps each rank
-contributes its [T, N_local, 87] float32 block (obs 56 | action 28 | reward | done | vpred) to an all-gather
-(RCCL over xGMI when the backend is "nccl"; "gloo" in the CPU tests).  Env e of the global range lives on rank
-e // N_local, and per-env RNG streams are keyed by the GLOBAL env id, so results do not depend on the sharding.
+`SegmentCollector` is one env batch's side of the generator: `launch()` enqueues a horizon of policy and env steps, `collect()` turns the filled
+buffers into a `Segment`.  Its optional features are objects that own their state: `EpisodeScan` (the returns and lengths of the episodes that end in
+a segment; a second one for the env's own reward beside a reward giver's), `_TimeLimitBootstrap` (the critic's value of the states a time limit cut
+off) and `HorizonKernelChoice` (four environments per wavefront or one for the next horizon launch).  `traj_segment_generator` and
+`pipelined_segment_generator` drive one collector or several; `add_vtarg_and_adv` (GAE) and `flatten_segment` are what the learners apply to a segment.
+`env_obs_width` is the one place that knows how wide an env's observation is.  The multi-GPU exchange of rollout blocks lives in exchange.py; its names
+are re-exported here.
 """
-import numpy as np
+from .batch import batch_option
+from .exchange import ROW, DoubleBufferedGather, RolloutBlock, shard_range  # noqa: F401
 
-ROW = 87  # 56 obs + 28 act + reward + done + vpred
-
-
-def shard_range(n_global, rank, world):
-    """Contiguous block [lo, hi) of the global env range owned by `rank` (sizes differ by at most one)."""
-    base, rem = divmod(int(n_global), int(world))
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
-
-
-class RolloutBlock(object):
-    """Accumulates T steps of (obs, action, reward, done[, vpred]) for the local shard; all-gathers on demand."""
-
-    def __init__(self, horizon, n_local, device="cpu"):
-        import torch
-        self.T, self.n = int(horizon), int(n_local)
-        self.buf = torch.zeros((self.T, self.n, ROW), dtype=torch.float32, device=device)
-        self.t = 0
-
-    def append(self, obs, action, reward, done, vpred=None):
-        row = self.buf[self.t]
-        if obs.shape[-1] != 56:
-            raise ValueError("the rollout block's row is 87 wide (56 obs | 28 act | reward | done | vpred): observations of width %d (obs_mode "
-                             "'deepmimic') are not gathered" % obs.shape[-1])
-        row[:, :56] = obs; row[:, 56:84] = action; row[:, 84] = reward; row[:, 85] = done
-        if vpred is not None:
-            row[:, 86] = vpred
-        self.t += 1
-        return self.t == self.T
-
-    def gather(self, out=None):
-        """All ranks receive every rank's block: returns [world, T, n_local, 87].  Resets the fill counter."""
-        import torch
-        import torch.distributed as dist
-        self.t = 0
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return self.buf.unsqueeze(0)
-        world = dist.get_world_size()
-        if out is None:
-            out = torch.empty((world,) + tuple(self.buf.shape), dtype=self.buf.dtype, device=self.buf.device)
-        dist.all_gather_into_tensor(out.view(world * self.T, self.n, ROW), self.buf)
-        return out
-
-
-# ---- device-resident rollouts -----------------------------------------------------------
 
 def add_vtarg_and_adv(seg, gamma, lam):
     """GAE(lambda) of `src/trpo.py:83-94` for N environments at once.
@@ -112,16 +71,29 @@ def can_fuse(pi, env, device=None):
             and getattr(env.batch, "can_step_act", True) and getattr(env, "obs_mode", "dp_env_v3") == "dp_env_v3" and getattr(pi, "ob_dim", 0) == 56 and getattr(pi, "ac_dim", 0) == 28 and getattr(pi, "hid_size", 0) == 100)
 
 
-class _PendingEpisodes:
-    """Episode statistics of a segment whose records are still on their way to the host (SegmentCollector._episodes_native)."""
+def env_obs_width(env):
+    """Width of the observation `env` hands to a policy: the step launch's 56 numbers in obs_mode "dp_env_v3" (and for an env object that names no mode),
+    else what its observation space says (171 for "deepmimic")."""
+    if getattr(env, "obs_mode", "dp_env_v3") == "dp_env_v3":
+        return 56
+    return int(env.observation_space.shape[0])
 
-    def __init__(self, collector, event, slot="_ep"):
-        self.c, self.event, self.out, self.slot = collector, event, None, slot       # slot: which of the collector's record buffers
+
+def _pack_is_stale(pi):
+    """the fused launches read the policy's packed float32 block: True when `pi.pack()` has to run first"""
+    return getattr(pi, "_dirty", False) or getattr(pi, "_packed", None) is None
+
+
+class _PendingEpisodes:
+    """Episode statistics of a segment whose records are still on their way to the host (EpisodeScan.native)."""
+
+    def __init__(self, scan, event):
+        self.scan, self.event, self.out = scan, event, None
 
     def result(self):
         if self.out is None:
             import numpy as np
-            cnt, rec, h_cnt, h_rec = getattr(self.c, self.slot + "_buf")
+            _cnt, rec, h_cnt, h_rec = self.scan.records
             self.event.synchronize()
             k = min(int(h_cnt[0]), rec.shape[0])
             r = h_rec[:min(k, h_rec.shape[0])].numpy()
@@ -129,9 +101,87 @@ class _PendingEpisodes:
                 r = np.concatenate([r, rec[h_rec.shape[0]:k].cpu().numpy()], 0)
             order = np.argsort(r[:, 0], kind="stable")                     # word 0 = t << 32 | env: time-major, then env
             self.out = (r[order, 1].copy().view(np.float64).tolist(), r[order, 2].tolist())
-            if getattr(self.c, self.slot + "_pending") is self:
-                setattr(self.c, self.slot + "_pending", None)
+            if self.scan.pending is self:
+                self.scan.pending = None
         return self.out
+
+
+class EpisodeScan(object):
+    """One episode stream over consecutive [T, n] segments: return and length of every episode that ends inside a segment, in time-major order (the order in
+    which a single-env loop would have appended them, src/trpo.py:72-76), and the carry of the episodes still open at its end."""
+
+    EP_HEAD = 16384                      # episode records fetched with the count in one asynchronous copy (more than that: a second copy)
+
+    def __init__(self, T, n, device):
+        import torch
+        self.T, self.n, self.device = int(T), int(n), torch.device(device)
+        self.cur_ret = torch.zeros(self.n, dtype=torch.float64, device=self.device)     # running return / length of the open episodes
+        self.cur_len = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        self.step_idx = torch.arange(1, self.T + 1, device=self.device, dtype=torch.int64)[:, None]
+        self.records = None              # native form: (count [1] i32, records [T n, 3] i64) on the device, and their pinned host copies
+        self.pending = None              # ... and its one result whose records may still be travelling into them
+        if self.device.type == "cuda":
+            cap = self.T * self.n
+            head = min(cap, self.EP_HEAD)
+            self.records = (torch.zeros(1, dtype=torch.int32, device=self.device), torch.empty((cap, 3), dtype=torch.int64, device=self.device),
+                            torch.zeros(1, dtype=torch.int32).pin_memory(), torch.empty((head, 3), dtype=torch.int64).pin_memory())
+
+    def scan(self, rew64, done8):
+        """-> a `_PendingEpisodes` (device buffers the kernel can walk) or the finished (ep_rets, ep_lens)"""
+        import torch
+        if self.device.type == "cuda" and rew64.dtype == torch.float64 and rew64.is_contiguous() and done8.is_contiguous():
+            return self.native(rew64, done8)
+        return self.torch(rew64, done8.to(torch.bool))
+
+    def native(self, rew64, done8):
+        """One launch (dm_episode_scan: thread = env walks its column of the segment) and a host sort of the few episodes that ended, instead
+        of ~100 launch-bound tensor ops.  Returns are float64 sums in step order, like the reference's `cur_ep_ret += rew`.  Nothing waits
+        here: the records travel to pinned memory behind the kernel, and `_PendingEpisodes.result()` sorts them when somebody asks — the
+        learner does while the device is busy with the update's first kernels."""
+        import torch
+        from . import _abi as A
+        dev = self.device
+        if self.pending is not None:
+            self.pending.result()                                          # (its pinned buffers are about to be overwritten)
+        cnt, rec, h_cnt, h_rec = self.records
+        L, p = A.load(), A.ptr
+        A.check(L.dm_episode_scan(p(rew64), p(done8), self.T, self.n, p(self.cur_ret), p(self.cur_len), p(cnt), rec.shape[0], p(rec),
+                                  A.stream(dev)), L)
+        h_cnt.copy_(cnt, non_blocking=True)
+        h_rec.copy_(rec[:h_rec.shape[0]], non_blocking=True)
+        ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(dev))
+        self.pending = _PendingEpisodes(self, ev)
+        return self.pending
+
+    def torch(self, rew64, done):
+        """the same in [T, n]-wide tensor ops on any device; done: bool [T, n].  -> (ep_rets, ep_lens)"""
+        import torch
+        T, n, device = self.T, self.n, self.device
+        cur_ret, cur_len = self.cur_ret, self.cur_len
+        csum = torch.cumsum(rew64, 0)
+        ends = done.nonzero()                                              # [K, 2] (t, env), sorted by t then env
+        ep_rets, ep_lens = [], []
+        if ends.numel():
+            te, ee = ends[:, 0], ends[:, 1]
+            # previous end of the same env inside the segment (or -1): sort by (env, t) and shift
+            order = torch.argsort(ee * T + te)
+            te_s, ee_s = te[order], ee[order]
+            prev_t = torch.full_like(te_s, -1)
+            same = ee_s[1:] == ee_s[:-1]
+            prev_t[1:] = torch.where(same, te_s[:-1], torch.full_like(te_s[:-1], -1))
+            seg_ret = csum[te_s, ee_s] - torch.where(prev_t >= 0, csum[prev_t.clamp(min=0), ee_s], torch.zeros_like(csum[te_s, ee_s]))
+            seg_len = te_s - prev_t
+            opening = prev_t < 0                                           # first end of that env: add what it carried in
+            seg_ret = seg_ret + torch.where(opening, cur_ret[ee_s], torch.zeros_like(seg_ret))
+            seg_len = seg_len + torch.where(opening, cur_len[ee_s], torch.zeros_like(seg_len))
+            inv = torch.empty_like(order); inv[order] = torch.arange(order.numel(), device=device)
+            ep_rets = seg_ret[inv].tolist(); ep_lens = seg_len[inv].tolist()
+        # carry the open episodes into the next segment
+        last_end = torch.where(done, self.step_idx.expand(T, n), torch.zeros((T, n), dtype=torch.int64, device=device)).amax(0)   # 1-based
+        tail_ret = csum[-1] - torch.where(last_end > 0, csum[(last_end - 1).clamp(min=0), torch.arange(n, device=device)], torch.zeros_like(csum[-1]))
+        self.cur_ret = torch.where(last_end > 0, tail_ret, cur_ret + tail_ret)
+        self.cur_len = torch.where(last_end > 0, T - last_end, cur_len + T)
+        return ep_rets, ep_lens
 
 
 class Segment(dict):
@@ -200,6 +250,126 @@ class Segment(dict):
         return self[key] if key in self else default
 
 
+class _TimeLimitBootstrap(object):
+    """SegmentCollector(bootstrap_time_limit=True): the env's truncation log sized to the segment, and the buffers its records are read into.  An
+    environment is truncated at most once per M steps, and a segment's first truncation may fall on any of its rows: at most T // M + 1 per environment,
+    so a log of n (T // M + 1) records never overflows."""
+
+    def __init__(self, pi, env, T, n, device, as_buf):
+        import torch
+        from . import _abi as A
+        self.pi, self.env, self.T, self.n, self.device, self.as_buf = pi, env, T, n, device, as_buf
+        M = int(env.max_episode_steps or 0)
+        if M <= 0:
+            raise ValueError("bootstrap_time_limit needs an env with a time limit (DPVecEnv(max_episode_steps=M), M > 0)")
+        C = self.capacity = n * (T // M + 1)
+        env.batch.set_option(A.OPT_TRUNCATION_LOG, C)
+        self.log = (torch.zeros(1, dtype=torch.int32, device=device), torch.zeros((C, 4), dtype=torch.int32, device=device),
+                    torch.zeros((C, A.NQ), dtype=torch.float64, device=device), torch.zeros((C, A.NV), dtype=torch.float64, device=device))
+        self.ob = torch.zeros((C, env_obs_width(env)), dtype=torch.float64, device=device)
+        self.slot = torch.arange(C, device=device, dtype=torch.int64)
+        self.vboot = torch.zeros((T, n), dtype=torch.float32, device=device)
+        self.h_count = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)] if device.type == "cuda" else None
+        self.h_k = 0
+
+    def clear(self):
+        """the log's count and tick start again (stream-ordered, nothing is copied but the old count)"""
+        self.env.batch.truncations(clear=True, out=(self.as_buf(self.log[0]), None, None, None))
+
+    def values(self, seg):
+        """seg["vboot"] [T, n] f32: the critic's value of every state the time limit cut off in this segment, at (tick, env); 0 elsewhere.  All C slots
+        of the log become observations and are evaluated (at most n rows for T <= M); the slots at or above the count are masked on the device, so
+        nothing waits for the count."""
+        import torch
+        from . import _abi as A
+        from .state_features import phase_of
+        b, T, n, as_buf = self.env.batch, self.T, self.n, self.as_buf
+        cnt, idx, qp, qv = self.log
+        b.truncations(clear=False, out=tuple(as_buf(x) for x in self.log))
+        if self.ob.shape[1] == 56:
+            torch.cat([qp[:, 7:], qv[:, 6:]], 1, out=self.ob)
+        else:
+            # the phase the features launch would have given this state had the episode gone on: from the cursors as the step left them
+            phase = phase_of(batch_option(b, A.OPT_REWARD_MODE), idx[:, 2], idx[:, 3], b.n_frames).contiguous()
+            b.state_features(as_buf(self.ob), qpos=as_buf(qp), qvel=as_buf(qv), phase=as_buf(phase))
+        with torch.no_grad():
+            v = self.pi.forward_value(self.ob).to(torch.float32)
+        tick, e = idx[:, 1].to(torch.int64), idx[:, 0].to(torch.int64)
+        ok = (self.slot < cnt.to(torch.int64)) & (tick >= 0) & (tick < T) & (e >= 0) & (e < n)
+        flat = torch.where(ok, tick * n + e, torch.zeros_like(tick))
+        # (tick, env) is unique among the valid records, the others add 0 to row 0: the sum IS the scatter, whatever order the records arrived in
+        self.vboot.zero_()
+        self.vboot.view(-1).index_add_(0, flat, torch.where(ok, v, torch.zeros_like(v)))
+        seg["vboot"] = self.vboot.clone()
+        if self.h_count is not None:
+            h = self.h_count[self.h_k]; self.h_k ^= 1
+            h.copy_(cnt, non_blocking=True)
+            ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(self.device))
+            seg.pending_trunc = (h, ev)
+        else:
+            seg.pending_trunc = (cnt.clone(), None)
+
+
+class HorizonKernelChoice(object):
+    """Four environments per wavefront or one, for the next horizon (envs that leave the choice open: DPVecEnv.horizon_packed_ok).
+    The horizon launch re-steps an environment beyond the packed path's capacities inside its wave, which holds up its three
+    partners: fine at the 1e-4 rates of a falling / walking population, not for one that stands on both feet (32+ rows) most of the
+    time.  Decided from the last horizon's own statistics (redo rate on the packed path, largest row count on the one-env path):
+    a deterministic function of the trajectory."""
+
+    # horizon launch -> one-env steps: an in-wave re-step holds a wave (four environments) for about one lone one-env step.  Measured on a
+    # population learning to stand (tools/train_trpo.py, 4 096 envs x 128 steps, MI355X; profiles/r04_ab_kernel_variants.md): 38 / 42 / 46 /
+    # 52 / 55 / 58-60 ms per horizon at 0.2 / 0.8 / 1.3 / 2.6 / 3.7 / 5 % of env-steps re-stepped (the rate levels off near 5 %) against
+    # 67 ms for the same population through one-env launches — the packed horizon stays ahead to about 7 %.  (Round 3's 2 % came from a cost
+    # estimate; a run that crossed it at 2.02 % lost a quarter of its rollout throughput for the rest of the training.)
+    REDO_RATE_MAX = 7e-2
+    HEAVY_ROWS = 38                        # the way back to the packed horizon launch: nobody above this (it holds _abi.PACKED_MAXROWS = 40 rows per env)
+
+    def __init__(self, env, T, n):
+        import os
+        self.env, self.T, self.n = env, int(T), int(n)
+        if os.environ.get("DM_HORIZON_REDO_RATE_MAX"):                   # (experiments: tools/prof_train.sh)
+            self.REDO_RATE_MAX = float(os.environ["DM_HORIZON_REDO_RATE_MAX"])
+        self.packed_now = None                     # what choose() picked for the last horizon (None: none yet)
+        self.kernel_switches = 0
+        self.last_redo_rate = None
+        self._redo_seen = None                     # the batch's redo counter after the last choice (None: no horizon yet)
+
+    def choose(self):
+        """Set the batch to the kernel for the next horizon.  -> the callable that undoes it after the horizon's calls, or None for an env whose
+        configuration pins the kernel (nothing is touched then)."""
+        from . import _abi as A
+        b = self.env.batch
+        if not self.env.horizon_packed_ok:
+            return None
+        # the choice holds for the collector's rollout calls only: what the batch was set to (and its per-step chooser, if on) comes back
+        # after each call, so `DPVecEnv.step` callers of the same env are not moved to a kernel that is the slower one per step
+        was_mode = batch_option(b, A.OPT_PACKED)        # (0 one env per wave, 1 packed, 2 packed with the three-set code per step)
+        was_on = bool(was_mode)
+        on = was_on if self.packed_now is None else self.packed_now
+        if self._redo_seen is None:                                         # first horizon: start packed
+            want = True
+        elif on:
+            self.last_redo_rate = (b.redo_total() - self._redo_seen) / float(self.T * self.n)
+            want = self.last_redo_rate <= self.REDO_RATE_MAX
+        else:
+            want = int(b.get(A.F_NEFC).max()) <= self.HEAVY_ROWS
+        if want != on:
+            self.kernel_switches += 1
+        self.packed_now = want
+        was_auto = b.suspend_auto()                                         # (suspended, not reset: its counters go on afterwards)
+        if want != was_on:
+            b.set_option(A.OPT_PACKED, 1 if want else 0)
+        self._redo_seen = b.redo_total()
+
+        def restore():
+            if want != was_on:
+                b.set_option(A.OPT_PACKED, was_mode)
+            if was_auto:
+                b.resume_auto()                                             # (rebaselined: the horizon's in-wave re-steps are not the per-step chooser's evidence)
+        return restore
+
+
 class SegmentCollector(object):
     """One env batch's side of `traj_segment_generator`, split into `launch()` (enqueue T policy + env steps, no host wait) and
     `collect()` (episode bookkeeping, the one host transfer per segment) so that several env batches can be in flight at once.
@@ -215,22 +385,21 @@ class SegmentCollector(object):
         """reward_terms (an env with reward="imitation"): one dm_batch_imitation_terms call per segment, on the states the segment ends in, behind the
         horizon's launches — the segment then carries `err_sums` (Segment); nothing is added to a step."""
         import torch
+        from . import _abi as A
         self.pi, self.env, self.T, self.stochastic, self.stream = pi, env, int(horizon), stochastic, stream
         n, T = env.num_envs, self.T
         self.n = n
         device = torch.device(pi.device if device is None else device)
         self.device = device
-        self._terms = None
+        self.as_buf = (lambda x: x) if device.type == "cuda" else (lambda x: x.numpy())   # host tensors: shared-memory views
+        self.terms = None                          # reward_terms: the [n, 28] rows of the states the segment ended in
         if reward_terms:
-            from . import _abi as A
-            if int(getattr(env.batch, "options", {}).get(A.OPT_REWARD_MODE, 0)) != 3:
+            if batch_option(env.batch, A.OPT_REWARD_MODE) != 3:
                 raise ValueError("reward_terms needs an env with reward=\"imitation\" (the batch's cursors name the compared frame in that mode only)")
-            self._terms = torch.zeros((n, A.NTERMS), dtype=torch.float64, device=device)
-        self.bootstrap = bool(bootstrap_time_limit)
-        if self.bootstrap:
-            self._init_bootstrap()
+            self.terms = torch.zeros((n, A.NTERMS), dtype=torch.float64, device=device)
+        self.bootstrap = _TimeLimitBootstrap(pi, env, T, n, device, self.as_buf) if bootstrap_time_limit else None
         f32, f64 = torch.float32, torch.float64
-        self.ob_width = int(env.observation_space.shape[0]) if getattr(env, "obs_mode", "dp_env_v3") != "dp_env_v3" else 56
+        self.ob_width = env_obs_width(env)
         self.ob64 = torch.zeros((T + 1, n, self.ob_width), dtype=f64, device=device)   # row t: observation the policy sees at step t
         # obs_mode "deepmimic": the step launch writes its 56 numbers here, then dm_batch_state_features fills the segment's row from the state it left
         self.ob56 = torch.zeros((n, 56), dtype=f64, device=device) if self.ob_width != 56 else None
@@ -240,15 +409,11 @@ class SegmentCollector(object):
         self.vpreds = torch.zeros((T + 1, n), dtype=f32, device=device)
         self.first = torch.ones(n, dtype=torch.int32, device=device)               # `new` of row 0: carried over from the last segment
         self.last_ac = torch.zeros((n, 28), dtype=f32, device=device)              # prevac of row 0 (trpo.py:29 samples a random one)
-        self.cur_ret = torch.zeros(n, dtype=f64, device=device)                    # running return / length of the open episodes
-        self.cur_len = torch.zeros(n, dtype=torch.int64, device=device)
+        self.episodes = EpisodeScan(T, n, device)                                  # of the segment's reward
         self.reward_giver = reward_giver
-        if reward_giver is not None:
+        if reward_giver is not None:                                               # (these two exist only then)
             self.drew64 = torch.zeros((T, n), dtype=f64, device=device)            # D's reward of every (ob, ac) of the segment
-            self.cur_true_ret = torch.zeros(n, dtype=f64, device=device)           # the env's return of the open episodes
-            self.cur_true_len = torch.zeros(n, dtype=torch.int64, device=device)
-        self.as_buf = (lambda x: x) if device.type == "cuda" else (lambda x: x.numpy())   # host tensors: shared-memory views
-        self.step_idx = torch.arange(1, T + 1, device=device, dtype=torch.int64)[:, None]
+            self.true_episodes = EpisodeScan(T, n, device)                         # of the env's own reward
         # fused path: the env step kernel also runs the policy on the observation it produced (dm_batch_step_act), one launch per step.
         # As in the reference's generator (src/trpo.py:47-56) the action for the first observation of a segment was then drawn BEFORE the
         # update in between (by the policy that finished the last segment) and only its value is re-evaluated afterwards.
@@ -256,193 +421,118 @@ class SegmentCollector(object):
             raise ValueError("fused rollout steps need the native policy kernel (56-100-100-28) and a device-resident env batch")
         self.fused = bool(fused)
         self.have_ac0 = False
-        self._redo_seen = None
-        import os
-        if os.environ.get("DM_HORIZON_REDO_RATE_MAX"):                   # (experiments: tools/prof_train.sh)
-            self.HORIZON_REDO_RATE_MAX = float(os.environ["DM_HORIZON_REDO_RATE_MAX"])
-        self._packed_now = None                    # what _choose_kernel picked for the last horizon (None: none yet)
-        self.kernel_switches = 0
+        self.kernel_choice = HorizonKernelChoice(env, T, n)
         with self._on_stream():
             env.reset(first_reset, out=self.as_buf(self.ob64[0]))                  # trpo.py:32 `ob = env.reset()` (RSI); later episodes: noisy init
 
-    def _init_bootstrap(self):
-        """bootstrap_time_limit: the env's truncation log sized to the segment, and the buffers its records are read into.  An environment is
-        truncated at most once per M steps, and a segment's first truncation may fall on any of its rows: at most T // M + 1 per environment, so a
-        log of n (T // M + 1) records never overflows."""
-        import torch
-        from . import _abi as A
-        env, n, T, dev = self.env, self.n, self.T, self.device
-        M = int(getattr(env, "max_episode_steps", 0) or 0)
-        if M <= 0:
-            raise ValueError("bootstrap_time_limit needs an env with a time limit (DPVecEnv(max_episode_steps=M), M > 0)")
-        C = n * (T // M + 1)
-        self._trunc_cap = C
-        env.batch.set_option(A.OPT_TRUNCATION_LOG, C)
-        self._trunc = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros((C, 4), dtype=torch.int32, device=dev),
-                       torch.zeros((C, A.NQ), dtype=torch.float64, device=dev), torch.zeros((C, A.NV), dtype=torch.float64, device=dev))
-        self._trunc_ob = torch.zeros((C, int(env.observation_space.shape[0]) if getattr(env, "obs_mode", "dp_env_v3") != "dp_env_v3" else 56), dtype=torch.float64, device=dev)
-        self._trunc_slot = torch.arange(C, device=dev, dtype=torch.int64)
-        self.vboot = torch.zeros((T, n), dtype=torch.float32, device=dev)
-        self._h_trunc = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)] if dev.type == "cuda" else None
-        self._h_trunc_k = 0
-
-    def _clear_truncations(self):
-        """the log's count and tick start again (stream-ordered, nothing is copied but the old count)"""
-        self.env.batch.truncations(clear=True, out=(self.as_buf(self._trunc[0]), None, None, None))
-
-    def _bootstrap_values(self, seg):
-        """seg["vboot"] [T, n] f32: the critic's value of every state the time limit cut off in this segment, at (tick, env); 0 elsewhere.  All C slots
-        of the log become observations and are evaluated (at most n rows for T <= M); the slots at or above the count are masked on the device, so
-        nothing waits for the count."""
-        import torch
-        from . import _abi as A
-        from .state_features import phase_of
-        env, b, T, n, as_buf = self.env, self.env.batch, self.T, self.n, self.as_buf
-        cnt, idx, qp, qv = self._trunc
-        b.truncations(clear=False, out=tuple(as_buf(x) for x in self._trunc))
-        if self._trunc_ob.shape[1] == 56:
-            torch.cat([qp[:, 7:], qv[:, 6:]], 1, out=self._trunc_ob)
-        else:
-            # the phase the features launch would have given this state had the episode gone on: from the cursors as the step left them
-            phase = phase_of(int(b.options.get(A.OPT_REWARD_MODE, 0)), idx[:, 2], idx[:, 3], b.n_frames).contiguous()
-            b.state_features(as_buf(self._trunc_ob), qpos=as_buf(qp), qvel=as_buf(qv), phase=as_buf(phase))
-        with torch.no_grad():
-            v = self.pi.forward_value(self._trunc_ob).to(torch.float32)
-        tick, e = idx[:, 1].to(torch.int64), idx[:, 0].to(torch.int64)
-        ok = (self._trunc_slot < cnt.to(torch.int64)) & (tick >= 0) & (tick < T) & (e >= 0) & (e < n)
-        flat = torch.where(ok, tick * n + e, torch.zeros_like(tick))
-        # (tick, env) is unique among the valid records, the others add 0 to row 0: the sum IS the scatter, whatever order the records arrived in
-        self.vboot.zero_()
-        self.vboot.view(-1).index_add_(0, flat, torch.where(ok, v, torch.zeros_like(v)))
-        seg["vboot"] = self.vboot.clone()
-        if self._h_trunc is not None:
-            h = self._h_trunc[self._h_trunc_k]; self._h_trunc_k ^= 1
-            h.copy_(cnt, non_blocking=True)
-            ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(self.device))
-            seg.pending_trunc = (h, ev)
-        else:
-            seg.pending_trunc = (cnt.clone(), None)
+    # what the last horizon ran on (None: no choice made yet) and how often the choice changed: read by the benchmark and tools/rollout_policy_bench.py
+    _packed_now = property(lambda self: self.kernel_choice.packed_now)
+    kernel_switches = property(lambda self: self.kernel_choice.kernel_switches)
 
     def _on_stream(self):
         import contextlib
         import torch
         return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
 
+    def _follow_current_stream(self):
+        """with `stream`: what the caller's stream has enqueued so far (parameter updates, the last collect's copies) comes before what the side stream gets next"""
+        if self.stream is not None:
+            import torch
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
     def launch(self):
         import torch
-        pi, env, T, as_buf = self.pi, self.env, self.T, self.as_buf
-        ob64, ac64, rew64, done8, vpreds = self.ob64, self.ac64, self.rew64, self.done8, self.vpreds
-        fs = getattr(env, "frame_skip", 1)
-        if self.stream is not None:
-            self.stream.wait_stream(torch.cuda.current_stream(self.device))         # parameters / filter updated by the learner are visible
-        if self.fused and (getattr(pi, "_dirty", False) or getattr(pi, "_packed", None) is None):
-            pi.pack()                                                               # (on the caller's stream, before the side stream forks)
-            if self.stream is not None:
-                self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._follow_current_stream()                                               # parameters / filter updated by the learner are visible
+        if self.fused and _pack_is_stale(self.pi):
+            self.pi.pack()                                                          # (on the caller's stream, before the side stream forks)
+            self._follow_current_stream()
         with self._on_stream(), torch.no_grad():                                    # (the learner may hold the parameters with requires_grad)
-            if self.bootstrap:
-                self._clear_truncations()                                           # tick 0 = this segment's first step
-            if self.fused:
-                if not self.have_ac0:
-                    pi.act(self.stochastic, ob64[0], out=ac64[0], vpred_out=vpreds[0])                   # very first step: :49
-                else:
-                    vpreds[0] = pi.forward_value(ob64[0])                                                 # :56, the updated policy's value
-                if hasattr(env.batch, "rollout"):
-                    # the whole horizon in one call (dm_batch_rollout): on the packed path ONE launch in which every wavefront runs its four
-                    # environments through all T steps at its own pace; on the one-env path T step launches issued without returning here
-                    restore = self._choose_kernel()
-                    try:
-                        env.batch.rollout(ac64, (ob64[1:], rew64, done8), fs, pi._packed, vpreds[1:], self.stochastic, pi._seed, pi._counter + 1)
-                        pi._counter += T
-                        env.batch.join()
-                    finally:                                        # (also when the rollout raises: the batch must not be left on the collector's kernel choice)
-                        if restore is not None:
-                            restore()                               # per-step callers of the same env keep the kernel THEY were given
-                    return
-                for t in range(T):                                                                       # :49 + :66, one launch
-                    pi._counter += 1
-                    env.batch.step_act(ac64[t], fs, (ob64[t + 1], rew64[t], done8[t]), pi._packed, ac64[t + 1], vpreds[t + 1],
-                                       self.stochastic, pi._seed, pi._counter)
-                env.batch.join()
-                return
-            for t in range(T):
-                pi.act(self.stochastic, ob64[t], out=ac64[t], vpred_out=vpreds[t])                       # :49
-                if self.ob56 is None:
-                    env.batch.step(as_buf(ac64[t]), fs, (as_buf(ob64[t + 1]), as_buf(rew64[t]), as_buf(done8[t])))   # :66, one launch
-                else:
-                    env.batch.step(as_buf(ac64[t]), fs, (as_buf(self.ob56), as_buf(rew64[t]), as_buf(done8[t])))
-                    env.batch.state_features(as_buf(ob64[t + 1]))
-            vpreds[T] = pi.forward(ob64[T])[1]                                      # value of the observation after the segment (:49-52);
-        # the action for it is sampled at the top of the next segment, i.e. from the policy as updated in between
+            if self.bootstrap is not None:
+                self.bootstrap.clear()                                              # tick 0 = this segment's first step
+            if not self.fused:
+                self._launch_steps()
+            elif hasattr(self.env.batch, "rollout"):
+                self._launch_fused_horizon()
+            else:
+                self._launch_fused_steps()
 
-    # horizon launch -> one-env steps: an in-wave re-step holds a wave (four environments) for about one lone one-env step.  Measured on a
-    # population learning to stand (tools/train_trpo.py, 4 096 envs x 128 steps, MI355X; profiles/r04_ab_kernel_variants.md): 38 / 42 / 46 /
-    # 52 / 55 / 58-60 ms per horizon at 0.2 / 0.8 / 1.3 / 2.6 / 3.7 / 5 % of env-steps re-stepped (the rate levels off near 5 %) against
-    # 67 ms for the same population through one-env launches — the packed horizon stays ahead to about 7 %.  (Round 3's 2 % came from a cost
-    # estimate; a run that crossed it at 2.02 % lost a quarter of its rollout throughput for the rest of the training.)
-    HORIZON_REDO_RATE_MAX = 7e-2
-    HORIZON_HEAVY_ROWS = 38                # the way back to the packed horizon launch: nobody above this (it holds _abi.PACKED_MAXROWS = 40 rows per env)
+    def _launch_steps(self):
+        """T policy forwards and T env step launches; the value of the observation after the segment (:49-52) behind them.  The action for that
+        observation is sampled at the top of the next segment, i.e. from the policy as updated in between."""
+        pi, batch, as_buf, fs = self.pi, self.env.batch, self.as_buf, getattr(self.env, "frame_skip", 1)
+        ob64, ac64, rew64, done8, vpreds = self.ob64, self.ac64, self.rew64, self.done8, self.vpreds
+        for t in range(self.T):
+            pi.act(self.stochastic, ob64[t], out=ac64[t], vpred_out=vpreds[t])                           # :49
+            if self.ob56 is None:
+                batch.step(as_buf(ac64[t]), fs, (as_buf(ob64[t + 1]), as_buf(rew64[t]), as_buf(done8[t])))   # :66, one launch
+            else:
+                batch.step(as_buf(ac64[t]), fs, (as_buf(self.ob56), as_buf(rew64[t]), as_buf(done8[t])))
+                batch.state_features(as_buf(ob64[t + 1]))
+        vpreds[self.T] = pi.forward(ob64[self.T])[1]
 
-    def _choose_kernel(self):
-        """Four environments per wavefront or one, for the next horizon (envs that leave the choice open: DPVecEnv.horizon_packed_ok).
-        The horizon launch re-steps an environment beyond the packed path's capacities inside its wave, which holds up its three
-        partners: fine at the 1e-4 rates of a falling / walking population, not for one that stands on both feet (32+ rows) most of the
-        time.  Decided from the last horizon's own statistics (redo rate on the packed path, largest row count on the one-env path):
-        a deterministic function of the trajectory."""
-        from . import _abi as A
-        env, b = self.env, self.env.batch
-        if not getattr(env, "horizon_packed_ok", False):
-            return None
-        # the choice holds for this collector's rollout calls only: what the batch was set to (and its per-step chooser, if on) comes back
-        # after each call, so `DPVecEnv.step` callers of the same env are not moved to a kernel that is the slower one per step
-        was_mode = int(b.__dict__.get("options", {}).get(A.OPT_PACKED, 0))      # (0 one env per wave, 1 packed, 2 packed with the three-set code per step)
-        was_on = bool(was_mode)
-        was_auto = bool(b.__dict__.get("_auto"))
-        on = getattr(self, "_packed_now", None)
-        if on is None:
-            on = was_on
-        if self._redo_seen is None:                                         # first horizon: start packed
-            want = True
-        elif on:
-            redo = b.redo_total()
-            self._last_redo_rate = (redo - self._redo_seen) / float(self.T * self.n)
-            want = self._last_redo_rate <= self.HORIZON_REDO_RATE_MAX
+    def _first_fused_action(self):
+        if not self.have_ac0:
+            self.pi.act(self.stochastic, self.ob64[0], out=self.ac64[0], vpred_out=self.vpreds[0])      # very first step: :49
         else:
-            want = int(b.get(A.F_NEFC).max()) <= self.HORIZON_HEAVY_ROWS
-        if want != on:
-            self.kernel_switches += 1
-        self._packed_now = want
-        if was_auto:
-            b._auto = False                                                 # (suspended, not reset: its counters go on afterwards)
-        if want != was_on:
-            b.set_option(A.OPT_PACKED, 1 if want else 0)
-        self._redo_seen = b.redo_total()
+            self.vpreds[0] = self.pi.forward_value(self.ob64[0])                                         # :56, the updated policy's value
 
-        def restore():
-            if want != was_on:
-                b.set_option(A.OPT_PACKED, was_mode)
-            if was_auto:
-                b._auto = True
-                b.rebaseline_auto()                                         # (the horizon's in-wave re-steps are not the per-step chooser's evidence)
-        return restore
+    def _launch_fused_horizon(self):
+        """the whole horizon in one call (dm_batch_rollout): on the packed path ONE launch in which every wavefront runs its four
+        environments through all T steps at its own pace; on the one-env path T step launches issued without returning here"""
+        pi, env, T = self.pi, self.env, self.T
+        self._first_fused_action()
+        restore = self.kernel_choice.choose() if getattr(env, "horizon_packed_ok", False) else None
+        try:
+            env.batch.rollout(self.ac64, (self.ob64[1:], self.rew64, self.done8), getattr(env, "frame_skip", 1), pi._packed, self.vpreds[1:],
+                              self.stochastic, pi._seed, pi._counter + 1)
+            pi._counter += T
+            env.batch.join()
+        finally:                                        # (also when the rollout raises: the batch must not be left on the collector's kernel choice)
+            if restore is not None:
+                restore()                               # per-step callers of the same env keep the kernel THEY were given
+
+    def _launch_fused_steps(self):
+        pi, batch, fs = self.pi, self.env.batch, getattr(self.env, "frame_skip", 1)
+        ob64, ac64, rew64, done8, vpreds = self.ob64, self.ac64, self.rew64, self.done8, self.vpreds
+        self._first_fused_action()
+        for t in range(self.T):                                                                          # :49 + :66, one launch
+            pi._counter += 1
+            batch.step_act(ac64[t], fs, (ob64[t + 1], rew64[t], done8[t]), pi._packed, ac64[t + 1], vpreds[t + 1],
+                           self.stochastic, pi._seed, pi._counter)
+        batch.join()
+
+    def _reward_term_sums(self, seg):
+        """reward_terms: behind the horizon's launches, before the next segment's — the states the segment ends in"""
+        import torch
+        self.env.batch.imitation_terms(out=self.as_buf(self.terms))
+        keep = (self.done8[-1] == 0).to(torch.float64)          # an env the last step reset shows its fresh episode's row: left out
+        seg.err_sums = torch.cat([(self.terms[:, :5] * keep[:, None]).sum(0), keep.sum()[None]])
+
+    def _scan_episodes(self, seg, rew64, true64):
+        """episode statistics: pending on the segment where the scan kernel runs, else finished lists under its keys"""
+        eps = self.episodes.scan(rew64, self.done8)
+        true = self.true_episodes.scan(true64, self.done8) if true64 is not None else None
+        if isinstance(eps, _PendingEpisodes):
+            seg.pending_episodes, seg.pending_true = eps, true
+        else:
+            seg["ep_rets"], seg["ep_lens"] = eps
+            if true is not None:
+                seg["ep_true_rets"] = true[0]
 
     def collect(self):
-        import torch
-        T, n, device = self.T, self.n, self.device
-        f32 = torch.float32
-        seg = Segment()
-        if self.bootstrap:
-            with self._on_stream():                    # (on the stream the batch is on: reading its log there needs no change of stream)
-                self._bootstrap_values(seg)
-        if self._terms is not None:
-            with self._on_stream():                    # behind the horizon's launches, before the next segment's: the states the segment ends in
-                self.env.batch.imitation_terms(out=self.as_buf(self._terms))
-                keep = (self.done8[-1] == 0).to(torch.float64)          # an env the last step reset shows its fresh episode's row: left out
-                seg.err_sums = torch.cat([(self._terms[:, :5] * keep[:, None]).sum(0), keep.sum()[None]])
-        if self.stream is not None:
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
         import os
         import time
+        import torch
+        T, device = self.T, self.device
+        f32 = torch.float32
+        seg = Segment()
+        with self._on_stream():                        # (on the stream the batch is on: reading its log there needs no change of stream)
+            if self.bootstrap is not None:
+                self.bootstrap.values(seg)
+            if self.terms is not None:
+                self._reward_term_sums(seg)
+        if self.stream is not None:
+            torch.cuda.current_stream(device).wait_stream(self.stream)
         prof = os.environ.get("DM_TRPO_PROFILE") and device.type == "cuda"
         if prof:
             torch.cuda.synchronize(device); t_c = time.perf_counter()
@@ -452,98 +542,26 @@ class SegmentCollector(object):
             with torch.no_grad():
                 self.reward_giver.reward_into(ob64[:T], ac64[:T], self.drew64)        # gail.py:78, the whole segment at once
             true64, rew64 = rew64, self.drew64
-        done = done8.to(torch.bool)
+        if device.type == "cuda":
+            done8.to(torch.bool)                       # (read by nothing since the scans take done8: the launch stays where it was, dropping it is a change of its own)
         new = torch.cat([self.first[None], done8[:-1].to(torch.int32)], 0)
         acs = ac64[:T].to(f32)
         prevacs = torch.cat([self.last_ac[None], acs[:-1]], 0)
-        # episode statistics: return / length of every episode that ended inside the segment, in time-major order
-        # (= the order in which a single-env loop would have appended them, :72-76)
-        native_eps = device.type == "cuda" and rew64.dtype == torch.float64 and rew64.is_contiguous() and done8.is_contiguous()
-        seg.info = {"packed": self._packed_now, "kernel_switches": self.kernel_switches, "redo_rate": getattr(self, "_last_redo_rate", None)}
-        if native_eps:
-            seg.pending_episodes = self._episodes_native(rew64, done8)
-            if true64 is not None:
-                seg.pending_true = self._episodes_native(true64, done8, true=True)
-        else:
-            seg["ep_rets"], seg["ep_lens"] = self._episodes_torch(rew64, done, T, n, device)
-            if true64 is not None:
-                seg["ep_true_rets"] = self._episodes_torch(true64, done, T, n, device, true=True)[0]
+        seg.info = {"packed": self._packed_now, "kernel_switches": self.kernel_switches, "redo_rate": self.kernel_choice.last_redo_rate}
+        self._scan_episodes(seg, rew64, true64)
         seg.update({"ob": ob64[:T].to(f32), "rew": rew64.to(f32), "vpred": vpreds[:T].clone(), "new": new, "ac": acs, "prevac": prevacs,
                     "nextvpred": vpreds[T] * (1 - done8[-1].to(f32))})
+        # the carry into the next segment
         self.first = done8[-1].to(torch.int32)
         self.last_ac = acs[-1].clone()
         ob64[0].copy_(ob64[T])
         if self.fused:
             ac64[0].copy_(ac64[T]); self.have_ac0 = True
-        if self.stream is not None:
-            self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the copies above are ordered before the next launch
+        self._follow_current_stream()                  # the copies above are ordered before the next launch
         if prof:
             torch.cuda.synchronize(device); self.collect_ms = (time.perf_counter() - t_c) * 1e3
             seg["collect_ms"] = self.collect_ms
         return seg
-
-    EP_HEAD = 16384                      # episode records fetched with the count in one asynchronous copy (more than that: a second copy)
-
-    def _episodes_native(self, rew64, done8, true=False):
-        """One launch (dm_episode_scan: thread = env walks its column of the segment) and a host sort of the few episodes that ended, instead
-        of ~100 launch-bound tensor ops.  Returns are float64 sums in step order, like the reference's `cur_ep_ret += rew`.  Nothing waits
-        here: the records travel to pinned memory behind the kernel, and `_PendingEpisodes.result()` sorts them when somebody asks — the
-        learner does while the device is busy with the update's first kernels."""
-        import torch
-        from . import _abi as A
-        T, n, dev = self.T, self.n, self.device
-        slot = "_ept" if true else "_ep"                                   # true: the env's returns beside D's (reward_giver), own buffers / carry
-        cur_ret, cur_len = (self.cur_true_ret, self.cur_true_len) if true else (self.cur_ret, self.cur_len)
-        if getattr(self, slot + "_buf", None) is None:
-            cap = T * n
-            head = min(cap, self.EP_HEAD)
-            setattr(self, slot + "_buf", (torch.zeros(1, dtype=torch.int32, device=dev), torch.empty((cap, 3), dtype=torch.int64, device=dev),
-                                          torch.zeros(1, dtype=torch.int32).pin_memory(), torch.empty((head, 3), dtype=torch.int64).pin_memory()))
-            setattr(self, slot + "_pending", None)
-        if getattr(self, slot + "_pending") is not None:
-            getattr(self, slot + "_pending").result()                     # (its pinned buffers are about to be overwritten)
-        cnt, rec, h_cnt, h_rec = getattr(self, slot + "_buf")
-        L, p = A.load(), A.ptr
-        A.check(L.dm_episode_scan(p(rew64), p(done8), T, n, p(cur_ret), p(cur_len), p(cnt), rec.shape[0], p(rec),
-                                  A.stream(dev)), L)
-        h_cnt.copy_(cnt, non_blocking=True)
-        h_rec.copy_(rec[:h_rec.shape[0]], non_blocking=True)
-        ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(dev))
-        pending = _PendingEpisodes(self, ev, slot)
-        setattr(self, slot + "_pending", pending)
-        return pending
-
-    def _episodes_torch(self, rew64, done, T, n, device, true=False):
-        import torch
-        csum = torch.cumsum(rew64, 0)
-        ends = done.nonzero()                                              # [K, 2] (t, env), sorted by t then env
-        ep_rets, ep_lens = [], []
-        cur_ret, cur_len = (self.cur_true_ret, self.cur_true_len) if true else (self.cur_ret, self.cur_len)
-        if ends.numel():
-            te, ee = ends[:, 0], ends[:, 1]
-            # previous end of the same env inside the segment (or -1): sort by (env, t) and shift
-            order = torch.argsort(ee * T + te)
-            te_s, ee_s = te[order], ee[order]
-            prev_t = torch.full_like(te_s, -1)
-            same = ee_s[1:] == ee_s[:-1]
-            prev_t[1:] = torch.where(same, te_s[:-1], torch.full_like(te_s[:-1], -1))
-            seg_ret = csum[te_s, ee_s] - torch.where(prev_t >= 0, csum[prev_t.clamp(min=0), ee_s], torch.zeros_like(csum[te_s, ee_s]))
-            seg_len = te_s - prev_t
-            opening = prev_t < 0                                           # first end of that env: add what it carried in
-            seg_ret = seg_ret + torch.where(opening, cur_ret[ee_s], torch.zeros_like(seg_ret))
-            seg_len = seg_len + torch.where(opening, cur_len[ee_s], torch.zeros_like(seg_len))
-            inv = torch.empty_like(order); inv[order] = torch.arange(order.numel(), device=device)
-            ep_rets = seg_ret[inv].tolist(); ep_lens = seg_len[inv].tolist()
-        # carry the open episodes into the next segment
-        last_end = torch.where(done, self.step_idx.expand(T, n), torch.zeros((T, n), dtype=torch.int64, device=device)).amax(0)   # 1-based
-        tail_ret = csum[-1] - torch.where(last_end > 0, csum[(last_end - 1).clamp(min=0), torch.arange(n, device=device)], torch.zeros_like(csum[-1]))
-        new_ret = torch.where(last_end > 0, tail_ret, cur_ret + tail_ret)
-        new_len = torch.where(last_end > 0, T - last_end, cur_len + T)
-        if true:
-            self.cur_true_ret, self.cur_true_len = new_ret, new_len
-        else:
-            self.cur_ret, self.cur_len = new_ret, new_len
-        return ep_rets, ep_lens
 
 
 def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first_reset="rsi", fused=False, reward_giver=None, bootstrap_time_limit=False,
@@ -568,7 +586,7 @@ def traj_segment_generator(pi, env, horizon, stochastic=True, device=None, first
     "ep_true_rets", the env's returns of the same episodes.
 
     bootstrap_time_limit (env with max_episode_steps > 0): the segment also carries "vboot" [T,N] f32, the critic's value of every state the time
-    limit cut off (SegmentCollector._bootstrap_values), which `add_vtarg_and_adv` adds to the one-step target there.
+    limit cut off (_TimeLimitBootstrap.values), which `add_vtarg_and_adv` adds to the one-step target there.
 
     reward_terms (env with reward="imitation"): the segment also carries `err_sums` (Segment), from one terms launch per segment."""
     c = SegmentCollector(pi, env, horizon, stochastic, device, first_reset, fused=fused, reward_giver=reward_giver, bootstrap_time_limit=bootstrap_time_limit,
@@ -588,7 +606,7 @@ def pipelined_segment_generator(pi, envs, horizon, stochastic=True, first_reset=
     cols = [SegmentCollector(pi, e, horizon, stochastic, None, first_reset, stream=torch.cuda.Stream(device=pi.device), fused=fused,
                              bootstrap_time_limit=bootstrap_time_limit, reward_terms=reward_terms) for e in envs]
     while True:
-        if getattr(pi, "_dirty", False) or getattr(pi, "_packed", None) is None:
+        if _pack_is_stale(pi):
             pi.pack()                                  # once, on the current stream, before the side streams fork from it
         for c in cols:
             c.launch()
@@ -619,81 +637,3 @@ def flatten_segment(seg):
             v = seg[k]
             out[k] = v.transpose(0, 1).reshape((-1,) + tuple(v.shape[2:]))
     return out
-
-
-class DoubleBufferedGather:
-    """Per-horizon all-gather of the rollout block, overlapped with stepping: two [T, n, 87] blocks per rank; while block k
-    travels (async all-gather on the collective's own stream) the envs fill block 1 - k.  `row(t)` returns the row to fill at
-    step t (first making sure that this block's previous gather has finished), `commit(t)` launches the gather when step t
-    completes a horizon, `drain()` waits for everything outstanding.  Single-process runs degenerate to one local block.
-
-    Backend "nccl" (RCCL) gathers device tensors in place.  Backend "gloo" has no device all-gather: a block on a GPU is first
-    copied to pinned host memory (stream-ordered), the gather runs between host buffers (async, gloo's own threads) and the
-    result stays on the host in `gathered_host[k]` — the path the world-2 tests and single-GPU multi-rank runs use."""
-
-    def __init__(self, horizon, n_local, device="cpu", world=None, collective=None, ob_width=56):
-        """ob_width: the width of the observations the caller will write into the rows; the 87-wide row holds 56 (obs_mode "dp_env_v3") and nothing else.
-        collective: run the multi-rank code path (two blocks, the all-gather into `gathered`) — default: when the process group has more
-        than one rank; True forces it for a group of ONE rank, which executes the same RCCL calls where only one GPU is visible."""
-        import torch
-        import torch.distributed as dist
-        if world is None:
-            world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        if int(ob_width) != 56:
-            raise ValueError("the gathered rollout row is 87 wide (56 obs | 28 act | reward | done | vpred): observations of width %d (obs_mode "
-                             "'deepmimic') are not gathered" % int(ob_width))
-        self.T, self.n, self.world = int(horizon), int(n_local), int(world)
-        self.collective = (self.world > 1) if collective is None else bool(collective)
-        nb = 2 if self.collective else 1
-        self.blocks = [torch.zeros((self.T, self.n, ROW), dtype=torch.float32, device=device) for _ in range(nb)]
-        on_gpu = torch.device(device).type == "cuda"
-        self.host_staged = self.collective and on_gpu and dist.get_backend() == "gloo"
-        self.gathered = self.gathered_host = self.host_blocks = None
-        if self.collective and self.host_staged:
-            self.host_blocks = [torch.zeros((self.T, self.n, ROW), dtype=torch.float32).pin_memory() for _ in range(nb)]
-            self.gathered_host = [torch.empty((self.world * self.T, self.n, ROW), dtype=torch.float32) for _ in range(nb)]
-        elif self.collective:
-            self.gathered = [torch.empty((self.world * self.T, self.n, ROW), dtype=torch.float32, device=device) for _ in range(nb)]
-        self.pending = [None] * nb
-        self.completed = 0                      # gathers launched so far
-
-    def _k(self, t):
-        return (t // self.T) % len(self.blocks)
-
-    def row(self, t):
-        k = self._k(t)
-        if t % self.T == 0 and self.pending[k] is not None:
-            self.pending[k].wait(); self.pending[k] = None
-        return self.blocks[k][t % self.T]
-
-    def block(self, t):
-        """The whole [T, n, 87] block step t belongs to (for producers that fill a block in one go at the end of a horizon)."""
-        k = self._k(t)
-        if self.pending[k] is not None:
-            self.pending[k].wait(); self.pending[k] = None
-        return self.blocks[k]
-
-    def commit(self, t):
-        """Call after step t's row has been written.  Returns the index of the gathered buffer when a gather was launched."""
-        if self.collective and (t + 1) % self.T == 0:
-            import torch
-            import torch.distributed as dist
-            k = self._k(t)
-            if self.host_staged:
-                self.host_blocks[k].copy_(self.blocks[k], non_blocking=True)
-                torch.cuda.current_stream(self.blocks[k].device).synchronize()      # the host copy is complete before gloo reads it
-                self.pending[k] = dist.all_gather_into_tensor(self.gathered_host[k], self.host_blocks[k], async_op=True)
-            else:
-                self.pending[k] = dist.all_gather_into_tensor(self.gathered[k], self.blocks[k], async_op=True)
-            self.completed += 1
-            return k
-        return None
-
-    def result(self, k):
-        """The gathered [world * T, n, 87] buffer of slot k (device tensor, or the host tensor on the host-staged path)."""
-        return self.gathered_host[k] if self.host_staged else self.gathered[k]
-
-    def drain(self):
-        for k in range(len(self.pending)):
-            if self.pending[k] is not None:
-                self.pending[k].wait(); self.pending[k] = None

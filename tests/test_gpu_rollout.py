@@ -668,7 +668,7 @@ def test_segment_collector_chooses_the_kernel_from_its_own_horizons():
         assert env.horizon_packed_ok
         c = SegmentCollector(pol, env, T, stochastic=True, first_reset="init", fused=True)
         if tolerate is not None:
-            c.HORIZON_REDO_RATE_MAX = tolerate
+            c.kernel_choice.REDO_RATE_MAX = tolerate
         segs = []
         for _ in range(5):
             c.launch(); segs.append(c.collect())
@@ -719,24 +719,19 @@ def test_kernels_and_launch_forms_hand_the_state_over_to_each_other():
 
 @pytest.mark.gpu
 def test_episode_scan_kernel_equals_the_generators_bookkeeping_loop():
-    """dm_episode_scan (SegmentCollector._episodes_native) against `cur_ep_ret += rew; cur_ep_len += 1; if new: append, reset` of
+    """dm_episode_scan (rollout.EpisodeScan.native) against `cur_ep_ret += rew; cur_ep_len += 1; if new: append, reset` of
     src/trpo.py:68-79 run env by env on the host, over three consecutive segments (episodes that span segments, several ends per env
     and segment, envs that never end): the same returns (float64 sums in step order: exact), lengths and time-major order — and the torch
     formulation it replaces on the device agrees to rounding."""
     import torch
-    from deepmimic_mujoco_amd.rollout import SegmentCollector
+    from deepmimic_mujoco_amd.rollout import EpisodeScan
     T, n = 37, 301
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(5)
 
-    def fresh():
-        c = SegmentCollector.__new__(SegmentCollector)
-        c.T, c.n, c.device = T, n, dev
-        c.cur_ret = torch.zeros(n, dtype=torch.float64, device=dev); c.cur_len = torch.zeros(n, dtype=torch.int64, device=dev)
-        c.step_idx = torch.arange(1, T + 1, device=dev, dtype=torch.int64)[:, None]
-        return c
-    a, b = fresh(), fresh()
-    a.EP_HEAD = 64                                                            # (most segments below end more episodes than the first copy holds)
+    class ShortHead(EpisodeScan):
+        EP_HEAD = 64                                                          # (most segments below end more episodes than the first copy holds)
+    a, b = ShortHead(T, n, dev), EpisodeScan(T, n, dev)
     ret = np.zeros(n); ln = np.zeros(n, dtype=np.int64)
     for seg in range(3):
         rew = rng.randn(T, n)
@@ -750,12 +745,12 @@ def test_episode_scan_kernel_equals_the_generators_bookkeeping_loop():
                 if done[t, e]:
                     want_r.append(ret[e]); want_l.append(int(ln[e])); ret[e] = 0.0; ln[e] = 0
         rew_t, done_t = torch.as_tensor(rew, device=dev), torch.as_tensor(done, device=dev)
-        got_r, got_l = a._episodes_native(rew_t, done_t).result()
+        got_r, got_l = a.native(rew_t, done_t).result()
         assert got_l == want_l and got_r == want_r
         assert np.array_equal(a.cur_len.cpu().numpy(), ln) and np.array_equal(a.cur_ret.cpu().numpy(), ret)
-        old_r, old_l = b._episodes_torch(rew_t, done_t.to(torch.bool), T, n, dev)
+        old_r, old_l = b.torch(rew_t, done_t.to(torch.bool))
         assert old_l == want_l and np.allclose(old_r, want_r, rtol=0, atol=1e-9)
-    empty_r, empty_l = a._episodes_native(torch.zeros((T, n), dtype=torch.float64, device=dev), torch.zeros((T, n), dtype=torch.uint8, device=dev)).result()
+    empty_r, empty_l = a.native(torch.zeros((T, n), dtype=torch.float64, device=dev), torch.zeros((T, n), dtype=torch.uint8, device=dev)).result()
     assert empty_r == [] and empty_l == [] and np.array_equal(a.cur_len.cpu().numpy(), ln + T)
 
 
@@ -814,7 +809,7 @@ def test_default_kernel_choice_by_batch_size():
     for n, contacts, want in ((4096, True, True), (3072, True, False), (512, False, True)):
         env = DPVecEnv(n, motion="walk", device=0, reward="alive", autoreset="rsi", seed=0, contacts=contacts, limits=contacts)
         assert bool(env.packed) == want, (n, contacts, env.packed)
-        assert bool(env.batch.__dict__.get("_auto")) == want            # the chooser keeps watching the batch's own row statistics
+        assert bool(env.batch._auto) == want            # the chooser keeps watching the batch's own row statistics
         env.reset("rsi")
         obs, rew, done, _ = env.step(np.zeros((n, 28)))
         assert np.isfinite(obs).all() and obs.shape == (n, 56)

@@ -336,12 +336,12 @@ def test_fused_rollout_step_is_refused_without_the_native_path():
 
 
 def test_collector_kernel_choice_is_a_function_of_the_last_horizons_statistics():
-    """`SegmentCollector._choose_kernel` (host logic, no device): starts packed, hands a batch to the one-env steps when more than
-    HORIZON_REDO_RATE_MAX of the last horizon's env-steps overflowed the packed path, hands it back when no environment holds more than
-    HORIZON_HEAVY_ROWS constraint rows, and leaves batches alone whose configuration pins the kernel."""
+    """`rollout.HorizonKernelChoice` (host logic, no device): starts packed, hands a batch to the one-env steps when more than
+    REDO_RATE_MAX of the last horizon's env-steps overflowed the packed path, hands it back when no environment holds more than
+    HEAVY_ROWS constraint rows, and leaves batches alone whose configuration pins the kernel."""
     import numpy as np
     from deepmimic_mujoco_amd import _abi as A
-    from deepmimic_mujoco_amd.rollout import SegmentCollector
+    from deepmimic_mujoco_amd.rollout import HorizonKernelChoice
 
     class FakeBatch:
         REDO_RATE_MAX, HEAVY_ROWS = 3e-4, 30
@@ -358,6 +358,13 @@ def test_collector_kernel_choice_is_a_function_of_the_last_horizons_statistics()
         def rebaseline_auto(self):
             pass
 
+        def suspend_auto(self):
+            was, self._auto = self._auto, False
+            return was
+
+        def resume_auto(self):
+            self._auto = True
+
         def redo_total(self):
             return self.redo
 
@@ -369,27 +376,59 @@ def test_collector_kernel_choice_is_a_function_of_the_last_horizons_statistics()
         def __init__(self, ok):
             self.batch, self.horizon_packed_ok = FakeBatch(), ok
 
-    c = SegmentCollector.__new__(SegmentCollector)
-    c.env, c.T, c.n, c._redo_seen, c.kernel_switches = FakeEnv(True), 100, 8, None, 0
+    c = HorizonKernelChoice(FakeEnv(True), 100, 8)
     b = c.env.batch
-    c._choose_kernel()                                                   # first horizon: packed, the per-step chooser switched off
+    c.choose()                                                   # first horizon: packed, the per-step chooser switched off
     assert b.options[A.OPT_PACKED] == 1 and b._auto is False and c.kernel_switches == 1
     b.redo += 10                                                         # 10 / 800 = 1.25 % of env-steps: tolerated (7 %)
-    c._choose_kernel()
+    c.choose()
     assert b.options[A.OPT_PACKED] == 1 and c.kernel_switches == 1
     b.redo += 80                                                         # 10 %: to the one-env steps
-    c._choose_kernel()
+    c.choose()
     assert b.options[A.OPT_PACKED] == 0 and c.kernel_switches == 2
     b.nefc[3] = 41                                                       # an environment beyond a slot's rows: stays
-    c._choose_kernel()
+    c.choose()
     assert b.options[A.OPT_PACKED] == 0 and c.kernel_switches == 2
     b.nefc[3] = 36                                                       # nobody above 38 rows: back
-    c._choose_kernel()
+    c.choose()
     assert b.options[A.OPT_PACKED] == 1 and c.kernel_switches == 3
-    c2 = SegmentCollector.__new__(SegmentCollector)
-    c2.env, c2.T, c2.n, c2._redo_seen, c2.kernel_switches = FakeEnv(False), 100, 8, None, 0
-    c2._choose_kernel()                                                  # DPVecEnv(packed=False / True), float32, v1-quat reward: not touched
+    c2 = HorizonKernelChoice(FakeEnv(False), 100, 8)
+    assert c2.choose() is None                                                 # DPVecEnv(packed=False / True), float32, v1-quat reward: not touched
     assert c2.env.batch.options == {} and c2.kernel_switches == 0 and c2.env.batch._auto is True
+
+
+def test_episode_scan_tensor_form_equals_the_generators_bookkeeping_loop():
+    """`rollout.EpisodeScan.torch` on the host against `cur_ep_ret += rew; cur_ep_len += 1; if new: append, reset` of src/trpo.py:68-79 run env by env,
+    over three consecutive segments of T = 5 steps and n = 3 envs: env 0 never ends, env 1 ends twice inside the first segment, env 2 ends only in a later
+    one (its episode spans segments).  Two scans run side by side on different rewards and ends: each keeps its own carry.  The rewards are multiples of
+    1/8, so every sum and difference of sums is exact and the comparison is `==`."""
+    from deepmimic_mujoco_amd.rollout import EpisodeScan
+    T, n = 5, 3
+    rng = np.random.RandomState(3)
+    done_a = np.zeros((3, T, n), dtype=np.uint8)
+    done_a[0, 1, 1] = done_a[0, 3, 1] = 1                                 # env 1: twice inside segment 0
+    done_a[2, 2, 2] = 1                                                   # env 2: 13 steps after the start, in segment 2
+    done_b = np.zeros((3, T, n), dtype=np.uint8)
+    done_b[1, 4, 0] = done_b[2, 0, 0] = done_b[1, 0, 2] = 1               # other ends: at a segment's last and first step
+    streams = [(EpisodeScan(T, n, "cpu"), done_a, rng.randint(-16, 17, size=(3, T, n)) / 8.0, np.zeros(n), np.zeros(n, dtype=np.int64)),
+               (EpisodeScan(T, n, "cpu"), done_b, rng.randint(-16, 17, size=(3, T, n)) / 8.0, np.zeros(n), np.zeros(n, dtype=np.int64))]
+    ended = [0, 0]
+    for seg in range(3):
+        for k, (scan, done, rew, ret, ln) in enumerate(streams):          # interleaved: a, b, a, b, ...
+            want_r, want_l = [], []
+            for t in range(T):
+                for e in range(n):
+                    ret[e] += rew[seg, t, e]; ln[e] += 1
+                    if done[seg, t, e]:
+                        want_r.append(ret[e]); want_l.append(int(ln[e])); ret[e] = 0.0; ln[e] = 0
+            got_r, got_l = scan.torch(torch.as_tensor(rew[seg]), torch.as_tensor(done[seg]).to(torch.bool))
+            assert got_l == want_l and got_r == want_r, (seg, k)
+            assert np.array_equal(scan.cur_len.numpy(), ln) and np.array_equal(scan.cur_ret.numpy(), ret), (seg, k)
+            ended[k] += len(want_l)
+    assert ended == [3, 3] and streams[0][4][0] == 15 and not np.array_equal(streams[0][0].cur_ret.numpy(), streams[1][0].cur_ret.numpy())
+    scan, ln = streams[0][0], streams[0][4]
+    assert scan.scan(torch.zeros((T, n), dtype=torch.float64), torch.zeros((T, n), dtype=torch.uint8)) == ([], [])   # host tensors: `scan` takes the tensor form
+    assert np.array_equal(scan.cur_len.numpy(), ln + T)
 
 
 def test_segment_dict_materialises_pending_episode_lists_on_access():
