@@ -192,9 +192,25 @@ DM_DEV bool rk4_step(const DevModel<R>& M, Shared<R>& s, StepScratch<R>& x, int 
   return true;
 }
 
+// The mocap frame env `env` is at as the env step starts: what the action front ends of modes 1, 2 and 4 track.  Reward modes 0, 1 and 3 keep
+// the frame itself in frame_idx.  Modes 2 and 4 keep the reference's two cursors (set_frame below): frame_idx counts steps without bound and the
+// frame is looked up through frame_init, exactly as their reward epilogues do — mode 4 with the v1 epilogue's update interval `upd`.  Always a row
+// of the mocap tables while frame_idx and frame_init are not negative.  Called inside the action-mode branches only: mode 0 pays nothing for it.
+template <class R>
+DM_DEV int step_start_frame(const DevModel<R>& M, const Batch<R>& B, int env, int n_substeps) {
+  const int idx = B.frame_idx[env];
+  if (B.reward_mode == REW_V2_POSE) return (idx + B.frame_init[env]) % B.n_frames;
+  if (B.reward_mode == REW_V1_QUAT) {
+    int upd = (int)floor(B.mocap_dt / (M.timestep * n_substeps));
+    if (upd < 1) upd = 1;
+    return (idx / upd + B.frame_init[env]) % B.n_frames;
+  }
+  return idx;
+}
+
 // load one env's row from HBM (coalesced: lane k reads element k) and turn the action into actuator forces
 template <class R>
-DM_DEV void load_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int env, int lane, const double* action) {
+DM_DEV void load_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int env, int lane, const double* action, int n_substeps = 1) {
   if (lane < NQ) s.qpos[lane] = B.qpos[(size_t)env * NQ + lane];
   if (lane < NV) { s.qvel[lane] = B.qvel[(size_t)env * NV + lane]; s.qws[lane] = B.qws[(size_t)env * NV + lane]; s.act[lane] = 0; }
   if (lane == 0) { s.status = 0; s.nefc = 0; s.ncon = 0; s.solver_iter = 0; s.aovf = B.aovf ? B.aovf + (size_t)env * AOVF_COLS * 64 : (R*)0; }
@@ -202,10 +218,10 @@ DM_DEV void load_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int 
   if (action && lane < NU) {
     R a = (R)action[(size_t)env * NU + lane];   // (the C ABI's buffers are float64 whatever the arithmetic type R)
     if (B.action_mode == 1) {  // P-control towards the current mocap frame (src/env_torque_test.py:14-20)
-      const int idx = B.frame_idx[env];
+      const int idx = step_start_frame(M, B, env, n_substeps);
       a += R(0.8) * (B.mocap_cfg[(size_t)idx * NQ + 7 + lane] - s.qpos[7 + lane]);
     } else if (B.action_mode == 2) {  // PD torque kp*dq + kd*dv written to ctrl (src/mujoco/setting_states.py:207-226)
-      const int idx = B.frame_idx[env];
+      const int idx = step_start_frame(M, B, env, n_substeps);
       a += M.kp[lane + 6] * (B.mocap_cfg[(size_t)idx * NQ + 7 + lane] - s.qpos[7 + lane]) +
            M.kd[lane + 6] * (B.mocap_vel[(size_t)idx * NV + 6 + lane] - s.qvel[6 + lane]);
     }
@@ -518,20 +534,20 @@ DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
   const bool kin0 = B.kin && dmw::uniform((int)B.kin_ok[env]) != 0;
   R kreg[KIN_PER_LANE];
   if (kin0) fetch_kin(kreg, B.kin + (size_t)env * KIN_DOUBLES, lane);
-  R qbar = 0, vbar = 0;                  // SPD: the target of dof `lane` (the frame cursor as it stands at the start of the env step)
+  R qbar = 0, vbar = 0;                  // SPD: the target of dof `lane` (the mocap frame the env is at as the env step starts: step_start_frame)
   if constexpr (SPD) {
     load_env(M, B, s, env, lane, (const double*)0);
     if (lane >= 6 && lane < NV) {
       const int u = lane - 6;
       if (action) qbar = (R)action[(size_t)env * NU + u];
       if (B.action_mode == 4) {
-        const int idx = B.frame_idx[env];
+        const int idx = step_start_frame(M, B, env, n_substeps);
         qbar += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
         vbar = B.mocap_vel[(size_t)idx * NV + 6 + u];
       }
     }
   } else
-  load_env(M, B, s, env, lane, action);
+  load_env(M, B, s, env, lane, action, n_substeps);
   if (kin0) { place_kin(s, kreg, lane); dmw::sync(); }
   for (int k = 0; k < n_substeps; k++) {   // do_simulation(action, n)
     if constexpr (SPD) spd_control(M, B, s, env, lane, lt, qbar, vbar, k == 0 && kin0);

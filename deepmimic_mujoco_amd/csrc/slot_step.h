@@ -84,7 +84,7 @@ DM_DEV void slot_rk4_step(const DevModel<R>& M, SlotShared<R>& s, const SlotTabl
 
 // load the slot's env row (each slot reads 128-byte runs of its own row) and turn the action into actuator forces
 template <class R>
-DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, int env, int sl, bool live, const double* action) {
+DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, int env, int sl, bool live, const double* action, int n_substeps = 1) {
 #pragma unroll
   for (int c = 0; c < Q_PASSES; c++) {
     const int i = sl + SW * c;
@@ -100,10 +100,10 @@ DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>
       if (u < NU) {
         R a = (R)action[(size_t)env * NU + u];
         if (B.action_mode == 1) {
-          const int idx = B.frame_idx[env];
+          const int idx = step_start_frame(M, B, env, n_substeps);
           a += R(0.8) * (B.mocap_cfg[(size_t)idx * NQ + 7 + u] - s.qpos[7 + u]);
         } else if (B.action_mode == 2) {
-          const int idx = B.frame_idx[env];
+          const int idx = step_start_frame(M, B, env, n_substeps);
           a += M.kp[u + 6] * (B.mocap_cfg[(size_t)idx * NQ + 7 + u] - s.qpos[7 + u]) + M.kd[u + 6] * (B.mocap_vel[(size_t)idx * NV + 6 + u] - s.qvel[6 + u]);
         }
         if (live) B.ctrl[(size_t)env * NU + u] = a;
@@ -315,7 +315,7 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   if (PROF) tstart = dmw::clk();
   const LaneTopo lt = lane_topo(sl);
   if constexpr (CARRY) { if (!kin_carry && sl == 0) s.kin_ok() = R(0); }       // (ordered before the first read by slot_load_env's hand-off)
-  DofVec<R> qbar, vbar;                  // SPD: dof-distributed targets (the frame cursor as it stands at the start of the env step)
+  DofVec<R> qbar, vbar;                  // SPD: dof-distributed targets (the mocap frame the env is at as the env step starts: env_step.h step_start_frame)
   if constexpr (SPD) {
     slot_load_env(M, B, s, env, sl, live, (const double*)0);
 #pragma unroll
@@ -326,14 +326,14 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
         const int u = d - 6;
         if (action) qbar.r[c] = (R)action[(size_t)env * NU + u];
         if (B.action_mode == 4) {
-          const int idx = B.frame_idx[env];
+          const int idx = step_start_frame(M, B, env, n_substeps);
           qbar.r[c] += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
           vbar.r[c] = B.mocap_vel[(size_t)idx * NV + 6 + u];
         }
       }
     }
   } else
-  slot_load_env(M, B, s, env, sl, live, action);
+  slot_load_env(M, B, s, env, sl, live, action, n_substeps);
   R xip[3];
   int why = 0;
   for (int k = 0; k < n_substeps; k++) {

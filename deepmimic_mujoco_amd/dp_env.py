@@ -450,6 +450,9 @@ class DPVecEnv(object):
         action_mode: one of ACTION_MODES.  "spd-target" / "spd-mocap": the action is a PD target pose, tracked by a stable PD controller evaluated at every
         simulation substep (include/dmenv.h DM_OPT_ACTION_MODE); `action_space` is then the hinges' joint range ("spd-target") — informative, not enforced.
         These two modes run on the per-step kernels: horizon launches and the step queue fall back to step launches with identical results.
+        "p-control", "pd" and "spd-mocap" track the mocap frame the env is at as the env step starts — the frame its `reward` counts from: the frame cursor
+        itself, but (cursor + drawn frame) % n_frames with reward="v2-pose" and (cursor // update interval + drawn frame) % n_frames with "v1-quat",
+        whose cursors count the episode's steps.
         step_queue: DM_OPT_STEP_QUEUE depth (0 = off): queue `batch.step` calls and run them as one horizon launch (see below).
         obs_mode: "dp_env_v3" (default: the 56 numbers the step launch writes; nothing else is launched) or "deepmimic": `reset`, `step` and `step_wait` return
         [N, 171] DeepMimic state features (state_features.py) and `observation_space` has shape (171,).  A step is then the step launch into an internal

@@ -115,12 +115,16 @@ enum {
                                L1 angular-rate and root errors, every int(mocap_dt // dt) steps, minus 0.1 sum ctrl^2) on this model's
                                hinge triples; modes 3 and 4 need dm_mocap_set_imitation() */
   DM_OPT_AUTORESET = 2,   /* 0 off (default), 1 RSI on done, 2 noisy-init on done (DummyVecEnv convention) */
-  DM_OPT_ACTION_MODE = 3, /* 0 raw ctrl (dp_env_v3.py:112, default), 1 P-control 0.8*(mocap_cfg - q) + action (env_torque_test.py:20),
-                             2 PD kp*(mocap_cfg - q) + kd*(mocap_vel - v) + action (setting_states.py:207-226, gains mocap_util.py:22-24).
+  DM_OPT_ACTION_MODE = 3, /* 0 raw ctrl (dp_env_v3.py:112, default), 1 P-control 0.8*(mocap_cfg[k] - q) + action (env_torque_test.py:20),
+                             2 PD kp*(mocap_cfg[k] - q) + kd*(mocap_vel[k] - v) + action (setting_states.py:207-226, gains mocap_util.py:22-24).
                              Modes 1 and 2 add their feedback term, evaluated ONCE per env step, to an action that is a motor command.
+                             k, in modes 1, 2 and 4, is THE MOCAP FRAME THE ENV IS AT AS THE ENV STEP STARTS — the frame its reward mode
+                             counts from: DM_F_FRAME_IDX in reward modes 0, 1 and 3; (DM_F_FRAME_IDX + DM_F_FRAME_INIT) % n_frames in mode 2
+                             and (DM_F_FRAME_IDX / upd + DM_F_FRAME_INIT) % n_frames in mode 4, where DM_F_FRAME_IDX counts the episode's
+                             steps without bound and upd = max(1, floor(mocap_dt / (timestep * n_substeps))) is that reward's update interval.
                              3 "spd-target": the action is a TARGET POSE qbar = action (28 absolute hinge angles, rad), target rate vbar = 0 —
-                             DeepMimic's action.  4 "spd-mocap": qbar = mocap_cfg[frame_idx][7:] + action, vbar = mocap_vel[frame_idx][6:]
-                             (frame_idx as at the start of the env step) — the stable form of mode 2.  In both a stable (implicit) PD controller
+                             DeepMimic's action.  4 "spd-mocap": qbar = mocap_cfg[k][7:] + action, vbar = mocap_vel[k][6:]
+                             (k as above) — the stable form of mode 2.  In both a stable (implicit) PD controller
                              (cImpPDController::CalcControlForces, code.md:147-179) turns the target into ctrl at the start of EVERY simulation
                              substep, from the state (q, v) that substep starts at, and holds it through the substep; h = the timestep:
                                p = kp (qbar - q - h v),  d = kd (vbar - v)   (hinge dofs; kp, kd as in mode 2; 0 on the root dofs)
