@@ -46,6 +46,12 @@ constexpr int DOF_PASSES = (NV + SW - 1) / SW, HINGE_PASSES = (NU + SW - 1) / SW
 #ifndef DM_SLOT_ASSUME
 #define DM_SLOT_ASSUME 31
 #endif
+// DM_SLOT_A10T: the two-set A build takes its block A10 from A01 through LDS (slot_a10_transpose) instead of forming it a second time.  Measured
+// (profiles/r07_ab_kernel_variants.md): the two-set evaluation 86.2 k -> 82.9 k cycles, the judged line +2 %, the 512-step line +0.8 %, bit-identical results.
+// (Same file: the smooth force's half solve as a spare row instead of a vector in every lane — fewer instructions, 1.4 .. 8 % SLOWER: not here.)
+#ifndef DM_SLOT_A10T
+#define DM_SLOT_A10T 1
+#endif
 #define DM_SLOT_LANE_AT(bit, x) (((DM_SLOT_ASSUME) >> (bit)) & 1 ? dmw::launder_slot_lane(x) : dmw::launder(x))
 
 template <class R>
@@ -804,10 +810,12 @@ template <int NS, class R> struct SlotRowStep<NV, NS, R> { static DM_DEV void ru
 
 // ---- nested unrolling over the wave's largest row count (wave-uniform `nmax`): column / row group c is only reached through c - 4 ---
 // column CC of A = Y Y^T: AR[k][CC] = Y_(row of the lane, set k) . Y_CC, the partner row broadcast inside the DPP row
-template <int CC, int NS, class R>
+// T10 (two sets): the block A10 (the second set's rows, columns < 16) is not formed here — it is A01 transposed, which the lanes of the columns hold
+// (slot_a10_transpose)
+template <int CC, int NS, class R, bool T10 = false>
 DM_DEV void slot_acol(R (*AR)[16 * NS], const R (*y)[NV]) {
 #pragma unroll
-  for (int k = 0; k < NS; k++) {
+  for (int k = 0; k < (T10 && CC < 16 ? 1 : NS); k++) {
     R acc0 = 0, acc1 = 0;                 // two partial sums (even / odd dofs): halves the dependent chain of the 34 fused multiply-adds
 #pragma unroll
     for (int d = 0; d + 8 <= NV; d += 8) dmw::row_fmac8<CC % 16>(acc0, acc1, &y[CC / 16][d], &y[k][d]);
@@ -816,15 +824,31 @@ DM_DEV void slot_acol(R (*AR)[16 * NS], const R (*y)[NV]) {
     AR[k][CC] = acc0 + acc1;
   }
 }
-template <int C, int NS, class R>
+template <int C, int NS, class R, bool T10 = false>
 struct SlotACols {
   static DM_DEV void run(R (*AR)[16 * NS], const R (*y)[NV], int nmax) {
     if constexpr (C < 16 * NS) {
-      slot_acol<C, NS, R>(AR, y); slot_acol<C + 1, NS, R>(AR, y); slot_acol<C + 2, NS, R>(AR, y); slot_acol<C + 3, NS, R>(AR, y);
-      if (C + 4 < nmax) SlotACols<C + 4, NS, R>::run(AR, y, nmax);
+      slot_acol<C, NS, R, T10>(AR, y); slot_acol<C + 1, NS, R, T10>(AR, y); slot_acol<C + 2, NS, R, T10>(AR, y); slot_acol<C + 3, NS, R, T10>(AR, y);
+      if (C + 4 < nmax) SlotACols<C + 4, NS, R, T10>::run(AR, y, nmax);
     }
   }
 };
+// A10 = A01^T through LDS: lane sl holds row sl of A01 in AR[0][16 ..] and takes row sl of A10 = column sl of A01 — the very sums the build would form (the same
+// products in the same order: a product's two factors swapped), so bit for bit what slot_acol gives.  The 16 x 17 tile (padded: the column reads of the 16
+// lanes fall into different banks) lies in the slot's adjacent qd + cdof regions, dead between the row build and the result's store.
+constexpr int A10_PITCH = SW + 1;
+static_assert(sizeof(((SlotShared<double>*)0)->qd) + sizeof(((SlotShared<double>*)0)->cdof) >= sizeof(double) * SW * A10_PITCH &&
+              sizeof(((SlotShared<float>*)0)->qd) + sizeof(((SlotShared<float>*)0)->cdof) >= sizeof(float) * SW * A10_PITCH, "slot_a10_transpose: the tile fits the qd + cdof regions");
+template <class R>
+DM_DEV void slot_a10_transpose(R (*AR)[2 * SW], SlotShared<R>& s, int sl) {
+  R* tile = &s.qd.o.qacc[0];
+#pragma unroll
+  for (int c = 0; c < SW; c++) tile[sl * A10_PITCH + c] = AR[0][SW + c];
+  dmw::sync();
+#pragma unroll
+  for (int c = 0; c < SW; c++) AR[1][c] = tile[c * A10_PITCH + sl];
+  dmw::sync();
+}
 // warm start: AR[k][c] scaled in place (row by -1 / A_rr);  t_k += A_scaled[k][c] f_c
 template <int CC, int NS, class R>
 DM_DEV void slot_warm_col(R (*AR)[16 * NS], R* t, const R* f, const R* ndinv) {
@@ -1173,7 +1197,9 @@ DM_DEV void slot_constraint(const DevModel<R>& M, SlotShared<R>& s, int sl_in, i
 #pragma unroll
     for (int c = 0; c < NC; c++) { AR[k][c] = 0; dmw::pin_value(AR[k][c]); }
   dmw::dpp_settle();
-  SlotACols<0, NF, R>::run(AR, y, nmax);
+  constexpr bool T10 = NS == 2 && DM_SLOT_A10T;     // (three sets: the region holds the surplus rows' Y by now)
+  SlotACols<0, NF, R, T10>::run(AR, y, nmax);
+  if constexpr (T10) slot_a10_transpose(AR, s, sl);
   R diag[NF];
 #pragma unroll
   for (int k = 0; k < NF; k++) {
