@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
-SOURCES = ["dmenv.hip", "views.hip", "learner.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_rollout_term.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "packed_body.h", "host_common.h", "batch_host.h", "kernels.h", "env_kernel.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "policy_wave_launch_order.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "slot_term.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h", "floor_contact.h", "term_kernel.h", "terms_kernel.h", "view_stage.h"]
+SOURCES = ["dmenv.hip", "views.hip", "learner.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_rollout_term.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "packed_body.h", "host_common.h", "batch_host.h", "kernels.h", "env_kernel.h", "step_rules.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "policy_wave_launch_order.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "slot_term.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h", "floor_contact.h", "term_kernel.h", "terms_kernel.h", "view_stage.h"]
 OUT = os.path.join(HERE, "libdmenv.so")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-shift-count-negative", "-Wno-implicit-const-int-float-conversion"]
 # Eight translation units (kernels.h lists them), each with the backend options its kernels want (round 4, A/B in profiles/r04_ab_kernel_variants.md):

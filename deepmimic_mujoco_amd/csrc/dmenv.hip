@@ -186,7 +186,7 @@ __global__ void k_get_obs(Batch<Real> B, Ext* __restrict__ obs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B.n_envs * NOBS) return;
   const int env = i / NOBS, k = i % NOBS;
-  obs[i] = k < 28 ? B.qpos[(size_t)env * NQ + 7 + k] : B.qvel[(size_t)env * NV + 6 + (k - 28)];
+  obs[i] = k < 28 ? B.qpos[(size_t)env * NQ + 7 + k] : B.qvel[(size_t)env * NV + 6 + (k - 28)];   // (step_rules.h obs_element, restated: through it the kernel takes two more registers)
 }
 
 // field reads / writes of the float32 build: device state is `Real`, the C ABI speaks float64
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void k_debug_forward(const DevModel<Real>* __re
   const int lane = dmw::lane();
   load_env(*Mp, B, s, env, lane, (const Ext*)0);
   // actuator forces from the stored ctrl
-  if (lane < NU) { const int d = lane + 6; s.act[d] = Mp->gear[d] * clampr(B.ctrl[(size_t)env * NU + lane], Mp->ctrl_lo[d], Mp->ctrl_hi[d]); }
+  if (lane < NU) s.act[lane + 6] = act_force(*Mp, lane + 6, B.ctrl[(size_t)env * NU + lane]);
   dmw::sync();
   DebugOut dbg{out};
   { const LaneTopo lt = lane_topo(lane); stage_tables(s, lane); dmw::sync(); forward(*Mp, s, lane, lt, &dbg); }

@@ -1,75 +1,12 @@
 // env_step.h — per-environment drivers built on env_kernel.h: the RK4 step (mj_step), the DPEnv epilogue
 // (obs / reward / done, src/dp_env_v3.py:115-132), set_state + forward, and the reset variants
 // (src/dp_env_v3.py:148-164).  One wavefront per environment; `lane` is the lane id, `env` the env index.
+// The rules of the step (action -> ctrl, frame cursors, reset, observation row) are step_rules.h's; here is their lane distribution.
 #pragma once
 
-#include "env_kernel.h"
+#include "step_rules.h"
 
 namespace dm {
-
-// device pointers to the batch's state (row-major [N, width] arrays) and its configuration
-template <class R>
-struct Batch {
-  R* qpos;      // [N,35]
-  R* qvel;      // [N,34]
-  R* qws;       // [N,34] qacc_warmstart
-  R* time;      // [N]
-  R* ctrl;      // [N,28] last raw ctrl
-  R* xipos;     // [N,14,3]
-  R* comz;      // [N]
-  int* frame_idx;   // [N] DPEnv.idx_curr
-  int* frame_init;  // [N] DPEnv.idx_init
-  int* ncon;        // [N]
-  int* nefc;        // [N]
-  int* cong;        // [N,MAXEFC,2]
-  R* aovf;          // [N, AOVF_COLS, 64] overflow columns of A for the register-tier kernel (nullptr if unused)
-  int* status;      // [N]
-  int* solver_iter; // [N]
-  int* episode;     // [N]
-  int* order;       // [N] dispatch order: workgroup w steps env order[w] (nullptr: identity) — costly envs first shortens the tail
-  // self-ordering per-step launches (dispatch_env / order_ticket below): every env stepped by launch t takes a ticket in the bucket of its cost
-  // key; launch t + 1 turns (bucket counts, bucket lists) into its dispatch order on the fly — no ordering kernel between two steps.
-  // All null: off.  The pointers are those of ONE launch (one pipelined part, one phase): the host rotates three phases per part.
-  const int* ord_in;       // [64] bucket counts the previous launch of this part left (nullptr: no order yet -> `order` / identity)
-  const int* ordl_in;      // its bucket lists: env of (bucket k, ticket p) at ordl_in[k * ord_stride + p]
-  int* ord_out;            // [64] bucket counters this launch's envs take their tickets from (zero when the launch starts)
-  int* ordl_out;           // this launch's bucket lists
-  int* ord_zero;           // [64] the counters the NEXT launch will count into: cleared by this launch's first workgroup
-  int ord_stride;
-  int* cycle;       // [N] completed motion cycles since the episode started (imitation reward: root advance of the reference)
-  R* kin;           // [N, KIN_DOUBLES] kinematics of the state an env was left in (see save_kin), valid where kin_ok[env] != 0
-  unsigned char* kin_ok;   // [N]
-  int* redo_list;          // [N] envs the four-envs-per-wave kernel could not step (a capacity of slot_kernel.h exceeded): re-stepped by the one-env kernel
-  int* redo_count;         // [DM_MAX_PIPELINE] one counter per pipelined sub-batch (its list starts at redo_list[first env of the sub-batch])
-  int* redo_why;           // [8] diagnostic tallies of the reasons (see slot_step.h)
-  const R* mocap_cfg;  // [F,35]
-  const R* mocap_vel;  // [F,34]
-  const R* imit_table; // [F,112] reference feature rows of the 5-term imitation reward (nullptr: not provided)
-  const R* imit_pdev;  // the same 32 parameters in device memory (the reward indexes them per lane)
-  R imit_params[32];   // joint weights [12], root weight, cycle shift x y, loop flag, end-effector bodies [4], offsets [4][3]
-  R mocap_dt;          // duration of a mocap frame (MocapDM.dt): dp_env_v1's update interval (reward mode 4)
-  int n_frames;
-  int n_envs;
-  int env_offset;      // global id of env 0 of this shard (multi-GPU: RNG streams do not depend on the sharding)
-  int reward_mode, autoreset, action_mode;
-  int diag;            // 1: k_step also stores the per-step diagnostics (xipos, contact geom list); 0: state, obs and the row counts only
-  unsigned long long seed;
-};
-
-// the same batch for code behind a real call (slot_step.h): there the struct arrives through a generic pointer and so would its members
-template <class R>
-DM_DEV Batch<R> global_members(Batch<R> b) {
-  using dmw::in_global;          // (the members are wave-uniform: loaded through a uniform pointer)
-  b.qpos = in_global(b.qpos); b.qvel = in_global(b.qvel); b.qws = in_global(b.qws); b.time = in_global(b.time); b.ctrl = in_global(b.ctrl);
-  b.xipos = in_global(b.xipos); b.comz = in_global(b.comz); b.frame_idx = in_global(b.frame_idx); b.frame_init = in_global(b.frame_init);
-  b.ncon = in_global(b.ncon); b.nefc = in_global(b.nefc); b.cong = in_global(b.cong); b.aovf = in_global(b.aovf); b.status = in_global(b.status);
-  b.solver_iter = in_global(b.solver_iter); b.episode = in_global(b.episode); b.order = in_global(b.order); b.cycle = in_global(b.cycle);
-  b.kin = in_global(b.kin); b.kin_ok = in_global(b.kin_ok); b.redo_list = in_global(b.redo_list); b.redo_count = in_global(b.redo_count);
-  b.redo_why = in_global(b.redo_why); b.mocap_cfg = in_global(b.mocap_cfg); b.mocap_vel = in_global(b.mocap_vel);
-  b.imit_table = in_global(b.imit_table); b.imit_pdev = in_global(b.imit_pdev);
-  // (the ord_* members stay as they are: code behind a call runs inside horizon launches, which take no tickets — the members are null there)
-  return b;
-}
 
 // ---- self-ordering per-step launches ---------------------------------------------------------------------------------------------
 // Dispatch order of a per-step launch: environments with more constraint rows (a good proxy for their step time: 0.32 .. 0.72 M shader
@@ -123,19 +60,6 @@ DM_DEV void dispatch_env(const Batch<R>& B, int first, int count, int r0, int la
     } else if (B.order) e = B.order[e];
     env_out[j] = e;
   }
-}
-
-// counter-based RNG: splitmix64 finaliser over (seed, global env, episode, k) -> U[0,1)
-DM_DEV unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-DM_DEV double rng_uniform(unsigned long long seed, int genv, int episode, int k) {
-  unsigned long long h = mix64(seed ^ mix64((unsigned long long)(unsigned)genv * 0x100000001B3ull + 0x1234567ull));
-  h = mix64(h ^ ((unsigned long long)(unsigned)episode << 32 | (unsigned)k));
-  return (double)(h >> 11) * (1.0 / 9007199254740992.0);
 }
 
 // [MJ mj_integratePos] s.qpos <- x0q (+) h * dv, with dv read from s.ua.f.tau (scratch).  Caller syncs before and after.
@@ -192,22 +116,6 @@ DM_DEV bool rk4_step(const DevModel<R>& M, Shared<R>& s, StepScratch<R>& x, int 
   return true;
 }
 
-// The mocap frame env `env` is at as the env step starts: what the action front ends of modes 1, 2 and 4 track.  Reward modes 0, 1 and 3 keep
-// the frame itself in frame_idx.  Modes 2 and 4 keep the reference's two cursors (set_frame below): frame_idx counts steps without bound and the
-// frame is looked up through frame_init, exactly as their reward epilogues do — mode 4 with the v1 epilogue's update interval `upd`.  Always a row
-// of the mocap tables while frame_idx and frame_init are not negative.  Called inside the action-mode branches only: mode 0 pays nothing for it.
-template <class R>
-DM_DEV int step_start_frame(const DevModel<R>& M, const Batch<R>& B, int env, int n_substeps) {
-  const int idx = B.frame_idx[env];
-  if (B.reward_mode == REW_V2_POSE) return (idx + B.frame_init[env]) % B.n_frames;
-  if (B.reward_mode == REW_V1_QUAT) {
-    int upd = (int)floor(B.mocap_dt / (M.timestep * n_substeps));
-    if (upd < 1) upd = 1;
-    return (idx / upd + B.frame_init[env]) % B.n_frames;
-  }
-  return idx;
-}
-
 // load one env's row from HBM (coalesced: lane k reads element k) and turn the action into actuator forces
 template <class R>
 DM_DEV void load_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int env, int lane, const double* action, int n_substeps = 1) {
@@ -216,18 +124,10 @@ DM_DEV void load_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int 
   if (lane == 0) { s.status = 0; s.nefc = 0; s.ncon = 0; s.solver_iter = 0; s.aovf = B.aovf ? B.aovf + (size_t)env * AOVF_COLS * 64 : (R*)0; }
   dmw::sync();
   if (action && lane < NU) {
-    R a = (R)action[(size_t)env * NU + lane];   // (the C ABI's buffers are float64 whatever the arithmetic type R)
-    if (B.action_mode == 1) {  // P-control towards the current mocap frame (src/env_torque_test.py:14-20)
-      const int idx = step_start_frame(M, B, env, n_substeps);
-      a += R(0.8) * (B.mocap_cfg[(size_t)idx * NQ + 7 + lane] - s.qpos[7 + lane]);
-    } else if (B.action_mode == 2) {  // PD torque kp*dq + kd*dv written to ctrl (src/mujoco/setting_states.py:207-226)
-      const int idx = step_start_frame(M, B, env, n_substeps);
-      a += M.kp[lane + 6] * (B.mocap_cfg[(size_t)idx * NQ + 7 + lane] - s.qpos[7 + lane]) +
-           M.kd[lane + 6] * (B.mocap_vel[(size_t)idx * NV + 6 + lane] - s.qvel[6 + lane]);
-    }
+    // (the C ABI's buffers are float64 whatever the arithmetic type R)
+    const R a = ctrl_of_action(M, B, env, lane, (R)action[(size_t)env * NU + lane], s.qpos[7 + lane], s.qvel[6 + lane], n_substeps);
     B.ctrl[(size_t)env * NU + lane] = a;  // data.ctrl keeps the unclamped value
-    const int d = lane + 6;
-    s.act[d] = M.gear[d] * clampr(a, M.ctrl_lo[d], M.ctrl_hi[d]);
+    s.act[lane + 6] = act_force(M, lane + 6, a);
   }
   dmw::sync_mem();
 }
@@ -262,46 +162,21 @@ DM_DEV void store_state(const Batch<R>& B, Shared<R>& s, int env, int lane) {
   if (lane < NV) { B.qvel[(size_t)env * NV + lane] = s.qvel[lane]; B.qws[(size_t)env * NV + lane] = s.qws[lane]; }
 }
 
-// DPEnv.reference_state_init for one env: `idx` is the drawn mocap frame.  dp_env_v3 (src/dp_env_v3.py:67-71) starts its frame
-// cursor AT the drawn frame; dp_env_v2 (src/dp_env_v2.py:68-70) keeps the draw in idx_init and counts steps from 0 in idx_curr
-// (its target frame is (idx_curr + idx_init) % F, :128-129); dp_env_v1 does the same (src/dp_env_v1.py:58-60,94-96).
-template <class R>
-DM_DEV void set_frame(const Batch<R>& B, int env, int idx) {
-  B.frame_init[env] = idx;
-  B.frame_idx[env] = (B.reward_mode == REW_V2_POSE || B.reward_mode == REW_V1_QUAT) ? 0 : idx;
-  B.cycle[env] = 0;
-}
-
-// reset variants (src/dp_env_v3.py:67-71,148-164).  mode 0: RSI, 1: noisy init pose, 2: qpos0 / zero velocity.
-// `hard` = sim.reset() semantics: time = 0, qacc_warmstart = 0.  Writes s.qpos / s.qvel (/ s.qws) and frame indices.
-// Modes 0 and 1 with `hard` are the two episode starts of the reference's trainer: env.reset() = sim.reset() + reset_model()
-// (RSI: draws the frame, copies the mocap state), optionally followed by reset_model_init() which overrides the STATE only
-// (src/trpo.py:78-79) — so mode 1 draws the frame as well; the frame-indexed rewards then start from it.
+// the reset variants (step_rules.h): writes s.qpos / s.qvel (/ s.qws), the clock, the episode counter and the frame cursors
 template <class R>
 DM_DEV void reset_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int env, int lane, int mode, int hard) {
   const int ep = B.episode[env];
   const int genv = B.env_offset + env;
-  int idx = (int)(rng_uniform(B.seed, genv, ep, 0) * (double)B.n_frames);
-  if (idx >= B.n_frames) idx = B.n_frames - 1;
-  if (mode == 0) {
-    if (lane < NQ) s.qpos[lane] = B.mocap_cfg[(size_t)idx * NQ + lane];
-    if (lane < NV) s.qvel[lane] = B.mocap_vel[(size_t)idx * NV + lane];
-  } else if (mode == 1) {
-    if (lane < NQ) s.qpos[lane] = M.qpos0[lane] + (R)((rng_uniform(B.seed, genv, ep, 1 + lane) * 2.0 - 1.0) * 0.01);
-    if (lane < NV) s.qvel[lane] = (R)((rng_uniform(B.seed, genv, ep, 64 + lane) * 2.0 - 1.0) * 0.01);
-  } else {
-    if (lane < NQ) s.qpos[lane] = M.qpos0[lane];
-    if (lane < NV) s.qvel[lane] = 0;
+  const int idx = reset_draw(B, env, ep);
+  if (lane < NQ) {
+    R q, v = 0;
+    reset_element(M, B, mode, idx, genv, ep, lane, q, v);
+    s.qpos[lane] = q;
+    if (lane < NV) s.qvel[lane] = v;
   }
-  if (hard) {
-    if (lane < NV) s.qws[lane] = 0;
-    if (lane == 0) B.time[env] = 0;
-  }
+  if (hard && lane < NV) s.qws[lane] = 0;
   dmw::sync_mem();
-  if (lane == 0) {
-    B.episode[env] = ep + 1;
-    if (mode == 0 || (mode == 1 && hard)) set_frame(B, env, idx); else B.cycle[env] = 0;
-  }
+  if (lane == 0) reset_commit(B, env, ep, mode, hard, idx);
 }
 
 // ---- 5-term imitation reward (code.md:1017-1143; feature layout: deepmimic_mujoco_amd/imitation.py) -----------------------
@@ -509,10 +384,9 @@ DM_DEV void spd_control(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, i
   dmw::sync();
   const R a = lane_solve_L(s, lane, x);
   if (hinge) {
-    const R g = M.gear[lane];
-    const R c = (p + d - h * kd * a) / g;
+    const R c = spd_ctrl(M, lane, p + d, kd, a, h);
     B.ctrl[(size_t)env * NU + (lane - 6)] = c;   // data.ctrl keeps the unclamped value (the last substep's: DM_F_CTRL, the control cost of reward modes 2 and 4)
-    s.act[lane] = g * clampr(c, M.ctrl_lo[lane], M.ctrl_hi[lane]);
+    s.act[lane] = act_force(M, lane, c);
   }
   dmw::sync_mem();
 }
@@ -537,15 +411,7 @@ DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
   R qbar = 0, vbar = 0;                  // SPD: the target of dof `lane` (the mocap frame the env is at as the env step starts: step_start_frame)
   if constexpr (SPD) {
     load_env(M, B, s, env, lane, (const double*)0);
-    if (lane >= 6 && lane < NV) {
-      const int u = lane - 6;
-      if (action) qbar = (R)action[(size_t)env * NU + u];
-      if (B.action_mode == 4) {
-        const int idx = step_start_frame(M, B, env, n_substeps);
-        qbar += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
-        vbar = B.mocap_vel[(size_t)idx * NV + 6 + u];
-      }
-    }
+    if (lane >= 6 && lane < NV) spd_target(M, B, env, lane - 6, action, n_substeps, qbar, vbar);
   } else
   load_env(M, B, s, env, lane, action, n_substeps);
   if (kin0) { place_kin(s, kreg, lane); dmw::sync(); }
@@ -555,60 +421,53 @@ DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
   }
   bool kin_saved = false;
   const R z = com_z(M, s);
-  bool dn = (z < R(0.7)) || (z > R(2.0));
+  bool dn = com_out_of_band(z);
   store_derived(B, M, s, env, lane, B.diag != 0);   // sim.data.* as they stand after sim.step(): 4th-stage quantities
   // reward
   R rew = 1;
   if (B.reward_mode == REW_V3_CONFIG) {          // src/dp_env_v3.py:89-104
-    const int idx = B.frame_idx[env];
+    const FrameStep f = frame_step(REW_V3_CONFIG, M, B, n_substeps, B.frame_idx[env], 0, 0);
     R err = 0;
-    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)idx * NQ + i]);
+    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
     rew = exp_once(-err);
     dmw::sync_mem();
-    if (lane == 0) B.frame_idx[env] = (idx + 1) % B.n_frames;
+    if (lane == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_V2_POSE) {     // src/dp_env_v2.py:116-183
-    const int idx = B.frame_idx[env] + 1;
-    const int im = (idx + B.frame_init[env]) % B.n_frames;
-    R err = 0, acs = 0;
-    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)im * NQ + i]);
-    for (int u = 0; u < NU; u++) { const R c = B.ctrl[(size_t)env * NU + u]; acs += c * c; }
+    const FrameStep f = frame_step(REW_V2_POSE, M, B, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
+    R err = 0;
+    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
+    const R acs = control_cost(B, env);
     rew = exp_once(R(-2) * err) - R(0.1) * acs;
     dmw::sync_mem();
-    if (lane == 0) B.frame_idx[env] = idx;
+    if (lane == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_IMITATION) {   // code.md:1017-1143: the state after the step against frame idx + 1
-    int k = dmw::uniform(B.frame_idx[env]) + 1, cyc = dmw::uniform(B.cycle[env]);
-    bool ended = false;
-    if (k >= B.n_frames) { if (B.imit_params[15] != R(0)) { k = 0; cyc += 1; } else { k = B.n_frames - 1; ended = true; } }
-    rew = imitation_reward(M, B, s, lane, lt, B.imit_table + (size_t)k * IMIT_FEAT, cyc * B.imit_params[13], cyc * B.imit_params[14]);
-    dn = dn || ended;                            // a "Loop: none" clip holds its last frame and ends the episode there
+    const FrameStep f = frame_step(REW_IMITATION, M, B, n_substeps, dmw::uniform(B.frame_idx[env]), 0, dmw::uniform(B.cycle[env]));
+    rew = imitation_reward(M, B, s, lane, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, f.cycle * B.imit_params[13], f.cycle * B.imit_params[14]);
+    dn = dn || f.ended;                          // a "Loop: none" clip holds its last frame and ends the episode there
     dmw::sync_mem();
-    if (lane == 0) { B.frame_idx[env] = k; B.cycle[env] = cyc; }
+    if (lane == 0) { B.frame_idx[env] = f.store; B.cycle[env] = f.cycle; }
     if (B.kin && !(dn && B.autoreset)) { save_kin(s, B.kin + (size_t)env * KIN_DOUBLES, lane); kin_saved = true; }   // (after the fence: the stores drain behind the rest of the epilogue)
   }
   else if (B.reward_mode == REW_V1_QUAT) {     // src/dp_env_v1.py:82-158: cursor counts steps, reward every `upd` steps, minus the control cost
-    const int idx = dmw::uniform(B.frame_idx[env]) + 1;
-    int upd = (int)floor(B.mocap_dt / (M.timestep * n_substeps));
-    if (upd < 1) upd = 1;
+    const FrameStep f = frame_step(REW_V1_QUAT, M, B, n_substeps, dmw::uniform(B.frame_idx[env]), dmw::uniform(B.frame_init[env]), 0);
     R robs = 0;
-    if (idx % upd == 0) {
-      const int k = (idx / upd + dmw::uniform(B.frame_init[env])) % B.n_frames, kv = k + 1 < B.n_frames ? k + 1 : B.n_frames - 1;
-      robs = v1_reward(M, B, s, lane, lt, B.imit_table + (size_t)k * IMIT_FEAT, B.imit_table + (size_t)kv * IMIT_FEAT);
+    if (f.take) {
+      robs = v1_reward(M, B, s, lane, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, B.imit_table + (size_t)f.row_v * IMIT_FEAT);
       if (B.kin) { save_kin(s, B.kin + (size_t)env * KIN_DOUBLES, lane); kin_saved = true; }
     }
-    R acs = 0;
-    for (int u = 0; u < NU; u++) { const R c = B.ctrl[(size_t)env * NU + u]; acs += c * c; }
+    const R acs = control_cost(B, env);
     rew = robs - R(0.1) * acs;
     dmw::sync_mem();
-    if (lane == 0) B.frame_idx[env] = idx;
+    if (lane == 0) B.frame_idx[env] = f.store;
   }
   if (lane == 0) { B.time[env] += M.timestep * n_substeps; reward[env] = rew; done[env] = dn ? 1 : 0; if (B.kin) B.kin_ok[env] = (kin_saved && !(dn && B.autoreset)) ? 1 : 0; }
   if (dn && B.autoreset) {                        // DummyVecEnv convention: obs of the fresh episode is returned
     dmw::sync_mem();
     reset_env(M, B, s, env, lane, B.autoreset == 1 ? 0 : 1, 1);
   }
-  // obs = qpos[7:] (+) qvel[6:]   (src/dp_env_v3.py:62-65), one coalesced 56-wide store
-  if (lane < 28) obs[(size_t)env * NOBS + lane] = s.qpos[7 + lane];
-  else if (lane < NOBS) obs[(size_t)env * NOBS + lane] = s.qvel[6 + (lane - 28)];
+  // one coalesced 56-wide store (two branches, as the kernels have always had them: one store of a select moves the one-env kernels' spilled scalars)
+  if (lane < 28) obs[(size_t)env * NOBS + lane] = obs_element(s.qpos, s.qvel, lane);
+  else if (lane < NOBS) obs[(size_t)env * NOBS + lane] = obs_element(s.qpos, s.qvel, lane);
   store_state(B, s, env, lane);
   if (lane == 0) order_ticket(B, env, s.nefc, s.solver_iter);
   if (PROF && lane == 0) {

@@ -98,24 +98,16 @@ DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>
     for (int c = 0; c < HINGE_PASSES; c++) {
       const int u = sl + SW * c;
       if (u < NU) {
-        R a = (R)action[(size_t)env * NU + u];
-        if (B.action_mode == 1) {
-          const int idx = step_start_frame(M, B, env, n_substeps);
-          a += R(0.8) * (B.mocap_cfg[(size_t)idx * NQ + 7 + u] - s.qpos[7 + u]);
-        } else if (B.action_mode == 2) {
-          const int idx = step_start_frame(M, B, env, n_substeps);
-          a += M.kp[u + 6] * (B.mocap_cfg[(size_t)idx * NQ + 7 + u] - s.qpos[7 + u]) + M.kd[u + 6] * (B.mocap_vel[(size_t)idx * NV + 6 + u] - s.qvel[6 + u]);
-        }
+        const R a = ctrl_of_action(M, B, env, u, (R)action[(size_t)env * NU + u], s.qpos[7 + u], s.qvel[6 + u], n_substeps);
         if (live) B.ctrl[(size_t)env * NU + u] = a;
-        const int d = u + 6;
-        s.act[d] = M.gear[d] * clampr(a, M.ctrl_lo[d], M.ctrl_hi[d]);
+        s.act[u + 6] = act_force(M, u + 6, a);
       }
     }
   }
   dmw::sync_mem();
 }
 
-// ---- stable PD control of the slot's environment (action modes 3 and 4; env_step.h spd_control has the rule).  A pass of its own over the
+// ---- stable PD control of the slot's environment (action modes 3 and 4; env_step.h spd_control has the rule, step_rules.h its per-dof ends).  A pass of its own over the
 // stages at the start of every substep: kinematics, bias without actuation (-c in s.tau), the mass-matrix stage with h kd on the diagonal,
 // one register solve (every lane of the slot carries the vector, as in slot_smooth_solve).  The factor overwrites the inertias here (r2), so
 // the substep's first RK4 evaluation forms its own kinematics again.  qbar / vbar: dof-distributed targets (dofs 6..33).
@@ -161,10 +153,9 @@ DM_DEV void slot_spd_control(const DevModel<R>& M, const Batch<R>& B, SlotShared
   for (int c = 0; c < DOF_PASSES; c++) {
     const int d = sl + SW * c;
     if (d >= 6 && d < NV) {
-      const R g = M.gear[d];
-      const R ct = (pd[c] - h * kd[c] * s.qd.o.qacc[d]) / g;
+      const R ct = spd_ctrl(M, d, pd[c], kd[c], s.qd.o.qacc[d], h);
       if (live) B.ctrl[(size_t)env * NU + (d - 6)] = ct;
-      s.act[d] = g * clampr(ct, M.ctrl_lo[d], M.ctrl_hi[d]);
+      s.act[d] = act_force(M, d, ct);
     }
   }
   dmw::sync_mem();
@@ -181,36 +172,27 @@ DM_DEV void slot_store_state(const Batch<R>& B, SlotShared<R>& s, int env, int s
   }
 }
 
-// reset variants of env_step.h's reset_env for the slots whose `doit` is set (collective: every lane calls it; barriers are unconditional)
+// the reset variants (step_rules.h) for the slots whose `doit` is set (collective: every lane calls it; barriers are unconditional)
 template <class R>
 DM_DEV void slot_reset_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, int env, int sl, bool doit, int mode, int hard) {
   const int ep = B.episode[env];
   const int genv = B.env_offset + env;
-  int idx = (int)(rng_uniform(B.seed, genv, ep, 0) * (double)B.n_frames);
-  if (idx >= B.n_frames) idx = B.n_frames - 1;
+  const int idx = reset_draw(B, env, ep);
   if (doit) {
 #pragma unroll
     for (int c = 0; c < Q_PASSES; c++) {
       const int i = sl + SW * c;
-      if (mode == 0) {
-        if (i < NQ) s.qpos[i] = B.mocap_cfg[(size_t)idx * NQ + i];
-        if (i < NV) s.qvel[i] = B.mocap_vel[(size_t)idx * NV + i];
-      } else if (mode == 1) {
-        if (i < NQ) s.qpos[i] = M.qpos0[i] + (R)((rng_uniform(B.seed, genv, ep, 1 + i) * 2.0 - 1.0) * 0.01);
-        if (i < NV) s.qvel[i] = (R)((rng_uniform(B.seed, genv, ep, 64 + i) * 2.0 - 1.0) * 0.01);
-      } else {
-        if (i < NQ) s.qpos[i] = M.qpos0[i];
-        if (i < NV) s.qvel[i] = 0;
+      if (i < NQ) {
+        R q, v = 0;
+        reset_element(M, B, mode, idx, genv, ep, i, q, v);
+        s.qpos[i] = q;
+        if (i < NV) s.qvel[i] = v;
       }
       if (hard && i < NV) s.qws[i] = 0;
     }
-    if (hard && sl == 0) B.time[env] = 0;
   }
   dmw::sync_mem();
-  if (doit && sl == 0) {
-    B.episode[env] = ep + 1;
-    if (mode == 0 || (mode == 1 && hard)) set_frame(B, env, idx); else B.cycle[env] = 0;
-  }
+  if (doit && sl == 0) reset_commit(B, env, ep, mode, hard, idx);
 }
 
 // ---- 5-term imitation reward (env_step.h imitation_reward; code.md:1017-1143) for the slot's environment: one extra kinematics pass on
@@ -322,15 +304,7 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
     for (int c = 0; c < DOF_PASSES; c++) {
       const int d = sl + SW * c;
       qbar.r[c] = 0; vbar.r[c] = 0;
-      if (d >= 6 && d < NV) {
-        const int u = d - 6;
-        if (action) qbar.r[c] = (R)action[(size_t)env * NU + u];
-        if (B.action_mode == 4) {
-          const int idx = step_start_frame(M, B, env, n_substeps);
-          qbar.r[c] += B.mocap_cfg[(size_t)idx * NQ + 7 + u];
-          vbar.r[c] = B.mocap_vel[(size_t)idx * NV + 6 + u];
-        }
-      }
+      if (d >= 6 && d < NV) spd_target(M, B, env, d - 6, action, n_substeps, qbar.r[c], vbar.r[c]);
     }
   } else
   slot_load_env(M, B, s, env, sl, live, action, n_substeps);
@@ -353,7 +327,7 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   // COM height of the 4th-stage body positions (src/dp_env_v3.py:134-139): mass-weighted sum over the body lanes
   const R mz = sl < NB - 1 ? M.body_mass[sl + 1] * xip[2] : R(0);
   const R z = dmw::sum16(mz) / M.total_mass;
-  bool dn = (z < R(0.7)) || (z > R(2.0));
+  bool dn = com_out_of_band(z);
   if (live) {
     if (B.diag != 0) {
       if (sl < NB - 1) for (int k = 0; k < 3; k++) B.xipos[(size_t)env * NB * 3 + 3 * (sl + 1) + k] = xip[k];
@@ -370,42 +344,35 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   }
   R rew = 1;
   if (B.reward_mode == REW_V3_CONFIG) {
-    const int idx = B.frame_idx[env];
+    const FrameStep f = frame_step(REW_V3_CONFIG, M, B, n_substeps, B.frame_idx[env], 0, 0);
     R err = 0;
-    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)idx * NQ + i]);
+    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
     rew = exp_once(-err);
     dmw::sync_mem();
-    if (live && sl == 0) B.frame_idx[env] = (idx + 1) % B.n_frames;
+    if (live && sl == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_V2_POSE) {
-    const int idx = B.frame_idx[env] + 1;
-    const int im = (idx + B.frame_init[env]) % B.n_frames;
-    R err = 0, acs = 0;
-    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)im * NQ + i]);
-    for (int u = 0; u < NU; u++) { const R c = B.ctrl[(size_t)env * NU + u]; acs += c * c; }
+    const FrameStep f = frame_step(REW_V2_POSE, M, B, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
+    R err = 0;
+    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
+    const R acs = control_cost(B, env);
     rew = exp_once(R(-2) * err) - R(0.1) * acs;
     dmw::sync_mem();
-    if (live && sl == 0) B.frame_idx[env] = idx;
+    if (live && sl == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_IMITATION) {   // code.md:1017-1143: the state after the step against frame idx + 1 (env_step.h)
-    int k = B.frame_idx[env] + 1, cyc = B.cycle[env];
-    bool ended = false;
-    if (k >= B.n_frames) { if (B.imit_params[15] != R(0)) { k = 0; cyc += 1; } else { k = B.n_frames - 1; ended = true; } }
-    rew = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)k * IMIT_FEAT, cyc * B.imit_params[13], cyc * B.imit_params[14]);
-    dn = dn || ended;
+    const FrameStep f = frame_step(REW_IMITATION, M, B, n_substeps, B.frame_idx[env], 0, B.cycle[env]);
+    rew = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, f.cycle * B.imit_params[13], f.cycle * B.imit_params[14]);
+    dn = dn || f.ended;
     dmw::sync_mem();
-    if (live && sl == 0) { B.frame_idx[env] = k; B.cycle[env] = cyc; }
+    if (live && sl == 0) { B.frame_idx[env] = f.store; B.cycle[env] = f.cycle; }
   } else if (B.reward_mode == REW_V1_QUAT) {     // src/dp_env_v1.py:82-158 (env_step.h): the cursor counts steps, the pose reward every `upd` steps, minus the control cost
-    const int idx = B.frame_idx[env] + 1;
-    int upd = (int)floor(B.mocap_dt / (M.timestep * n_substeps));
-    if (upd < 1) upd = 1;
+    const FrameStep f = frame_step(REW_V1_QUAT, M, B, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
     // (the four environments of a wave sit at different cursors: the pass is collective, so it runs every step on every slot — its kinematics are the
     //  next step's first evaluation's anyway (kin_carry) — and a slot takes its value on the steps its own cursor says so)
-    const int k = (idx / upd + B.frame_init[env]) % B.n_frames, kv = k + 1 < B.n_frames ? k + 1 : B.n_frames - 1;
-    const R robs = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)k * IMIT_FEAT, R(0), R(0), B.imit_table + (size_t)kv * IMIT_FEAT);
-    R acs = 0;
-    for (int u = 0; u < NU; u++) { const R c = B.ctrl[(size_t)env * NU + u]; acs += c * c; }
-    rew = (idx % upd == 0 ? robs : R(0)) - R(0.1) * acs;
+    const R robs = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, R(0), R(0), B.imit_table + (size_t)f.row_v * IMIT_FEAT);
+    const R acs = control_cost(B, env);
+    rew = (f.take ? robs : R(0)) - R(0.1) * acs;
     dmw::sync_mem();
-    if (live && sl == 0) B.frame_idx[env] = idx;
+    if (live && sl == 0) B.frame_idx[env] = f.store;
   }
   if (live && sl == 0) { B.time[env] += M.timestep * n_substeps; reward[env] = rew; done[env] = dn ? 1 : 0; if (B.kin) B.kin_ok[env] = 0; }
   if (B.autoreset) {                              // DummyVecEnv convention: obs of the fresh episode is returned
@@ -419,8 +386,7 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
 #pragma unroll
     for (int c = 0; c < (NOBS + SW - 1) / SW; c++) {
       const int o = sl + SW * c;
-      if (o < 28) obs[(size_t)env * NOBS + o] = s.qpos[7 + o];
-      else if (o < NOBS) obs[(size_t)env * NOBS + o] = s.qvel[6 + (o - 28)];
+      if (o < NOBS) obs[(size_t)env * NOBS + o] = obs_element(s.qpos, s.qvel, o);
     }
   }
   slot_store_state(B, s, env, sl, live);

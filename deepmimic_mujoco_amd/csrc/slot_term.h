@@ -22,12 +22,10 @@ template <class R>
 DM_DEV void slot_terminate(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, const TermArgs& T, int t, int env, int sl, int lane, bool live,
                            bool lds_lost, double* obs, unsigned char* done) {
   dmw::sync_mem();                                             // the step's rows and state, written by other lanes of this wave
-  const bool stepdone = done[env] != 0;
-  const bool test = live && !stepdone;
-  const int steps = T.steps[env] + 1;
-  const bool limit = T.max_steps > 0 && steps >= T.max_steps;
+  const TermVerdict v = term_verdict(done[env] != 0, T.steps[env], T.max_steps);
+  const bool test = live && !v.stepdone;
   dmw::sync();                                                 // every lane has read the flag and the counter that lane 0 of the slot writes below
-  if (live && stepdone && sl == 0) { T.reason[env] = DM_DONE_STEP; T.steps[env] = 0; }
+  if (live && v.stepdone && sl == 0) { T.reason[env] = v.reason(false); T.steps[env] = v.steps_kept(false); }
   bool fall = false;
   if (T.fall_bodies) {                                         // (wave-uniform)
     const bool own = !lds_lost && s.kin_ok() != R(0);
@@ -45,15 +43,15 @@ DM_DEV void slot_terminate(const DevModel<R>& M, const Batch<R>& B, SlotShared<R
     if (sl >= 1 && sl < NG) touch = dmfc::geom_touches_floor(sl, M.geom_body, M.geom_type, M.geom_pos, M.geom_mat, M.geom_size, M.geom_margin, s.xpos, s.xmat);
     fall = (dmw::row_ballot(touch, lane) & dmfc::geoms_of_bodies(T.fall_bodies, M.geom_body, NG)) != 0u;
   }
-  const bool end = test && (fall || limit);
-  if (test && !end && sl == 0) { T.steps[env] = steps; T.reason[env] = 0; }
+  const bool end = live && v.ends(fall);
+  if (test && !end && sl == 0) { T.steps[env] = v.steps_kept(fall); T.reason[env] = v.reason(fall); }
   if (T.log_cap > 0) {                                         // ended by the time limit alone: a truncation — log the state the step left
     const bool rec = end && !fall;
     int k = 0;
     if (rec && sl == 0) k = dmw::global_counter_next(T.log_count);
     k = dmw::row_bcast_i<0>(k);
     if (rec && k < T.log_cap) {
-      if (sl < 4) T.log_index[(size_t)k * 4 + sl] = sl == 0 ? env : (sl == 1 ? T.tick + t : (sl == 2 ? B.frame_idx[env] : B.frame_init[env]));
+      if (sl < 4) T.log_index[(size_t)k * 4 + sl] = trunc_index_value(sl, env, T.tick + t, B);
 #pragma unroll
       for (int c = 0; c < Q_PASSES; c++) {
         const int i = sl + SW * c;
@@ -62,7 +60,7 @@ DM_DEV void slot_terminate(const DevModel<R>& M, const Batch<R>& B, SlotShared<R
       }
     }
   }
-  if (end && sl == 0) { done[env] = 1; T.reason[env] = (fall ? DM_DONE_FALL : 0) | (limit ? DM_DONE_TIME_LIMIT : 0); T.steps[env] = 0; }
+  if (end && sl == 0) { done[env] = 1; T.reason[env] = v.reason(fall); T.steps[env] = v.steps_kept(fall); }
   if (B.autoreset) {                                           // the tail of the step's epilogue: the fresh episode's state and observation row
     dmw::sync_mem();
     slot_reset_env(M, B, s, env, sl, end, B.autoreset == 1 ? 0 : 1, 1);
@@ -70,8 +68,7 @@ DM_DEV void slot_terminate(const DevModel<R>& M, const Batch<R>& B, SlotShared<R
 #pragma unroll
       for (int c = 0; c < (NOBS + SW - 1) / SW; c++) {
         const int o = sl + SW * c;
-        if (o < 28) obs[(size_t)env * NOBS + o] = s.qpos[7 + o];
-        else if (o < NOBS) obs[(size_t)env * NOBS + o] = s.qvel[6 + (o - 28)];
+        if (o < NOBS) obs[(size_t)env * NOBS + o] = obs_element(s.qpos, s.qvel, o);
       }
       if (sl == 0) { if (B.kin) B.kin_ok[env] = 0; s.kin_ok() = R(0); }   // parked and carried kinematics belong to the old state
     }

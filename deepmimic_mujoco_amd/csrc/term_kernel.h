@@ -60,19 +60,19 @@ __global__ __launch_bounds__(64) void k_terminate(const DevModel<Real>* __restri
   // the step kernel ended the episode itself (COM band, clip end): the state may already be a fresh episode's, and a reference pose of a
   // floor clip legitimately touches the floor — nothing is tested
   if (dmw::uniform((int)done[env]) != 0) {
-    if (lane == 0) { T.reason[env] = DM_DONE_STEP; T.steps[env] = 0; }
+    const TermVerdict v = term_verdict(true, 0, T.max_steps);
+    if (lane == 0) { T.reason[env] = v.reason(false); T.steps[env] = v.steps_kept(false); }
     return;
   }
-  const int steps = dmw::uniform(T.steps[env]) + 1;
-  const bool limit = T.max_steps > 0 && steps >= T.max_steps;
+  const TermVerdict v = term_verdict(false, dmw::uniform(T.steps[env]), T.max_steps);
   load_env(M, B, s, env, lane, (const double*)0);         // ends with a hand-off
   bool fall = false;
   if (T.fall_bodies) {
     stage_kinematics(M, s, lane, lane_topo(lane));
     fall = (floor_touch_mask(M, s, lane) & dmfc::geoms_of_bodies(T.fall_bodies, M.geom_body, NG)) != 0u;
   }
-  if (!fall && !limit) {
-    if (lane == 0) { T.steps[env] = steps; T.reason[env] = 0; }
+  if (!v.ends(fall)) {
+    if (lane == 0) { T.steps[env] = v.steps_kept(fall); T.reason[env] = v.reason(fall); }
     return;
   }
   if (T.log_cap > 0 && !fall) {                           // ended by the time limit alone: a truncation, not a failure — log the state the step left
@@ -80,17 +80,16 @@ __global__ __launch_bounds__(64) void k_terminate(const DevModel<Real>* __restri
     if (lane == 0) slot = atomicAdd(T.log_count, 1);      // (device scope: pipelined parts on other streams share the counter)
     slot = dmw::uniform(slot);
     if (slot < T.log_cap) {
-      if (lane < 4) T.log_index[(size_t)slot * 4 + lane] = lane == 0 ? env : (lane == 1 ? T.tick : (lane == 2 ? B.frame_idx[env] : B.frame_init[env]));
+      if (lane < 4) T.log_index[(size_t)slot * 4 + lane] = trunc_index_value(lane, env, T.tick, B);
       if (lane < NQ) T.log_qpos[(size_t)slot * NQ + lane] = (double)s.qpos[lane];
       if (lane < NV) T.log_qvel[(size_t)slot * NV + lane] = (double)s.qvel[lane];
     }
   }
-  if (lane == 0) { done[env] = 1; T.reason[env] = (fall ? DM_DONE_FALL : 0) | (limit ? DM_DONE_TIME_LIMIT : 0); T.steps[env] = 0; }
+  if (lane == 0) { done[env] = 1; T.reason[env] = v.reason(fall); T.steps[env] = v.steps_kept(fall); }
   if (B.autoreset) {                                      // the tail of env_step_impl's epilogue: the fresh episode's state and observation row
     dmw::sync_mem();
     reset_env(M, B, s, env, lane, B.autoreset == 1 ? 0 : 1, 1);
-    if (lane < 28) obs[(size_t)env * NOBS + lane] = s.qpos[7 + lane];
-    else if (lane < NOBS) obs[(size_t)env * NOBS + lane] = s.qvel[6 + (lane - 28)];
+    if (lane < NOBS) obs[(size_t)env * NOBS + lane] = obs_element(s.qpos, s.qvel, lane);
     store_state(B, s, env, lane);
     if (lane == 0 && B.kin) B.kin_ok[env] = 0;            // the parked kinematics belong to the old state
   }
