@@ -27,13 +27,17 @@ OPT_TRUNCATION_LOG = 11
 OPT_HORIZON_TERMINATION = 12
 # DM_OPT_ACTION_MODE values (include/dmenv.h): 3 and 4 make the action a PD target pose under a stable PD controller evaluated per substep
 ACTION_RAW, ACTION_P_CONTROL, ACTION_PD, ACTION_SPD_TARGET, ACTION_SPD_MOCAP = 0, 1, 2, 3, 4
+# multi-clip batches (dm_mocap_create_set; clips.ClipSet): 0 an env keeps its clip (F_CLIP), 1 every reset that sets the frame cursor draws the episode's clip first
+OPT_CLIP_MODE = 13
+CLIP_FIXED, CLIP_EPISODE = 0, 1
+MAX_CLIPS = 32
 MAX_PIPELINE = 8
 MAX_STEP_QUEUE = 256
 # per-environment capacities of the OPT_PACKED path (include/dmenv.h DM_PACKED_*)
 PACKED_MAXROWS, PACKED_MAXLIMROWS, PACKED_MAXCON, PACKED_MAXFRAME, PACKED_MAXCAND = 40, 16, 13, 8, 32      # (rows: inside a horizon launch)
 PACKED_MAXROWS_PER_STEP = 32
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_FRAME_IDX, F_FRAME_INIT, F_XIPOS, F_COM_Z, F_NCON, F_NEFC,
- F_CONTACT_GEOMS, F_STATUS, F_SOLVER_ITER, F_CTRL, F_EPISODE, F_CYCLE, F_EPISODE_STEPS, F_DONE_REASON) = range(1, 19)
+ F_CONTACT_GEOMS, F_STATUS, F_SOLVER_ITER, F_CTRL, F_EPISODE, F_CYCLE, F_EPISODE_STEPS, F_DONE_REASON, F_CLIP) = range(1, 20)
 
 # field -> (numpy dtype, per-env shape)
 FIELD_SPEC = {
@@ -42,7 +46,7 @@ FIELD_SPEC = {
     F_XIPOS: (np.float64, (NBODY, 3)), F_COM_Z: (np.float64, ()), F_NCON: (np.int32, ()), F_NEFC: (np.int32, ()),
     F_CONTACT_GEOMS: (np.int32, (MAXEFC, 2)), F_STATUS: (np.int32, ()), F_SOLVER_ITER: (np.int32, ()),
     F_CTRL: (np.float64, (NU,)), F_EPISODE: (np.int32, ()), F_CYCLE: (np.int32, ()),
-    F_EPISODE_STEPS: (np.int32, ()), F_DONE_REASON: (np.int32, ()),
+    F_EPISODE_STEPS: (np.int32, ()), F_DONE_REASON: (np.int32, ()), F_CLIP: (np.int32, ()),
 }
 
 _dp = C.POINTER(C.c_double)
@@ -116,7 +120,7 @@ def make_model_desc(cm):
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DMENV_LIB") or os.path.join(_HERE, "csrc", "libdmenv.so")   # DMENV_LIB: developer override (A/B builds)
-EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_destroy", "dm_batch_create",
+EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_create_set", "dm_mocap_destroy", "dm_batch_create",
            "dm_batch_destroy", "dm_batch_set_stream", "dm_batch_set_option", "dm_batch_set_state", "dm_batch_reset",
            "dm_batch_step", "dm_batch_get_obs", "dm_batch_get", "dm_batch_set", "dm_batch_debug_forward",
            "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_imitation_terms", "dm_batch_truncations", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
@@ -149,6 +153,7 @@ def load(dtype=64):
     L.dm_model_destroy.argtypes = [vp]; L.dm_model_destroy.restype = None
     L.dm_mocap_create.argtypes = [_dp, _dp, i32, C.c_double, C.POINTER(vp)]
     L.dm_mocap_set_imitation.argtypes = [vp, _dp, i32, _dp]
+    L.dm_mocap_create_set.argtypes = [C.POINTER(vp), i32, _dp, C.POINTER(vp)]
     L.dm_mocap_destroy.argtypes = [vp]; L.dm_mocap_destroy.restype = None
     L.dm_batch_create.argtypes = [vp, vp, i32, i32, C.c_uint32, C.POINTER(vp)]
     L.dm_batch_destroy.argtypes = [vp]; L.dm_batch_destroy.restype = None

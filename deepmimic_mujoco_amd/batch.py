@@ -63,8 +63,10 @@ def batch_option(batch, opt, default=0):
 
 
 class Batch(object):
-    def __init__(self, compiled_model, data_config, data_vel, n_envs, device=0, flags=0, mocap_dt=0.0, imitation=None, dtype=64):
-        """dtype: arithmetic / device-state type of the kernels, 64 (default: the parity path) or 32 (the float32 build of the same
+    def __init__(self, compiled_model, data_config, data_vel, n_envs, device=0, flags=0, mocap_dt=0.0, imitation=None, dtype=64, clips=None):
+        """clips: a clips.ClipSet — the batch is then MULTI-CLIP (dm_mocap_create_set: every env imitates one clip of the set, F_CLIP; OPT_CLIP_MODE);
+        data_config, data_vel, mocap_dt and imitation are the set's and must be None / left at their defaults.
+        dtype: arithmetic / device-state type of the kernels, 64 (default: the parity path) or 32 (the float32 build of the same
         source, libdmenv32.so: faster; per step ~4e-7 of the observation scale at the median and ~4e-6 at worst against a float64 evaluation
         of the same float32-rounded state, the error of any float32 evaluation: DESIGN.md section 5).  Buffers are float64 either way."""
         # the Python side's own state, all of it
@@ -84,6 +86,14 @@ class Batch(object):
         md, self._keep = A.make_model_desc(compiled_model)
         self._model = C.c_void_p(); self._mocap = C.c_void_p(); self._h = C.c_void_p()
         A.check(L.dm_model_create(C.byref(md), C.byref(self._model)), L)
+        self.clips = clips
+        if clips is not None:
+            if data_config is not None or data_vel is not None or imitation is not None:
+                raise ValueError("clips=ClipSet carries the mocap tables: data_config, data_vel and imitation must be None")
+            self.n_frames = int(clips.n_frames.sum())
+            self._mocap = self._create_clip_set(L, clips)
+            A.check(L.dm_batch_create(self._model, self._mocap, self.n, self.device, int(flags), C.byref(self._h)), L)
+            return
         cfg = np.ascontiguousarray(data_config, dtype=np.float64); vel = np.ascontiguousarray(data_vel, dtype=np.float64)
         if cfg.ndim != 2 or cfg.shape[1] != A.NQ or vel.shape != (cfg.shape[0], A.NV):
             raise ValueError("mocap tables must be [F,35] and [F,34]")
@@ -96,6 +106,28 @@ class Batch(object):
                 raise ValueError("imitation = (table [F,112], params [32])")
             A.check(L.dm_mocap_set_imitation(self._mocap, tab.ctypes.data_as(A._dp), 112, par.ctypes.data_as(A._dp)), L)
         A.check(L.dm_batch_create(self._model, self._mocap, self.n, self.device, int(flags), C.byref(self._h)), L)
+
+    @staticmethod
+    def _create_clip_set(L, clips):
+        """dm_mocap_create_set over one dm_mocap per clip of the ClipSet (destroyed again: the set holds its own copy) -> the set's handle"""
+        hs = []
+        try:
+            for k, m in enumerate(clips.mocaps):
+                cfg = np.ascontiguousarray(m.data_config, dtype=np.float64); vel = np.ascontiguousarray(m.data_vel, dtype=np.float64)
+                h = C.c_void_p()
+                A.check(L.dm_mocap_create(cfg.ctypes.data_as(A._dp), vel.ctypes.data_as(A._dp), cfg.shape[0], float(m.dt), C.byref(h)), L)
+                hs.append(h)
+                if clips.imitation is not None:
+                    tab = np.ascontiguousarray(clips.imitation[k][0], dtype=np.float64); par = np.ascontiguousarray(clips.imitation[k][1], dtype=np.float64)
+                    A.check(L.dm_mocap_set_imitation(h, tab.ctypes.data_as(A._dp), 112, par.ctypes.data_as(A._dp)), L)
+            arr = (C.c_void_p * len(hs))(*[h.value for h in hs])
+            w = np.ascontiguousarray(clips.weights, dtype=np.float64)
+            out = C.c_void_p()
+            A.check(L.dm_mocap_create_set(arr, len(hs), w.ctypes.data_as(A._dp), C.byref(out)), L)
+            return out
+        finally:
+            for h in hs:
+                L.dm_mocap_destroy(h)
 
     def close(self):
         L = getattr(self, "_L", None)

@@ -45,7 +45,19 @@ struct dm_batch {
   bool horizon_term = false;
   // the truncation log (DM_OPT_TRUNCATION_LOG, dm_batch_truncations): trunc_cap records, allocated when the option is set; trunc_tick = step calls since it was cleared
   int trunc_cap = 0, trunc_tick = 0; int *d_trunc_count = nullptr, *d_trunc_index = nullptr; double *d_trunc_qpos = nullptr, *d_trunc_qvel = nullptr;
+  // the clip set (dm_mocap_create_set; step_rules.h ClipArgs): n_clips > 1 makes the batch multi-clip — its launches are the clip kernels (kernels_clips.hip,
+  // kernels_packed_clips.hip).  d_clip is DM_F_CLIP (all 0 on a single-clip batch); clip_frames: the clips' lengths, for the host's range checks
+  int n_clips = 1, clip_mode = 0; int* d_clip = nullptr; dm::ClipRec<Real>* d_clip_rec = nullptr; std::vector<int> clip_frames;
 };
+inline bool multi_clip(const dm_batch* b) { return b->n_clips > 1; }
+inline dm::ClipArgs<Real> clip_args(const dm_batch* b) { return dm::ClipArgs<Real>{b->d_clip, b->d_clip_rec, b->n_clips, b->clip_mode}; }
+// the batch's DM_F_CLIP on the host (stream-ordered copy and a wait): the per-env range checks of a multi-clip batch
+inline int clip_ids_host(dm_batch* b, std::vector<int>& ids) {
+  ids.resize((size_t)b->n);
+  HIPCHK(hipMemcpyAsync(ids.data(), b->d_clip, (size_t)b->n * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return DM_OK;
+}
 // make the batch's stream wait for every sub-batch launch still in flight (no host wait)
 inline int pipe_join(dm_batch* b) {
   if (!b->pipe_pending) return DM_OK;

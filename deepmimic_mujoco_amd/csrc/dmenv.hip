@@ -215,7 +215,9 @@ __global__ __launch_bounds__(64) void k_debug_forward(const DevModel<Real>* __re
 thread_local std::string g_err;
 
 struct dm_model { DevModel<Real> h; };
-struct dm_mocap { std::vector<double> cfg, vel, imit_table, imit_params; int n_frames; double dt; };
+// a clip of a clip set (dm_mocap_create_set): its rows in the concatenated tables, its own dt and imitation parameters 13..15, its draw cdf
+struct ClipInfo { int row0, n_frames; double dt, loop, shift_x, shift_y, cdf; };
+struct dm_mocap { std::vector<double> cfg, vel, imit_table, imit_params; int n_frames; double dt; std::vector<ClipInfo> clips; /* empty: a single clip */ };
 
 extern "C" const char* dm_last_error(void) { return g_err.c_str(); }
 extern "C" int dm_abi_version(void) { return DM_ABI_VERSION; }
@@ -250,6 +252,39 @@ extern "C" int dm_mocap_set_imitation(dm_mocap* mc, const double* table, int32_t
   mc->imit_params.assign(params, params + 32);
   return DM_OK;
 }
+extern "C" int dm_mocap_create_set(const dm_mocap* const* clips, int32_t K, const double* weights, dm_mocap** out) {
+  if (!clips || !out || K < 1 || K > DM_MAX_CLIPS) return fail(DM_EINVAL, "dm_mocap_create_set: null argument, or n_clips outside 1..DM_MAX_CLIPS");
+  double total = 0;
+  for (int c = 0; c < K; c++) {
+    if (!clips[c]) return fail(DM_EINVAL, "dm_mocap_create_set: null clip");
+    if (!clips[c]->clips.empty()) return fail(DM_EINVAL, "dm_mocap_create_set: a clip of a set must be a single clip, not a set");
+    if (clips[c]->imit_table.empty() != clips[0]->imit_table.empty()) return fail(DM_EINVAL, "dm_mocap_create_set: either every clip carries an imitation table or none does");
+    if (!clips[c]->imit_table.empty())
+      for (int k = 0; k < 32; k++)
+        if ((k < 13 || k > 15) && clips[c]->imit_params[k] != clips[0]->imit_params[k]) return fail(DM_EINVAL, "dm_mocap_create_set: imitation parameters 0..12 and 16..31 must be equal across the set");
+    const double w = weights ? weights[c] : 1.0;
+    if (!(w >= 0) || !(w <= 1.7976931348623157e308)) return fail(DM_EINVAL, "dm_mocap_create_set: weights must be finite and >= 0");
+    total += w;
+  }
+  if (!(total > 0) || !(total <= 1.7976931348623157e308)) return fail(DM_EINVAL, "dm_mocap_create_set: the weights must have a positive, finite sum");
+  dm_mocap* mc = new (std::nothrow) dm_mocap();
+  if (!mc) return fail(DM_ENOMEM, "dm_mocap_create_set: out of memory");
+  mc->n_frames = 0; mc->dt = clips[0]->dt; mc->imit_params = clips[0]->imit_params;
+  double run = 0;
+  for (int c = 0; c < K; c++) {
+    const dm_mocap* q = clips[c];
+    run += weights ? weights[c] : 1.0;
+    const bool im = !q->imit_table.empty();
+    mc->clips.push_back(ClipInfo{mc->n_frames, q->n_frames, q->dt, im ? q->imit_params[15] : 0.0, im ? q->imit_params[13] : 0.0, im ? q->imit_params[14] : 0.0,
+                                 c == K - 1 ? 1.0 : run / total});
+    mc->cfg.insert(mc->cfg.end(), q->cfg.begin(), q->cfg.end()); mc->vel.insert(mc->vel.end(), q->vel.begin(), q->vel.end());
+    mc->imit_table.insert(mc->imit_table.end(), q->imit_table.begin(), q->imit_table.end());
+    mc->n_frames += q->n_frames;
+  }
+  if (K == 1) mc->clips.clear();      // a set of one clip IS that clip: n_frames, dt and the parameters above are its own
+  *out = mc;
+  return DM_OK;
+}
 extern "C" void dm_mocap_destroy(dm_mocap* mc) { delete mc; }
 
 template <class T> static hipError_t dalloc(T** p, size_t n) { hipError_t e = hipMalloc((void**)p, n * sizeof(T)); if (e == hipSuccess) e = hipMemset(*p, 0, n * sizeof(T)); return e; }
@@ -264,7 +299,7 @@ extern "C" void dm_batch_destroy(dm_batch* b) {
   if (b->ev_in) hipEventDestroy(b->ev_in);
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_clip, b->d_clip_rec, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
@@ -312,6 +347,8 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   A(b->d_ep_steps, n); A(b->d_done_reason, n);
   A(b->d_qpos_in, (size_t)n * NQ); A(b->d_qvel_in, (size_t)n * NV); A(b->d_fidx_in, n); A(b->d_debug, DM_DEBUG_DOUBLES);
   if (sizeof(Real) != sizeof(Ext)) A(b->d_cvt, (size_t)n * NB * 3);   // largest Real field per env: xipos (42)
+  A(b->d_clip, n);                                                    // DM_F_CLIP and the clip records: the last allocations, so that a single-clip batch's other arrays lie where they always lay
+  if (!mc->clips.empty()) A(b->d_clip_rec, mc->clips.size());
 #undef A
   if (!ok) { dm_batch_destroy(b); return fail(DM_ENOMEM, "dm_batch_create: hipMalloc failed"); }
   ok = hipMemcpy(b->d_model, &hm, sizeof hm, hipMemcpyHostToDevice) == hipSuccess;
@@ -328,6 +365,15 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   }
   b->B.imit_pdev = b->d_imit;
   b->B.imit_table = b->d_imit ? b->d_imit + 32 : nullptr;
+  if (!mc->clips.empty()) {             // the clip set: records, and the default assignment (global env) % K
+    b->n_clips = (int)mc->clips.size();
+    std::vector<ClipRec<Real>> rec;
+    for (const ClipInfo& c : mc->clips) { rec.push_back(ClipRec<Real>{c.row0, c.n_frames, (Real)c.dt, (Real)c.loop, (Real)c.shift_x, (Real)c.shift_y, c.cdf}); b->clip_frames.push_back(c.n_frames); }
+    std::vector<int> ids((size_t)n);
+    for (int e2 = 0; e2 < n; e2++) ids[e2] = e2 % b->n_clips;
+    ok = ok && hipMemcpy(b->d_clip_rec, rec.data(), rec.size() * sizeof(ClipRec<Real>), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(b->d_clip, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  } else b->clip_frames.push_back(mc->n_frames);
   // initial state = MjSim(model): qpos0, zero velocity
   std::vector<Real> q0((size_t)n * NQ);
   for (int e2 = 0; e2 < n; e2++) for (int k = 0; k < NQ; k++) q0[(size_t)e2 * NQ + k] = hm.qpos0[k];
@@ -400,6 +446,9 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
     case DM_OPT_HORIZON_TERMINATION:
       if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_HORIZON_TERMINATION must be 0 or 1");
       b->horizon_term = v != 0; break;
+    case DM_OPT_CLIP_MODE:
+      if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_CLIP_MODE must be 0 (fixed) or 1 (episode)");
+      b->clip_mode = (int)v; break;
     case DM_OPT_PIPELINE: {
       if (v < 1 || v > DM_MAX_PIPELINE) return fail(DM_EINVAL, "pipeline depth must be 1..DM_MAX_PIPELINE");
       HIPCHK(hipSetDevice(b->device));
@@ -421,7 +470,17 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
       if (v < 0 || v > 2) return fail(DM_EINVAL, "DM_OPT_PACKED must be 0, 1 or 2");
       b->packed = v != 0; b->packed_ext = v == 2; break;
     case 104: b->reorder = v != 0; if (!b->reorder) b->B.order = nullptr; break;   /* 1 (default): longest-first dispatch order (k_order) */
-    case 100: b->B.env_offset = (int)v; break;  /* global id of env 0 (multi-GPU sharding) */
+    case 100:                                   /* global id of env 0 (multi-GPU sharding); a multi-clip batch's default assignment follows it */
+      b->B.env_offset = (int)v;
+      if (multi_clip(b)) {
+        HIPCHK(hipSetDevice(b->device));
+        if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+        std::vector<int> ids((size_t)b->n);
+        for (int e = 0; e < b->n; e++) ids[e] = (int)(((long long)v + e) % b->n_clips + b->n_clips) % b->n_clips;
+        HIPCHK(hipMemcpyAsync(b->d_clip, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+      }
+      break;
     case 102: b->two_tier = v != 0; break;       /* 1 (default): register tier of NARROW_ROWS columns + overflow strip; 0: all 64 columns in registers */
     case 103: {                                 /* test hook: 1 = every PGS sweep takes the guarded-replay path (results must not change) */
       const Real lvl = v ? Real(-1e300) : Real(1e-10);
@@ -443,6 +502,12 @@ extern "C" int dm_batch_set_state(dm_batch* b, const double* qpos, const double*
   HIPCHK(hipSetDevice(b->device));
   if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
   const void *q, *v, *f, *mk; int rc;
+  if (multi_clip(b) && fidx && kind == DM_PTR_HOST) {       // a frame is local to the env's clip
+    std::vector<int> ids;
+    if ((rc = clip_ids_host(b, ids))) return rc;
+    for (int e = 0; e < b->n; e++)
+      if ((!mask || mask[e]) && (fidx[e] < 0 || fidx[e] >= b->clip_frames[ids[e]])) return fail(DM_EINVAL, "dm_batch_set_state: frame_idx outside the env's clip");
+  }
   if ((rc = stage_in(b, b->d_qpos_in, qpos, (size_t)b->n * NQ * 8, kind, &q))) return rc;
   if ((rc = stage_in(b, b->d_qvel_in, qvel, (size_t)b->n * NV * 8, kind, &v))) return rc;
   if ((rc = stage_in(b, b->d_fidx_in, fidx, (size_t)b->n * 4, kind, &f))) return rc;
@@ -461,6 +526,8 @@ extern "C" int dm_batch_reset(dm_batch* b, int32_t mode, int32_t hard, const uin
   const void* mk; int rc;
   if ((rc = stage_in(b, b->d_mask, mask, (size_t)b->n, kind, &mk))) return rc;
   HIPCHK(hipMemsetAsync(b->B.kin_ok, 0, (size_t)b->n, b->stream));
+  if (multi_clip(b)) hipLaunchKernelGGL(k_reset_clips, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk, clip_args(b));
+  else
   hipLaunchKernelGGL(k_reset, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk);
   hipLaunchKernelGGL(k_zero_masked, dim3((b->n + 255) / 256), dim3(256), 0, b->stream, b->d_ep_steps, (const unsigned char*)mk, b->n);   // DM_F_EPISODE_STEPS
   HIPCHK(hipGetLastError());
@@ -481,9 +548,9 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
   // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches;
-  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set)
+  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set; and those of a multi-clip batch, with or without it)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && !multi_clip(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -585,6 +652,15 @@ struct StepKernels {
   decltype(&k_step_packed) packed; decltype(&k_step_packed_act) packed_act; decltype(&k_step_packed_prof) packed_prof;
   decltype(&k_step_redo) redo; decltype(&k_step_narrow) narrow; decltype(&k_step_act) act; decltype(&k_step) single; decltype(&k_step_prof) prof;
 };
+// ... and a multi-clip batch's (kernels_clips.hip, kernels_packed_clips.hip): the same launches with the clip argument last; one set for every action mode
+// (they pick the controller at run time), none with per-stage profiling
+struct ClipStepKernels {
+  decltype(&k_step_packed_clips) packed; decltype(&k_step_packed_act_clips) packed_act; decltype(&k_step_redo_clips) redo; decltype(&k_step_narrow_clips) narrow;
+  decltype(&k_step_act_clips) act; decltype(&k_step_clips) single;
+};
+static ClipStepKernels clip_step_kernels(bool ext) {
+  return {ext ? k_step_packed_ext_clips : k_step_packed_clips, ext ? k_step_packed_act_ext_clips : k_step_packed_act_clips, k_step_redo_clips, k_step_narrow_clips, k_step_act_clips, k_step_clips};
+}
 static StepKernels step_kernels(bool spd, bool ext) {
   if (spd) return {ext ? k_step_packed_ext_spd : k_step_packed_spd, ext ? k_step_packed_act_ext_spd : k_step_packed_act_spd, k_step_packed_prof_spd,
                    k_step_redo_spd, k_step_narrow_spd, k_step_act_spd, k_step_spd, k_step_prof_spd};
@@ -595,6 +671,7 @@ static StepKernels step_kernels(bool spd, bool ext) {
 static int step_impl(dm_batch* b, const double* action, double* obs, double* reward, uint8_t* done, int32_t nsub, int32_t kind, const dmp::PolicyArgs* pol) {
   if (!b || !action || !obs || !reward || !done || nsub < 1) return fail(DM_EINVAL, "dm_batch_step: bad argument");
   if (pol && (kind != DM_PTR_DEVICE || b->prof || !b->two_tier)) return fail(DM_EINVAL, "dm_batch_step_act: device pointers, the two-tier kernel and no profiling");
+  if (b->prof && multi_clip(b)) return fail(DM_EUNSUPPORTED, "dm_batch_step: the profiling kernels (option 101) do not cover a multi-clip batch");
   HIPCHK(hipSetDevice(b->device));
   if (b->queue_cap > 0 && can_queue(b, kind, pol)) {
     // DM_OPT_STEP_QUEUE: remember the call; the queued steps run as ONE horizon launch (flush_queue).  A call that names a buffer an
@@ -621,6 +698,9 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   const bool reorder = b->reorder && b->has_rows && b->n > b->resident_waves;   // more envs than resident waves: later rounds exist, their tail matters
   const bool packed = packed_covers(b);      // this call runs on the packed kernels (profiled or not)
   const StepKernels K = step_kernels(b->B.action_mode >= 3, b->packed_ext);
+  const bool clips = multi_clip(b);          // the third axis: the clip forms, launched exactly like their counterparts with the clip argument last
+  const ClipStepKernels KC = clip_step_kernels(b->packed_ext);
+  const ClipArgs<Real> ca = clip_args(b);
   // early termination: the plain step launches, then k_terminate on the same stream; a fused policy step would act on the observation of an episode
   // k_terminate may still end, so the policy runs as a launch of its own behind it (below)
   const bool term = term_on(b);
@@ -631,6 +711,8 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     if (!term) return;
     const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count,
                       b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->trunc_cap, tick};
+    if (clips) hipLaunchKernelGGL(k_terminate_clips, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn, ca);
+    else
     hipLaunchKernelGGL(k_terminate, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn);
   };
   if (packed) {
@@ -647,7 +729,18 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   auto launch_part = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count, int* pair, const dmp::PolicyArgs* pa) {
     constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
     const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
-    if (packed) {
+    if (clips) {
+      if (packed) {
+        const dim3 grid((count + SLOTS - 1) / SLOTS);
+        int* rc = pair + b->redo_phase; int* rn = pair + (1 - b->redo_phase);
+        if (pa) hipLaunchKernelGGL(KC.packed_act, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, *pa, ca);
+        else hipLaunchKernelGGL(KC.packed, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, ca);
+        if (b->has_rows) hipLaunchKernelGGL(KC.redo, dim3(REDO_BLOCKS), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pa ? *pa : nopol, ca);
+      }
+      else if (pa) hipLaunchKernelGGL(KC.act, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, *pa, ca);
+      else hipLaunchKernelGGL(KC.narrow, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, ca);
+    }
+    else if (packed) {
       const dim3 grid((count + SLOTS - 1) / SLOTS);
       int* rc = pair + b->redo_phase; int* rn = pair + (1 - b->redo_phase);
       if (b->prof) hipLaunchKernelGGL(K.packed_prof, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, b->d_prof);
@@ -692,7 +785,8 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of redo counters is clean — pair 0's
     //  two are cleared above once if a pipelined step used them before)
     launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, fused);
-  } else { hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
+  } else if (clips) { hipLaunchKernelGGL(KC.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, ca); terminate(b->stream, b->B, 0, b->n); }
+  else { hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
   HIPCHK(hipGetLastError());
   for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
   if (packed) b->redo_phase ^= 1;
@@ -783,6 +877,7 @@ static int field_ptr(dm_batch* b, int field, void** p, size_t* count, bool* is_r
     case DM_F_CYCLE: *p = b->B.cycle; *count = n; break;
     case DM_F_EPISODE_STEPS: *p = b->d_ep_steps; *count = n; break;
     case DM_F_DONE_REASON: *p = b->d_done_reason; *count = n; break;
+    case DM_F_CLIP: *p = b->d_clip; *count = n; break;
     default: return fail(DM_EINVAL, "unknown field");
   }
   return DM_OK;
@@ -814,6 +909,13 @@ extern "C" int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t b
   if (bytes != need) return fail(DM_EINVAL, "dm_batch_set: buffer size does not match the field");
   if (field == DM_F_XIPOS || field == DM_F_COM_Z || field == DM_F_NCON || field == DM_F_NEFC || field == DM_F_CONTACT_GEOMS || field == DM_F_SOLVER_ITER)
     return fail(DM_EINVAL, "dm_batch_set: derived field is read-only");
+  if (field == DM_F_CLIP) {                      // validated on the host (a device caller's ids are read back first: one copy and a wait)
+    std::vector<int> ids((size_t)b->n);
+    if (kind == DM_PTR_HOST) memcpy(ids.data(), in, need);
+    else { HIPCHK(hipMemcpyAsync(ids.data(), in, need, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
+    for (int e = 0; e < b->n; e++) if (ids[e] < 0 || ids[e] >= b->n_clips) return fail(DM_EINVAL, "dm_batch_set: DM_F_CLIP outside [0, n_clips)");
+    HIPCHK(hipMemsetAsync(b->B.kin_ok, 0, (size_t)b->n, b->stream));
+  }
   if (field == DM_F_QPOS) HIPCHK(hipMemsetAsync(b->B.kin_ok, 0, (size_t)b->n, b->stream));   // parked kinematics belong to the old positions
   if (real && sizeof(Real) != sizeof(Ext)) {       // float32 build: copy, then narrow on the device
     const Ext* src = (const Ext*)in;
@@ -821,6 +923,10 @@ extern "C" int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t b
     hipLaunchKernelGGL(k_from_ext, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, b->stream, src, (Real*)p, cnt);
     HIPCHK(hipGetLastError());
   } else HIPCHK(hipMemcpyAsync(p, in, need, kind == DM_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
+  if (field == DM_F_CLIP && multi_clip(b)) {     // cursors beyond the new clip are held inside it (k_clip_clamp): no step can read past a clip's rows
+    hipLaunchKernelGGL(k_clip_clamp, dim3((b->n + 255) / 256), dim3(256), 0, b->stream, b->B, clip_args(b));
+    HIPCHK(hipGetLastError());
+  }
   if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
   return DM_OK;
 }

@@ -178,6 +178,13 @@ DM_DEV void reset_env(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, int
   dmw::sync_mem();
   if (lane == 0) reset_commit(B, env, ep, mode, hard, idx);
 }
+// ... on a multi-clip batch (step_rules.h ClipArgs; B is the batch, not a view): the episode's clip first, then the same reset in that clip's view
+template <class R>
+DM_DEV void reset_env_clips(const DevModel<R>& M, const Batch<R>& B, const ClipArgs<R>& C, Shared<R>& s, int env, int lane, int mode, int hard) {
+  const int c = dmw::uniform(C.episode_clip(B, env, B.episode[env], mode, hard));
+  reset_env(M, clip_view(B, C.rec[c]), s, env, lane, mode, hard);
+  if (lane == 0) C.clip[env] = c;
+}
 
 // ---- 5-term imitation reward (code.md:1017-1143; feature layout: deepmimic_mujoco_amd/imitation.py) -----------------------
 // [upstream] cMathUtil::QuatDiffTheta: rotation angle of q1 * conj(q0), normalised to [-pi, pi]
@@ -396,9 +403,11 @@ DM_DEV void spd_control(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, i
 // (up to MAXEFC) keeps the remaining columns in the env's global-memory strip s.aovf (see stage_constraint).
 // SPD: the instantiation for action modes 3 and 4 (spd_control above) — the action is a target pose and the control is evaluated per substep.  The
 // kernels of modes 0..2 instantiate SPD = false, whose code is what it was before the modes existed.
-template <class R, int ROWS, bool PROF, bool SPD>
-DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, StepScratch<R>& x, int env, int lane,
-                          const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0) {
+// CLIPS: NoClips, or the ClipArgs of a multi-clip batch (step_rules.h) — the step then runs in the env's clip view, uniform for the wave.
+template <class R, int ROWS, bool PROF, bool SPD, class CLIPS = NoClips>
+DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B_in, Shared<R>& s, StepScratch<R>& x, int env, int lane,
+                          const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0, const CLIPS& clips = CLIPS()) {
+  decltype(auto) B = clips.view_uniform(B_in, env);
   long long prof[PROF_SLOTS];
   for (int k = 0; k < PROF_SLOTS; k++) prof[k] = 0;
   long long tstart = 0;
@@ -463,6 +472,8 @@ DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
   if (lane == 0) { B.time[env] += M.timestep * n_substeps; reward[env] = rew; done[env] = dn ? 1 : 0; if (B.kin) B.kin_ok[env] = (kin_saved && !(dn && B.autoreset)) ? 1 : 0; }
   if (dn && B.autoreset) {                        // DummyVecEnv convention: obs of the fresh episode is returned
     dmw::sync_mem();
+    if constexpr (CLIPS::on) reset_env_clips(M, B_in, clips, s, env, lane, B.autoreset == 1 ? 0 : 1, 1);
+    else
     reset_env(M, B, s, env, lane, B.autoreset == 1 ? 0 : 1, 1);
   }
   // one coalesced 56-wide store (two branches, as the kernels have always had them: one store of a select moves the one-env kernels' spilled scalars)
@@ -479,11 +490,11 @@ DM_DEV bool env_step_impl(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s,
 }
 // The step by the batch's action mode: the wave testbench and the kernels of modes 3 and 4 come through here or name their instantiation; the
 // kernels of modes 0..2 call env_step_impl<.., false> directly and carry no controller code.
-template <class R, int ROWS = MAXEFC, bool PROF = false>
+template <class R, int ROWS = MAXEFC, bool PROF = false, class CLIPS = NoClips>
 DM_DEV bool env_step(const DevModel<R>& M, const Batch<R>& B, Shared<R>& s, StepScratch<R>& x, int env, int lane,
-                     const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0) {
-  if (B.action_mode >= 3) return env_step_impl<R, ROWS, PROF, true>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out);
-  return env_step_impl<R, ROWS, PROF, false>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out);
+                     const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, long long* prof_out = 0, const CLIPS& clips = CLIPS()) {
+  if (B.action_mode >= 3) return env_step_impl<R, ROWS, PROF, true, CLIPS>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out, clips);
+  return env_step_impl<R, ROWS, PROF, false, CLIPS>(M, B, s, x, env, lane, action, obs, reward, done, n_substeps, prof_out, clips);
 }
 
 }  // namespace dm

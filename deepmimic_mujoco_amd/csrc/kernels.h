@@ -1,5 +1,5 @@
 // kernels.h — what the translation units of libdmenv.so with environment kernels share: the build's arithmetic type and the prototypes of the step
-// kernels that one unit defines and dmenv.hip launches.  The library's eight units (csrc/build.py UNITS):
+// kernels that one unit defines and dmenv.hip launches.  The library's ten units (csrc/build.py UNITS):
 //   dmenv.hip           one-env step kernels of action modes 0..2, reset / state / ordering / render / state-feature / termination kernels, the batch half of the C ABI
 //                       (host side: models, mocap, batches, options, state, step / rollout / queue, profiling and timing)
 //   views.hip           dm_batch_render, dm_batch_state_features and dm_batch_floor_contacts (host side: one prologue, one staging helper over view_stage.h; kernels in dmenv.hip's unit)
@@ -9,6 +9,9 @@
 //                       options of kernels_rollout.hip; a unit of its own so that k_rollout_packed stays the code object it was
 //   kernels_spd.hip / kernels_packed_spd.hip   the one-env and the packed step kernels of action modes 3 and 4 (stable PD control per substep), units
 //                       of their own with the options of dmenv.hip / kernels_packed.hip: the kernels of modes 0..2 carry no controller code
+//   kernels_clips.hip / kernels_packed_clips.hip   the kernels of MULTI-CLIP batches (dm_mocap_create_set: one clip per env, step_rules.h ClipArgs): the one-env and
+//                       the packed step kernels, and the clip forms of k_reset, k_terminate, k_state_features and k_imitation_terms; units of their own with the
+//                       options of dmenv.hip / kernels_packed.hip.  They pick the stable-PD instantiation by the action mode at run time.
 //   kernels_packed.hip  the four-environments-per-wavefront per-step kernels (slot_kernel.h / slot_step.h): compiled with their own backend options
 //                       (csrc/build.py PACKED_FLAGS — one wave per SIMD with the whole register file wants a scheduler that goes for
 //                       instruction-level parallelism, the two-waves-per-SIMD one-env kernels do not: profiles/r04_ab_kernel_variants.md)
@@ -89,3 +92,24 @@ __global__ void k_step_redo_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::B
                                 unsigned char* __restrict__ done, int n_substeps, int first, const int* __restrict__ redo_count, int* __restrict__ redo_count_next, dmp::PolicyArgs pa);
 __global__ void k_step_prof_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
                                 unsigned char* __restrict__ done, int n_substeps, long long* prof);
+// ---- kernels_packed_clips.hip, kernels_clips.hip: the same launches on a multi-clip batch (the clip argument last; action modes 0..4) ------------------
+__global__ void k_step_packed_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                    unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dm::ClipArgs<Real> ca);
+__global__ void k_step_packed_ext_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                        unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dm::ClipArgs<Real> ca);
+__global__ void k_step_packed_act_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                        unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dmp::PolicyArgs pa, dm::ClipArgs<Real> ca);
+__global__ void k_step_packed_act_ext_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                            unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count, dmp::PolicyArgs pa, dm::ClipArgs<Real> ca);
+__global__ void k_step_narrow_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                    unsigned char* __restrict__ done, int n_substeps, int first, int count, dm::ClipArgs<Real> ca);
+__global__ void k_step_act_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                 unsigned char* __restrict__ done, int n_substeps, int first, int count, dmp::PolicyArgs pa, dm::ClipArgs<Real> ca);
+__global__ void k_step_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                             unsigned char* __restrict__ done, int n_substeps, dm::ClipArgs<Real> ca);
+__global__ void k_step_redo_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
+                                  unsigned char* __restrict__ done, int n_substeps, int first, const int* __restrict__ redo_count, int* __restrict__ redo_count_next, dmp::PolicyArgs pa,
+                                  dm::ClipArgs<Real> ca);
+__global__ void k_clip_clamp(dm::Batch<Real> B, dm::ClipArgs<Real> ca);
+__global__ void k_reset_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, int mode, int hard, const unsigned char* __restrict__ mask, dm::ClipArgs<Real> ca);
+__global__ void k_terminate_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, TermArgs T, Ext* __restrict__ obs, unsigned char* __restrict__ done, dm::ClipArgs<Real> ca);

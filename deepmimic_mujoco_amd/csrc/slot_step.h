@@ -194,6 +194,13 @@ DM_DEV void slot_reset_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R
   dmw::sync_mem();
   if (doit && sl == 0) reset_commit(B, env, ep, mode, hard, idx);
 }
+// ... on a multi-clip batch (env_step.h reset_env_clips): the slot's episode clip, then the same reset in that clip's view
+template <class R>
+DM_DEV void slot_reset_env_clips(const DevModel<R>& M, const Batch<R>& B, const ClipArgs<R>& C, SlotShared<R>& s, int env, int sl, bool doit, int mode, int hard) {
+  const int c = C.episode_clip(B, env, B.episode[env], mode, hard);
+  slot_reset_env(M, clip_view(B, C.rec[c]), s, env, sl, doit, mode, hard);
+  if (doit && sl == 0) C.clip[env] = c;
+}
 
 // ---- 5-term imitation reward (env_step.h imitation_reward; code.md:1017-1143) for the slot's environment: one extra kinematics pass on
 // the integrated state, whose by-products are the joint features.  Slot lane = body - 1 (lane 0 root, lanes 1..12 joint groups); the four
@@ -287,10 +294,12 @@ DM_DEV R slot_imitation_reward(const DevModel<R>& M, const Batch<R>& B, SlotShar
 // means what it says and the first evaluation may skip its position stage (slot_forward): one kinematics pass in five less with the 5-term
 // reward, bit-identical results.  Without kin_carry (the first step of a launch, the step after an in-wave re-step) the flags are cleared first.
 // SPD: the instantiation for action modes 3 and 4 (slot_spd_control); the kernels of modes 0..2 — the horizon launch among them — instantiate SPD = false.
-template <class R, bool PROF, bool CARRY, int MAXR, bool SPD>
+// CLIPS: NoClips, or the ClipArgs of a multi-clip batch (step_rules.h).  The clip view is per slot; it is built where the clip is read — the action front end, the
+// reward epilogue, the reset — and is not alive across the substeps between them: the constraint solve has no registers to give.
+template <class R, bool PROF, bool CARRY, int MAXR, bool SPD, class CLIPS = NoClips>
 DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, SlotTables& tb, int env, int sl, int lane, bool live,
                                const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int* redo_count, int* redo_list,
-                               long long* prof_out = 0, bool kin_carry = false) {
+                               long long* prof_out = 0, bool kin_carry = false, const CLIPS& clips = CLIPS()) {
   long long prof[32];
   for (int k = 0; k < 32; k++) prof[k] = 0;
   long long tstart = 0;
@@ -298,16 +307,19 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   const LaneTopo lt = lane_topo(sl);
   if constexpr (CARRY) { if (!kin_carry && sl == 0) s.kin_ok() = R(0); }       // (ordered before the first read by slot_load_env's hand-off)
   DofVec<R> qbar, vbar;                  // SPD: dof-distributed targets (the mocap frame the env is at as the env step starts: env_step.h step_start_frame)
+  {
+  decltype(auto) Bv = clips.view(B, env);      // (the action front ends of modes 1, 2 and 4 read the frame the env is at)
   if constexpr (SPD) {
     slot_load_env(M, B, s, env, sl, live, (const double*)0);
 #pragma unroll
     for (int c = 0; c < DOF_PASSES; c++) {
       const int d = sl + SW * c;
       qbar.r[c] = 0; vbar.r[c] = 0;
-      if (d >= 6 && d < NV) spd_target(M, B, env, d - 6, action, n_substeps, qbar.r[c], vbar.r[c]);
+      if (d >= 6 && d < NV) spd_target(M, Bv, env, d - 6, action, n_substeps, qbar.r[c], vbar.r[c]);
     }
   } else
-  slot_load_env(M, B, s, env, sl, live, action, n_substeps);
+  slot_load_env(M, Bv, s, env, sl, live, action, n_substeps);
+  }
   R xip[3];
   int why = 0;
   for (int k = 0; k < n_substeps; k++) {
@@ -343,40 +355,45 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
     if (sl == 0) { B.comz[env] = z; B.ncon[env] = s.ncon; B.nefc[env] = s.nefc; B.status[env] = s.status; B.solver_iter[env] = s.solver_iter; if constexpr (!CARRY) order_ticket(B, env, s.nefc, s.solver_iter); }   // (CARRY = inside a horizon launch: no tickets)
   }
   R rew = 1;
+  {
+  decltype(auto) Bc = clips.view(B, env);        // the reward's mocap tables and frame rules are those of the env's clip (NoClips: the batch itself)
   if (B.reward_mode == REW_V3_CONFIG) {
-    const FrameStep f = frame_step(REW_V3_CONFIG, M, B, n_substeps, B.frame_idx[env], 0, 0);
+    const FrameStep f = frame_step(REW_V3_CONFIG, M, Bc, n_substeps, B.frame_idx[env], 0, 0);
     R err = 0;
-    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
+    for (int i = 7; i < NQ; i++) err += fabs(s.qpos[i] - Bc.mocap_cfg[(size_t)f.row * NQ + i]);
     rew = exp_once(-err);
     dmw::sync_mem();
     if (live && sl == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_V2_POSE) {
-    const FrameStep f = frame_step(REW_V2_POSE, M, B, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
+    const FrameStep f = frame_step(REW_V2_POSE, M, Bc, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
     R err = 0;
-    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - B.mocap_cfg[(size_t)f.row * NQ + i]);
+    for (int i = 3; i < NQ; i++) err += fabs(s.qpos[i] - Bc.mocap_cfg[(size_t)f.row * NQ + i]);
     const R acs = control_cost(B, env);
     rew = exp_once(R(-2) * err) - R(0.1) * acs;
     dmw::sync_mem();
     if (live && sl == 0) B.frame_idx[env] = f.store;
   } else if (B.reward_mode == REW_IMITATION) {   // code.md:1017-1143: the state after the step against frame idx + 1 (env_step.h)
-    const FrameStep f = frame_step(REW_IMITATION, M, B, n_substeps, B.frame_idx[env], 0, B.cycle[env]);
-    rew = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, f.cycle * B.imit_params[13], f.cycle * B.imit_params[14]);
+    const FrameStep f = frame_step(REW_IMITATION, M, Bc, n_substeps, B.frame_idx[env], 0, B.cycle[env]);
+    rew = slot_imitation_reward(M, B, s, sl, lt, Bc.imit_table + (size_t)f.row * IMIT_FEAT, f.cycle * Bc.imit_params[13], f.cycle * Bc.imit_params[14]);
     dn = dn || f.ended;
     dmw::sync_mem();
     if (live && sl == 0) { B.frame_idx[env] = f.store; B.cycle[env] = f.cycle; }
   } else if (B.reward_mode == REW_V1_QUAT) {     // src/dp_env_v1.py:82-158 (env_step.h): the cursor counts steps, the pose reward every `upd` steps, minus the control cost
-    const FrameStep f = frame_step(REW_V1_QUAT, M, B, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
+    const FrameStep f = frame_step(REW_V1_QUAT, M, Bc, n_substeps, B.frame_idx[env], B.frame_init[env], 0);
     // (the four environments of a wave sit at different cursors: the pass is collective, so it runs every step on every slot — its kinematics are the
     //  next step's first evaluation's anyway (kin_carry) — and a slot takes its value on the steps its own cursor says so)
-    const R robs = slot_imitation_reward(M, B, s, sl, lt, B.imit_table + (size_t)f.row * IMIT_FEAT, R(0), R(0), B.imit_table + (size_t)f.row_v * IMIT_FEAT);
+    const R robs = slot_imitation_reward(M, B, s, sl, lt, Bc.imit_table + (size_t)f.row * IMIT_FEAT, R(0), R(0), Bc.imit_table + (size_t)f.row_v * IMIT_FEAT);
     const R acs = control_cost(B, env);
     rew = (f.take ? robs : R(0)) - R(0.1) * acs;
     dmw::sync_mem();
     if (live && sl == 0) B.frame_idx[env] = f.store;
   }
+  }
   if (live && sl == 0) { B.time[env] += M.timestep * n_substeps; reward[env] = rew; done[env] = dn ? 1 : 0; if (B.kin) B.kin_ok[env] = 0; }
   if (B.autoreset) {                              // DummyVecEnv convention: obs of the fresh episode is returned
     dmw::sync_mem();
+    if constexpr (CLIPS::on) slot_reset_env_clips(M, B, clips, s, env, sl, dn && live, B.autoreset == 1 ? 0 : 1, 1);
+    else
     slot_reset_env(M, B, s, env, sl, dn && live, B.autoreset == 1 ? 0 : 1, 1);
   }
   // the slot's kinematics are those of the state the env is left in: the 5-term reward's pass ran on it and no reset replaced it (a slot that
@@ -397,12 +414,12 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   return live;                                  // the slot's environment was stepped and stored by this wave
 }
 // The step by the batch's action mode (the wave testbench; see env_step.h env_step).  Device kernels name their instantiation.
-template <class R, bool PROF = false, bool CARRY = false, int MAXR = 2 * SW>
+template <class R, bool PROF = false, bool CARRY = false, int MAXR = 2 * SW, class CLIPS = NoClips>
 DM_DEV bool slot_env_step(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, SlotTables& tb, int env, int sl, int lane, bool live,
                           const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int* redo_count, int* redo_list,
-                          long long* prof_out = 0, bool kin_carry = false) {
-  if (B.action_mode >= 3) return slot_env_step_impl<R, PROF, CARRY, MAXR, true>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry);
-  return slot_env_step_impl<R, PROF, CARRY, MAXR, false>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry);
+                          long long* prof_out = 0, bool kin_carry = false, const CLIPS& clips = CLIPS()) {
+  if (B.action_mode >= 3) return slot_env_step_impl<R, PROF, CARRY, MAXR, true, CLIPS>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry, clips);
+  return slot_env_step_impl<R, PROF, CARRY, MAXR, false, CLIPS>(M, B, s, tb, env, sl, lane, live, action, obs, reward, done, n_substeps, redo_count, redo_list, prof_out, kin_carry, clips);
 }
 
 // ---- a whole horizon without leaving the wave (dm_batch_rollout) ---------------------------------------------------------------------

@@ -88,6 +88,48 @@ DM_DEV double rng_uniform(unsigned long long seed, int genv, int episode, int k)
   return (double)(h >> 11) * (1.0 / 9007199254740992.0);
 }
 
+// ---- clip sets: K clips concatenated row-wise in the batch's three tables, one clip per env ---------------------------------------
+// A rule below reads the clip through the Batch it is given: n_frames, mocap_dt, the three table pointers, imit_params[13..15].  On a single-clip batch
+// that is the batch itself.  On a multi-clip batch the layouts hand the rules the env's CLIP VIEW (clip_view): the same batch with exactly those members
+// replaced by the clip's own — the tables start at the clip's first row, so frame_idx / frame_init / cycle stay local to the clip.  The view is uniform
+// per wave in the one-env layout and per slot in the packed one (which builds it at its uses and does not carry it across the solve).
+template <class R>
+struct ClipRec { int row0, n_frames; R dt, loop, shift_x, shift_y; double cdf; };   // cdf: running sum of the draw weights over their total, 1.0 for the last clip
+template <class R>
+DM_DEV Batch<R> clip_view(Batch<R> b, const ClipRec<R>& r) {
+  b.mocap_cfg += (size_t)r.row0 * NQ; b.mocap_vel += (size_t)r.row0 * NV;
+  if (b.imit_table) b.imit_table += (size_t)r.row0 * IMIT_FEAT;
+  b.n_frames = r.n_frames; b.mocap_dt = r.dt;
+  b.imit_params[13] = r.shift_x; b.imit_params[14] = r.shift_y; b.imit_params[15] = r.loop;
+  return b;
+}
+// The switch the step and reset routines are instantiated with (the last template parameter; the way slot_rollout takes its termination).  NoClips — every
+// kernel of a single-clip batch — hands the batch itself back by reference and compiles no trace of the clip code.
+struct NoClips {
+  static constexpr bool on = false;
+  template <class R> DM_DEV const Batch<R>& view(const Batch<R>& B, int) const { return B; }
+  template <class R> DM_DEV const Batch<R>& view_uniform(const Batch<R>& B, int) const { return B; }
+};
+// ... and the kernel argument of the clip forms (kernels_clips.hip, kernels_packed_clips.hip), beside the batch as PolicyArgs and TermArgs are
+template <class R>
+struct ClipArgs {
+  static constexpr bool on = true;
+  int* clip;                   // [N] DM_F_CLIP: the env's clip (stored by reset_commit's lane where DM_OPT_CLIP_MODE draws it)
+  const ClipRec<R>* rec;       // [n_clips]
+  int n_clips, mode;           // DM_OPT_CLIP_MODE
+  DM_DEV Batch<R> view(const Batch<R>& B, int env) const { return clip_view(B, rec[clip[env]]); }
+  DM_DEV Batch<R> view_uniform(const Batch<R>& B, int env) const { return clip_view(B, rec[dmw::uniform(clip[env])]); }
+  // The clip of episode `ep` of env `env`.  "episode" mode draws it wherever the reset sets the frame cursor (reset_commit's condition), from stream
+  // index 128 of the episode's RNG (0 is the frame, 1..35 and 64..97 the pose noise): the first clip whose cdf exceeds the draw.  Otherwise the env keeps its clip.
+  DM_DEV int episode_clip(const Batch<R>& B, int env, int ep, int reset_mode, int hard) const {
+    if (mode != 1 || !(reset_mode == 0 || (reset_mode == 1 && hard))) return clip[env];
+    const double u = rng_uniform(B.seed, B.env_offset + env, ep, 128);
+    int c = 0;
+    while (c < n_clips - 1 && !(u < rec[c].cdf)) c++;
+    return c;
+  }
+};
+
 // ---- mocap frame cursors ---------------------------------------------------------------------------------------------------------------
 // dp_env_v1's update interval (src/dp_env_v1.py:82-158): env steps per mocap frame, at least one
 template <class R>

@@ -38,6 +38,7 @@ DM_DEV unsigned floor_touch_mask(const DevModel<Real>& M, const Shared<Real>& s,
   return (unsigned)dmw::ballot(t);
 }
 
+#ifndef DM_TERM_NO_KERNELS    // (kernels_clips.hip — the clip form of k_terminate, a unit of its own — wants the struct and the floor test)
 // state v: an explicit pose (qpos_ext [n,35]) or the batch's state of env env_ids[v] (or v)
 __global__ __launch_bounds__(64) void k_floor_contacts(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos,
                                                        const double* __restrict__ qpos_ext, const int* __restrict__ env_ids, int* __restrict__ out) {
@@ -100,4 +101,5 @@ __global__ void k_zero_masked(int* __restrict__ v, const unsigned char* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && (!mask || mask[i])) v[i] = 0;
 }
+#endif  // DM_TERM_NO_KERNELS
 #endif  // DM_TERM_ARGS_ONLY

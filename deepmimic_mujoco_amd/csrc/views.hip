@@ -27,6 +27,14 @@ __global__ void k_imitation_terms(const DevModel<Real>* __restrict__ Mp, Batch<R
 __global__ void k_floor_contacts(const DevModel<Real>* __restrict__ Mp, const Real* __restrict__ state_qpos, const double* __restrict__ qpos_ext,
                                  const int* __restrict__ env_ids, int* __restrict__ out);
 
+// ... and their forms on a multi-clip batch (kernels_clips.hip)
+__global__ void k_state_features_clips(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const double* __restrict__ qpos_ext,
+                                       const double* __restrict__ qvel_ext, const double* __restrict__ phase_ext, const int* __restrict__ env_ids,
+                                       Ext* __restrict__ out, ClipArgs<Real> ca);
+__global__ void k_imitation_terms_clips(const DevModel<Real>* __restrict__ Mp, Batch<Real> B, const double* __restrict__ qpos_ext,
+                                        const double* __restrict__ qvel_ext, const int* __restrict__ frame_ext, const int* __restrict__ cycle_ext,
+                                        const int* __restrict__ env_ids, Ext* __restrict__ out, ClipArgs<Real> ca);
+
 // the argument checks every view starts with, in this order; nothing here touches a device.  required: the pointers the view cannot do without;
 // explicit_state: the caller gave states of their own (`state_word` names them in the message) instead of the batch's
 static int view_args(dm_batch* b, bool required, int kind, int n, bool explicit_state, const char* state_word, const int32_t* env_ids, const char* who) {
@@ -137,6 +145,9 @@ extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const do
   const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_p = st.in(phase, (size_t)n * sizeof(double));
   const int i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NSTATE * sizeof(double));
   if ((rc = st.commit())) return rc;
+  if (multi_clip(b)) hipLaunchKernelGGL(k_state_features_clips, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                                        st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o), clip_args(b));
+  else
   hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
                      st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());
@@ -168,13 +179,22 @@ extern "C" int dm_batch_imitation_terms(dm_batch* b, const double* qpos, const d
   if (explicit_state && !(qpos && qvel && frame)) return fail(DM_EINVAL, "dm_batch_imitation_terms: an explicit state needs qpos, qvel and frame");
   if (!b->B.imit_table) return fail(DM_EINVAL, "dm_batch_imitation_terms: the mocap has no imitation table (dm_mocap_set_imitation)");
   if (!explicit_state && b->B.reward_mode != REW_IMITATION) return fail(DM_EINVAL, "dm_batch_imitation_terms: the batch's own cursors name the compared row in reward mode 3 only");
-  if (explicit_state && kind == DM_PTR_HOST)
+  if (explicit_state && multi_clip(b) && n > b->n) return fail(DM_EINVAL, "dm_batch_imitation_terms: on a multi-clip batch state i is compared with the clip of env i: n exceeds the batch size");
+  if (explicit_state && kind == DM_PTR_HOST && !multi_clip(b))
     for (int i = 0; i < n; i++) if (frame[i] < 0 || frame[i] >= b->B.n_frames) return fail(DM_EINVAL, "dm_batch_imitation_terms: frame out of range");
   if ((rc = view_enter(b, env_ids, n, kind == DM_PTR_HOST, who))) return rc;
+  if (explicit_state && kind == DM_PTR_HOST && multi_clip(b)) {      // frame i is local to the clip of env i
+    std::vector<int> ids;
+    if ((rc = clip_ids_host(b, ids))) return rc;
+    for (int i = 0; i < n; i++) if (frame[i] < 0 || frame[i] >= b->clip_frames[ids[i]]) return fail(DM_EINVAL, "dm_batch_imitation_terms: frame outside the env's clip");
+  }
   Stage st(b, kind, who);
   const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_f = st.in(frame, (size_t)n * sizeof(int32_t));
   const int i_c = st.in(cycle, (size_t)n * sizeof(int32_t)), i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NTERMS * sizeof(double));
   if ((rc = st.commit())) return rc;
+  if (multi_clip(b)) hipLaunchKernelGGL(k_imitation_terms_clips, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                                        st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o), clip_args(b));
+  else
   hipLaunchKernelGGL(k_imitation_terms, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
                      st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());

@@ -65,6 +65,8 @@ def _camera(camera_name):
 # a motor command; "spd-target": the action is a target pose (28 absolute hinge angles, rad) tracked by a stable PD controller that is evaluated at the
 # start of every simulation substep (DeepMimic's action); "spd-mocap": the same controller around mocap frame + action (include/dmenv.h has the rule).
 ACTION_MODES = {"raw": 0, "p-control": 1, "pd": 2, "spd-target": 3, "spd-mocap": 4}
+# DM_OPT_CLIP_MODE of a multi-clip DPVecEnv (a list of motions): an env keeps its clip, or every episode start draws one
+CLIP_MODES = {"fixed": 0, "episode": 1}
 
 
 def _action_space(cm, action_mode):
@@ -411,8 +413,13 @@ class DPVecEnv(object):
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
                  step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False,
-                 horizon_termination=False):
-        """reward_terms (reward="imitation" only, else ValueError): after every `step` one more launch (Batch.imitation_terms) takes the reward the step
+                 horizon_termination=False, clip_weights=None, clip_mode="fixed"):
+        """motion: a clip, or a LIST of clips (names / files): the batch is then multi-clip (clips.ClipSet, dm_mocap_create_set) — env e imitates clip
+        (env_offset + e) % K (`clip_ids`, `set_clip_ids`) and, with clip_mode="episode", every reset that sets the frame cursor first draws the episode's clip
+        with the probabilities clip_weights (None: uniform).  `mocap` / `mocap_dt` / `mocap_data_len` are then the FIRST clip's, `clip_set` the whole set, and
+        frame_skip="mocap" (the imitation reward's default) is taken from the first clip's dt for every env: clips of another dt (walk 0.0333 s, spinkick
+        0.0167 s) then play at the wrong speed, with a warning.  Horizon launches and the step queue run as step launches (`horizon_termination` included).  clip_mode="fixed" (default): an env keeps its clip.
+        reward_terms (reward="imitation" only, else ValueError): after every `step` one more launch (Batch.imitation_terms) takes the reward the step
         returned apart, and `last_reward_terms` is the [N, 28] float64 rows (imitation.py has the columns: the five errors, the five weighted terms, their
         sum — the step's reward —, the joint groups' shares of the pose error, the end effectors' distances), numpy or device tensor like the step's
         outputs and overwritten by the next step.  With `autoreset`, the row of an environment the step ended is NaN: the step kernel has already
@@ -476,8 +483,16 @@ class DPVecEnv(object):
         self._reward_terms = bool(reward_terms)
         self._autoreset = autoreset not in (None, "none")
         self.last_reward_terms = None
+        if clip_mode not in CLIP_MODES:
+            raise ValueError("clip_mode must be one of %s" % sorted(CLIP_MODES))
+        self.clip_set = None
+        many = isinstance(motion, (list, tuple))
+        if not many and clip_weights is not None:
+            raise ValueError("clip_weights needs a list of motions")
+        if many and batch_factory is not None:
+            raise ValueError("a list of motions makes a multi-clip Batch: batch_factory is not supported with it")
         self.mocap = MocapDM()
-        self.mocap.load_mocap(motion)
+        self.mocap.load_mocap(motion[0] if many else motion)
         self.mocap_dt = self.mocap.dt
         self.mocap_data_len = len(self.mocap.data)
         self._cm = _load_model(xml_path)
@@ -498,7 +513,15 @@ class DPVecEnv(object):
             from .imitation import ImitationSpec
             self.imitation = ImitationSpec(self._cm)
             imit = self.imitation.table_for(self.mocap)
-        if batch_factory is None:
+        if many:
+            from .clips import ClipSet
+            self.clip_set = ClipSet(motion, clip_weights, self.imitation if imit is not None else None)
+            if reward == "imitation" and self.frame_skip == per_frame and len(set(max(1, int(d / float(self._cm.timestep))) for d in self.clip_set.dt)) > 1:
+                import warnings
+                warnings.warn("a list of motions with different frame durations %s: frame_skip=%d is the first clip's; the imitation reward advances one frame per "
+                              "env step, so the other clips play at another speed" % ([round(float(d), 4) for d in self.clip_set.dt], self.frame_skip))
+            self._batch = Batch(self._cm, None, None, self.num_envs, device=device, flags=flags, dtype=dtype, clips=self.clip_set)
+        elif batch_factory is None:
             self._batch = Batch(self._cm, self.mocap.data_config, self.mocap.data_vel, self.num_envs, device=device,
                                 flags=flags, mocap_dt=float(self.mocap_dt), imitation=imit, dtype=dtype)
         elif imit is not None:
@@ -514,6 +537,9 @@ class DPVecEnv(object):
         self.action_mode = action_mode
         b.set_option(A.OPT_SEED, int(seed))
         b.set_option(A.OPT_ENV_OFFSET, int(env_offset))
+        if many:
+            b.set_option(A.OPT_CLIP_MODE, CLIP_MODES[clip_mode])
+        self.clip_mode = clip_mode
         b.set_option(A.OPT_DIAGNOSTICS, 1 if diagnostics else 0)
         self.fall_body_mask = fall_body_mask(fall_contact_bodies)
         self.max_episode_steps = int(max_episode_steps)
@@ -531,7 +557,8 @@ class DPVecEnv(object):
         # for the slowest wave of every step
         # (with early termination on there is no horizon launch unless `horizon_termination`: a horizon is step launches, for which the per-step choice above holds)
         self.horizon_packed_ok = (packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64
-                                  and (self.horizon_termination or not (self.fall_body_mask or self.max_episode_steps)))
+                                  and (self.horizon_termination or not (self.fall_body_mask or self.max_episode_steps))
+                                  and not many)      # (a multi-clip batch's horizons are step launches too)
         if packed or auto:
             b.set_option(A.OPT_PACKED, 2 if (packed is not True and packed == 2) else 1)     # (packed=2: per-step launches with the three-set code, see the docstring)
         if auto:
@@ -558,6 +585,14 @@ class DPVecEnv(object):
 
     def seed(self, seed):
         self._batch.set_option(A.OPT_SEED, int(seed))
+
+    def clip_ids(self, out=None):
+        """int32 [N]: the clip of `clip_set` each environment imitates (F_CLIP; all 0 with a single motion).  `out`: a numpy array or a device tensor."""
+        return self._batch.get(A.F_CLIP, out)
+
+    def set_clip_ids(self, ids):
+        """Assign the environments' clips (values outside the set raise).  The frame cursors are left alone: follow with `reset` or `batch.set_state`."""
+        self._batch.set(A.F_CLIP, ids)
 
     def done_reason(self, out=None):
         """int32 [N]: why the last step ended each environment's episode — bits termination.DONE_STEP (COM band, clip end), DONE_FALL, DONE_TIME_LIMIT; 0

@@ -262,6 +262,12 @@ class _TimeLimitBootstrap(object):
         M = int(env.max_episode_steps or 0)
         if M <= 0:
             raise ValueError("bootstrap_time_limit needs an env with a time limit (DPVecEnv(max_episode_steps=M), M > 0)")
+        # a multi-clip batch with the 171-wide observation: the phase of a truncated state runs over the length of the clip the env was on, which a log
+        # record does not carry.  With clip_mode "fixed" it is still the env's clip when the log is read; with "episode" it has been redrawn by then.
+        self.many_clips = getattr(env, "clip_set", None) is not None and len(env.clip_set) > 1
+        if self.many_clips and env_obs_width(env) != 56 and getattr(env, "clip_mode", "fixed") != "fixed":
+            raise ValueError("bootstrap_time_limit with obs_mode=\"deepmimic\" on a list of motions needs clip_mode=\"fixed\": the truncation log does not record the "
+                             "clip a truncated state was on, and clip_mode=\"episode\" has redrawn it when the log is read")
         C = self.capacity = n * (T // M + 1)
         env.batch.set_option(A.OPT_TRUNCATION_LOG, C)
         self.log = (torch.zeros(1, dtype=torch.int32, device=device), torch.zeros((C, 4), dtype=torch.int32, device=device),
@@ -290,7 +296,15 @@ class _TimeLimitBootstrap(object):
             torch.cat([qp[:, 7:], qv[:, 6:]], 1, out=self.ob)
         else:
             # the phase the features launch would have given this state had the episode gone on: from the cursors as the step left them
-            phase = phase_of(batch_option(b, A.OPT_REWARD_MODE), idx[:, 2], idx[:, 3], b.n_frames).contiguous()
+            mode = batch_option(b, A.OPT_REWARD_MODE)
+            if self.many_clips:      # (clip_mode "fixed": the record's env is still on the clip it was truncated on; slots beyond the count are masked below)
+                lens = torch.tensor([int(x) for x in self.env.clip_set.n_frames], device=idx.device, dtype=torch.int64)
+                clip = torch.as_tensor(self.env.clip_ids(), device=idx.device).to(torch.int64)
+                F = lens[clip[idx[:, 0].to(torch.int64).clamp(0, n - 1)]]
+                k = idx[:, 2].to(torch.int64) + (idx[:, 3].to(torch.int64) if mode in (2, 4) else 0)      # state_features.phase_of with a length per record
+                phase = ((k % F).to(torch.float64) / F.to(torch.float64)).contiguous()
+            else:
+                phase = phase_of(mode, idx[:, 2], idx[:, 3], b.n_frames).contiguous()
             b.state_features(as_buf(self.ob), qpos=as_buf(qp), qvel=as_buf(qv), phase=as_buf(phase))
         with torch.no_grad():
             v = self.pi.forward_value(self.ob).to(torch.float32)

@@ -94,6 +94,25 @@ int dm_mocap_create(const double* data_config, const double* data_vel, int32_t n
  * specify but dp_env_v3.py:117-128 never computes): table [n_frames, 112] and params [32], both built on the host by
  * deepmimic_mujoco_amd/imitation.py (row layout documented there).  Call before dm_batch_create; enables reward mode 3. */
 int dm_mocap_set_imitation(dm_mocap* mc, const double* table, int32_t n_cols, const double* params);
+/* A CLIP SET: K = n_clips clips (1 <= K <= DM_MAX_CLIPS) for one batch, every environment imitating one of them (DM_F_CLIP) — DeepMimic trains one policy
+ * on a set of motions and picks one as an episode starts.  The clips' data_config, data_vel and, where present, imitation tables are concatenated row-wise
+ * on the device; a clip keeps its own n_frames, dt and imitation parameters 13..15 (cycle shift x, y and the loop flag).  Either every clip carries an
+ * imitation table or none does, and parameters 0..12 and 16..31 (joint weights, root weight, end effectors) must be equal across the set: DM_EINVAL otherwise.
+ * weights [K]: the probabilities (up to their sum) with which DM_OPT_CLIP_MODE 1 draws a clip; NULL: uniform; all >= 0 and finite, sum > 0, else DM_EINVAL.
+ * The draw uses cdf[c] = (w[0] + .. + w[c]) / sum in float64, the last entry exactly 1.0.  The result goes to dm_batch_create like any other mocap handle (the clips
+ * may be destroyed afterwards) and makes the batch MULTI-CLIP:
+ *   - DM_F_FRAME_IDX, DM_F_FRAME_INIT and DM_F_CYCLE stay local to the env's clip; the table row is the clip's first row + the local frame.  Every rule that
+ *     reads the clip reads the env's: the frame cursors of reward modes 1..4 (mode 4's update interval from the clip's own dt), the wrap with its cycle count
+ *     against a "Loop: none" clip holding its last frame and ending, the root's cycle shift, the mocap frame of action modes 1, 2 and 4, the RSI draw and pose.
+ *   - the default assignment is clip (env_offset + env) % K, so it does not depend on the sharding.  Setting option 100 deals it afresh EVERY time
+ *     (a host copy and a wait for the stream): it overwrites an assignment written through DM_F_CLIP or drawn by DM_OPT_CLIP_MODE 1, so set the offset first.
+ *   - dm_batch_step, dm_batch_step_act, dm_batch_reset, early termination and the views below run kernels of their own (one-env and DM_OPT_PACKED, where the
+ *     four environments of a wavefront may follow four clips); dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches, as they do for action modes 3 and 4
+ *     (DM_OPT_HORIZON_TERMINATION included); a profiled step (option 101) is DM_EUNSUPPORTED.  The packed forms keep their promise: an environment's result
+ *     does not depend on its wave neighbours, so env e equals env e of a single-clip batch of its clip bit for bit (DM_OPT_PACKED 0 and 2; with 1, as rows 33..40).
+ *   - dm_batch_set_state with host pointers range-checks frame_idx[e] against the clip of env e (DM_EINVAL).
+ * A set of ONE clip gives a batch that behaves exactly as that clip's own (same kernels; DM_F_CLIP reads 0). */
+int dm_mocap_create_set(const dm_mocap* const* clips, int32_t n_clips, const double* weights, dm_mocap** out);
 void dm_mocap_destroy(dm_mocap* mc);
 
 /* flags for dm_batch_create */
@@ -244,6 +263,14 @@ enum {
 #define DM_PACKED_MAXCAND 32
 #define DM_MAX_STEP_QUEUE 256
 #define DM_MAX_PIPELINE 8
+/* DM_OPT_CLIP_MODE: an option of dm_batch_set_option like those of the enum above (whose ids end at 12), for multi-clip batches (dm_mocap_create_set).
+ * 0 (default, "fixed"): an environment keeps its clip (DM_F_CLIP).  1 ("episode"): every reset that sets the frame cursor — dm_batch_reset modes 0 and
+ * 1-with-hard, the auto-reset inside the step kernels, the termination launch's — first draws the episode's clip: u = the env's counter-based RNG at
+ * (seed, global env, episode, index 128) (index 0 is the frame, 1..35 and 64..97 the pose noise), clip = the first c with u < cdf[c]; then the frame is
+ * drawn as always, over that clip's n_frames, and DM_F_CLIP is stored with the cursors.  On a single-clip batch the option is accepted and changes
+ * nothing.  Other values: DM_EINVAL. */
+#define DM_OPT_CLIP_MODE 13
+#define DM_MAX_CLIPS 32      /* clips of a clip set (dm_mocap_create_set) */
 /* further option ids (diagnostics / tests; defaults are what the timed path uses):
  *   100 global id of env 0 of this batch (multi-GPU sharding: RNG streams are keyed by the global env id)
  *   101 per-stage shader-clock profile (k_step_prof + dm_batch_read_profile)
@@ -295,8 +322,12 @@ enum {
   DM_F_CYCLE = 16,      /* int32 [N] completed motion cycles since the episode started (reward mode 3) */
   DM_F_EPISODE_STEPS = 17, /* int32 [N] env steps since the episode began; maintained only while DM_OPT_FALL_BODIES or DM_OPT_MAX_EPISODE_STEPS
                               is on; readable and writable; dm_batch_reset zeroes it for the masked envs */
-  DM_F_DONE_REASON = 18 /* int32 [N] why the LAST step ended the episode (maintained like DM_F_EPISODE_STEPS): DM_DONE_STEP, or
+  DM_F_DONE_REASON = 18,/* int32 [N] why the LAST step ended the episode (maintained like DM_F_EPISODE_STEPS): DM_DONE_STEP, or
                            DM_DONE_FALL | DM_DONE_TIME_LIMIT (both may be set); 0 where the env is not done */
+  DM_F_CLIP = 19        /* int32 [N] the env's clip in the batch's clip set (0 on a single-clip batch).  Writable: values outside [0, n_clips) are DM_EINVAL (device
+                           pointers are read back for the check).  A write leaves the cursors alone — follow it with dm_batch_reset or dm_batch_set_state —
+                           except that a cursor naming a table row beyond the new clip is set to that clip's last frame (DM_F_FRAME_INIT always,
+                           DM_F_FRAME_IDX in reward modes 0, 1 and 3), so that a step taken in between stays inside the clip's rows */
 };
 int dm_batch_get(dm_batch* b, int32_t field, void* out, size_t bytes, int32_t ptr_kind);
 /* Read the truncation log (DM_OPT_TRUNCATION_LOG = C > 0).  Runs what is queued and joins the pipelined parts first, like dm_batch_join.  count [1]
@@ -368,7 +399,8 @@ int dm_batch_render(dm_batch* b, const double* qpos, const int32_t* env_ids, int
  * device env_ids are read back and range-checked on the host first (one copy and a wait for the stream), as dm_batch_render does.  Queued steps run and pipelined sub-batches join first, so the
  * features are those of the latest step (after an auto-reset: of the fresh episode's state, like a step's observation).  Read-only: the
  * call reads qpos, qvel, the two cursor fields and the reward mode and changes no batch state.  DM_EINVAL: n <= 0, n beyond the batch
- * without qpos, an env id out of range, a partial explicit state, env_ids with an explicit state, a bad ptr_kind. */
+ * without qpos, an env id out of range, a partial explicit state, env_ids with an explicit state, a bad ptr_kind.
+ * On a multi-clip batch (dm_mocap_create_set) n_frames is the length of the env's clip. */
 int dm_batch_state_features(dm_batch* b, const double* qpos, const double* qvel, const double* phase, const int32_t* env_ids, int32_t n,
                             double* out, int32_t ptr_kind);
 
@@ -405,7 +437,9 @@ int dm_batch_floor_contacts(dm_batch* b, const double* qpos, const int32_t* env_
  * its row is that state against the frame it was drawn at.
  * One launch on the batch's stream, one wave per state; argument checks, stream ordering (device env_ids are read back and
  * range-checked, nothing else waits), settle-first behaviour and ptr_kind as for dm_batch_state_features.  Read-only: changes no batch
- * state.  DM_EINVAL also when the mocap has no imitation table (dm_mocap_set_imitation was not called) and for a partial explicit state. */
+ * state.  DM_EINVAL also when the mocap has no imitation table (dm_mocap_set_imitation was not called) and for a partial explicit state.
+ * On a multi-clip batch (dm_mocap_create_set) a state is compared with the clip of env env_ids[i] (or i): explicit state i with the clip of env i (n <= the
+ * batch size), its frame local to that clip and range-checked against that clip's n_frames. */
 int dm_batch_imitation_terms(dm_batch* b, const double* qpos, const double* qvel, const int32_t* frame, const int32_t* cycle,
                              const int32_t* env_ids, int32_t n, double* out /* [n, DM_NTERMS] */, int32_t ptr_kind);
 

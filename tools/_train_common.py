@@ -8,8 +8,11 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
-    ap.add_argument("--motion", default="walk")
+    """--motion, --clip-weights, --clip-mode, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    ap.add_argument("--motion", default="walk", help="the clip to imitate, or a comma-separated list (walk,spinkick,kick): one policy on a set of clips, env e on clip e mod K")
+    ap.add_argument("--clip-weights", default=None, help="with a list of motions: comma-separated draw probabilities of --clip-mode episode (up to their sum; default uniform)")
+    ap.add_argument("--clip-mode", default="fixed", choices=["fixed", "episode"],
+                    help="with a list of motions: fixed (default) = an env keeps its clip; episode = every episode start draws the env's clip, as DeepMimic does")
     if reward_help:
         ap.add_argument("--reward", default="alive", help=reward_help)
     ap.add_argument("--obs-mode", default="dp_env_v3", choices=["dp_env_v3", "deepmimic"],
@@ -38,8 +41,24 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
         ap.add_argument("--frame-skip", default=None, help=frame_skip_help)
 
 
+def motions(args):
+    """--motion as DPVecEnv takes it: a clip name, or the list of a comma-separated value"""
+    names = [m for m in str(args.motion).split(",") if m]
+    return names if len(names) > 1 else names[0]
+
+
 def check_env_args(ap, args):
     """Refuse flag combinations that cannot work, with the parser's own error message."""
+    many = isinstance(motions(args), list)
+    if not many and (getattr(args, "clip_weights", None) or getattr(args, "clip_mode", "fixed") != "fixed"):
+        ap.error("--clip-weights and --clip-mode episode need a list of motions: --motion a,b,c")
+    if many and getattr(args, "clip_weights", None):
+        try:
+            w = [float(x) for x in args.clip_weights.split(",")]
+        except ValueError:
+            ap.error("--clip-weights: comma-separated numbers")
+        if len(w) != len(motions(args)):
+            ap.error("--clip-weights: one weight per motion (%d), got %d" % (len(motions(args)), len(w)))
     if getattr(args, "bootstrap_time_limit", False) and not args.max_episode_steps > 0:
         ap.error("--bootstrap-time-limit bootstraps the value where the time limit ends an episode: it needs --max-episode-steps M with M > 0")
     if getattr(args, "horizon_termination", False):
@@ -54,7 +73,9 @@ def check_env_args(ap, args):
 def env_kwargs(args):
     """The DPVecEnv arguments that the env flags set."""
     fs = getattr(args, "frame_skip", None)
-    return dict(motion=args.motion, reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
+    cw = getattr(args, "clip_weights", None)
+    return dict(motion=motions(args), clip_weights=[float(x) for x in cw.split(",")] if cw else None, clip_mode=getattr(args, "clip_mode", "fixed"),
+                reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
                 frame_skip=fs if fs in (None, "mocap") else int(fs),
                 fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps,
                 horizon_termination=bool(getattr(args, "horizon_termination", False)))
