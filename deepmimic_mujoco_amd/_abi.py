@@ -38,6 +38,9 @@ PACKED_MAXROWS, PACKED_MAXLIMROWS, PACKED_MAXCON, PACKED_MAXFRAME, PACKED_MAXCAN
 PACKED_MAXROWS_PER_STEP = 32
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_FRAME_IDX, F_FRAME_INIT, F_XIPOS, F_COM_Z, F_NCON, F_NEFC,
  F_CONTACT_GEOMS, F_STATUS, F_SOLVER_ITER, F_CTRL, F_EPISODE, F_CYCLE, F_EPISODE_STEPS, F_DONE_REASON, F_CLIP) = range(1, 20)
+# external pushes (dm_batch_push, dm_batch_set_push_schedule; perturb.py): the schedule's record {episode_seen, wait, left, body, count} and the force of the
+# env's current or last scheduled push (float64 in both libraries)
+F_PUSH_STATE, F_PUSH_FORCE = 20, 21
 
 # field -> (numpy dtype, per-env shape)
 FIELD_SPEC = {
@@ -47,6 +50,7 @@ FIELD_SPEC = {
     F_CONTACT_GEOMS: (np.int32, (MAXEFC, 2)), F_STATUS: (np.int32, ()), F_SOLVER_ITER: (np.int32, ()),
     F_CTRL: (np.float64, (NU,)), F_EPISODE: (np.int32, ()), F_CYCLE: (np.int32, ()),
     F_EPISODE_STEPS: (np.int32, ()), F_DONE_REASON: (np.int32, ()), F_CLIP: (np.int32, ()),
+    F_PUSH_STATE: (np.int32, (5,)), F_PUSH_FORCE: (np.float64, (3,)),
 }
 
 _dp = C.POINTER(C.c_double)
@@ -79,6 +83,14 @@ class RenderDesc(C.Structure):
         ("geom_rgb", (C.c_double * 3) * NGEOM), ("floor_rgb1", C.c_double * 3), ("floor_rgb2", C.c_double * 3), ("floor_square", C.c_double),
         ("sky_top", C.c_double * 3), ("sky_bottom", C.c_double * 3), ("light_dir", C.c_double * 3),
         ("ambient", C.c_double), ("headlight", C.c_double), ("diffuse", C.c_double),
+    ]
+
+
+class PushDesc(C.Structure):
+    """include/dmenv.h dm_push_desc (built by perturb.PushSchedule.desc)."""
+    _fields_ = [
+        ("bodies", C.c_uint32), ("wait_min", C.c_int32), ("wait_max", C.c_int32), ("duration_min", C.c_int32), ("duration_max", C.c_int32),
+        ("force_min", C.c_double), ("force_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
     ]
 
 
@@ -123,7 +135,7 @@ LIB_PATH = os.environ.get("DMENV_LIB") or os.path.join(_HERE, "csrc", "libdmenv.
 EXPORTS = ["dm_model_create", "dm_model_destroy", "dm_mocap_create", "dm_mocap_set_imitation", "dm_mocap_create_set", "dm_mocap_destroy", "dm_batch_create",
            "dm_batch_destroy", "dm_batch_set_stream", "dm_batch_set_option", "dm_batch_set_state", "dm_batch_reset",
            "dm_batch_step", "dm_batch_get_obs", "dm_batch_get", "dm_batch_set", "dm_batch_debug_forward",
-           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_imitation_terms", "dm_batch_truncations", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
+           "dm_batch_last_step_ms", "dm_batch_enable_timing", "dm_batch_read_profile", "dm_batch_sync", "dm_batch_join", "dm_policy_weight_count", "dm_policy_act", "dm_batch_step_act", "dm_batch_rollout", "dm_vf_param_count", "dm_vf_scratch_bytes", "dm_vf_fit_epoch", "dm_pg_param_count", "dm_pg_scratch_bytes", "dm_pg_losses", "dm_pg_fvp", "dm_batch_redo_total", "dm_batch_queue_stats", "dm_gae", "dm_episode_scan", "dm_rms_scratch_bytes", "dm_rms_update", "dm_disc_param_count", "dm_disc_scratch_bytes", "dm_disc_reward", "dm_disc_lossgrad", "dm_bc_scratch_bytes", "dm_bc_lossgrad", "dm_bc_fit", "dm_ppo_scratch_bytes", "dm_ppo_lossgrad", "dm_ppo_fit", "dm_batch_render", "dm_batch_state_features", "dm_batch_floor_contacts", "dm_batch_imitation_terms", "dm_batch_truncations", "dm_batch_push", "dm_batch_set_push_schedule", "dm_gae_boot", "dm_last_error", "dm_abi_version", "dm_real_bits",
            "dm_device_count"]
 _LIB = None
 
@@ -202,6 +214,11 @@ def load(dtype=64):
     L.dm_batch_truncations.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32]
     L.dm_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]
     L.dm_episode_scan.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]
+    # (entry points added under ABI version 9: a library built from an earlier tree of that version still loads, for same-box comparisons of two builds, and
+    #  then has no such attribute — a call fails loudly)
+    for name, at in (("dm_batch_push", [vp, vp, vp, vp, i32]), ("dm_batch_set_push_schedule", [vp, C.POINTER(PushDesc)])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = at
     if L.dm_abi_version() != ABI_VERSION:
         raise DmenvError("libdmenv.so ABI version %d != %d" % (L.dm_abi_version(), ABI_VERSION))
     if L.dm_real_bits() != dtype:

@@ -77,6 +77,7 @@ class Batch(object):
         self._auto = False                 # the per-step kernel chooser (enable_auto_packed) and its window
         self._auto_ctr = self._redo_last = self._redo_rows_last = self._calm_checks = 0
         self.auto_switches = None          # (None: this batch never had a chooser)
+        self.push_schedule = None          # the perturb.PushSchedule set_push_schedule last set (None: off)
         L = A.load(dtype)
         self.dtype = int(dtype)
         self._L = L
@@ -498,6 +499,26 @@ class Batch(object):
     def reset(self, mode=0, hard=1, mask=None):
         mp, k, _ = self._ptr(mask, np.uint8, (self.n,))
         A.check(self._L.dm_batch_reset(self._h, int(mode), int(hard), mp, k), self._L)
+
+    def push(self, body, impulse, mask=None):
+        """External pushes through dm_batch_push (one launch, now): env e's velocity takes the impulse[e] (N s, world frame) applied at the centre of mass of
+        model body body[e] (1..13), dqvel = M^-1 J_b^T p with the step's own mass matrix; body[e] == 0 or mask[e] == 0 leaves env e untouched, bit for bit.
+        body [n] int32, impulse [n,3] float64, mask [n] uint8: numpy arrays (a body outside 0..13 or a non-finite impulse raises) or tensors on the
+        batch's device (stream-ordered, not read back: such an env is left untouched).  Only qvel changes."""
+        n = self.n
+        bp, k0, _a = self._ptr(body, np.int32, (n,)); ip, k1, _b = self._ptr(impulse, np.float64, (n, 3)); mp, k2, _c = self._ptr(mask, np.uint8, (n,))
+        if len({k0, k1} | ({k2} if mask is not None else set())) != 1:
+            raise ValueError("push buffers must be all numpy arrays or all device tensors")
+        A.check(self._L.dm_batch_push(self._h, bp, ip, mp, k0), self._L)
+
+    def set_push_schedule(self, schedule):
+        """The random push schedule through dm_batch_set_push_schedule: a perturb.PushSchedule (or what PushSchedule.coerce takes); None: off.  While one
+        is set every per-step launch is preceded by the schedule's launch (k_push), and rollouts and queued steps run as step launches.  Setting it clears
+        the schedule's records (F_PUSH_STATE, F_PUSH_FORCE)."""
+        from .perturb import PushSchedule
+        schedule = PushSchedule.coerce(schedule)
+        A.check(self._L.dm_batch_set_push_schedule(self._h, None if schedule is None else C.byref(schedule.desc())), self._L)
+        self.push_schedule = schedule
 
     def get(self, field, out=None):
         dt, shp = A.FIELD_SPEC[field]

@@ -48,7 +48,11 @@ struct dm_batch {
   // the clip set (dm_mocap_create_set; step_rules.h ClipArgs): n_clips > 1 makes the batch multi-clip — its launches are the clip kernels (kernels_clips.hip,
   // kernels_packed_clips.hip).  d_clip is DM_F_CLIP (all 0 on a single-clip batch); clip_frames: the clips' lengths, for the host's range checks
   int n_clips = 1, clip_mode = 0; int* d_clip = nullptr; dm::ClipRec<Real>* d_clip_rec = nullptr; std::vector<int> clip_frames;
+  // external pushes (dm_batch_push, dm_batch_set_push_schedule; push_kernel.h): DM_F_PUSH_STATE and DM_F_PUSH_FORCE, the schedule (push.bodies == 0: off — no
+  // k_push launch) and the model descriptor's timestep in float64, from which a held force's impulse F h is formed
+  int* d_push_state = nullptr; double* d_push_force = nullptr; dm_push_desc push{}; double timestep64 = 0;
 };
+inline bool push_on(const dm_batch* b) { return b->push.bodies != 0u; }
 inline bool multi_clip(const dm_batch* b) { return b->n_clips > 1; }
 inline dm::ClipArgs<Real> clip_args(const dm_batch* b) { return dm::ClipArgs<Real>{b->d_clip, b->d_clip_rec, b->n_clips, b->clip_mode}; }
 // the batch's DM_F_CLIP on the host (stream-ordered copy and a wait): the per-env range checks of a multi-clip batch

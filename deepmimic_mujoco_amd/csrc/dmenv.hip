@@ -20,6 +20,7 @@ using namespace dm;
 #include "state_kernel.h"
 #include "term_kernel.h"
 #include "terms_kernel.h"
+#include "push_kernel.h"
 static_assert(DM_NSTATE == dmsf::NSTATE, "include/dmenv.h documents the feature row: keep it in step with state_features.h");
 static_assert(DM_NTERMS == IMIT_NTERMS, "include/dmenv.h documents the terms row: keep it in step with env_step.h imitation_reward");
 static_assert((DM_PACKED_MAXROWS == SLOT_MAXROWS || DM_SLOT_MAXROWS != 40 /* an experiment build */) && DM_PACKED_MAXROWS_PER_STEP == 2 * SW && DM_PACKED_MAXLIMROWS == SLOT_MAXLIMROWS && DM_PACKED_MAXCON == SLOT_MAXCON && DM_PACKED_MAXFRAME == SLOT_MAXFRAME &&
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64) void k_debug_forward(const DevModel<Real>* __re
 // ============================================ host side ====================================================
 thread_local std::string g_err;
 
-struct dm_model { DevModel<Real> h; };
+struct dm_model { DevModel<Real> h; double timestep64; /* the descriptor's, whatever the arithmetic type (a held push's impulse F h: push_kernel.h) */ };
 // a clip of a clip set (dm_mocap_create_set): its rows in the concatenated tables, its own dt and imitation parameters 13..15, its draw cdf
 struct ClipInfo { int row0, n_frames; double dt, loop, shift_x, shift_y, cdf; };
 struct dm_mocap { std::vector<double> cfg, vel, imit_table, imit_params; int n_frames; double dt; std::vector<ClipInfo> clips; /* empty: a single clip */ };
@@ -231,6 +232,7 @@ extern "C" int dm_model_create(const dm_model_desc* d, dm_model** out) {
   std::string err;
   const int rc = dm::build_dev_model(d, &m->h, &err);
   if (rc != DM_OK) { delete m; return fail(rc, err); }
+  m->timestep64 = d->timestep;
   *out = m;
   return DM_OK;
 }
@@ -299,7 +301,7 @@ extern "C" void dm_batch_destroy(dm_batch* b) {
   if (b->ev_in) hipEventDestroy(b->ev_in);
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_clip, b->d_clip_rec, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_clip, b->d_clip_rec, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->d_push_state, b->d_push_force};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
@@ -317,7 +319,7 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   HIPCHK(hipSetDevice(device));
   dm_batch* b = new (std::nothrow) dm_batch();
   if (!b) return fail(DM_ENOMEM, "dm_batch_create: out of memory");
-  b->n = n; b->device = device;
+  b->n = n; b->device = device; b->timestep64 = m->timestep64;
   hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete b; return fail(DM_EHIP, "hipStreamCreate failed"); }
   b->own_stream = true;
@@ -349,6 +351,7 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   if (sizeof(Real) != sizeof(Ext)) A(b->d_cvt, (size_t)n * NB * 3);   // largest Real field per env: xipos (42)
   A(b->d_clip, n);                                                    // DM_F_CLIP and the clip records: the last allocations, so that a single-clip batch's other arrays lie where they always lay
   if (!mc->clips.empty()) A(b->d_clip_rec, mc->clips.size());
+  A(b->d_push_state, (size_t)n * 5); A(b->d_push_force, (size_t)n * 3);   // DM_F_PUSH_STATE, DM_F_PUSH_FORCE (after every older allocation, like the clip arrays)
 #undef A
   if (!ok) { dm_batch_destroy(b); return fail(DM_ENOMEM, "dm_batch_create: hipMalloc failed"); }
   ok = hipMemcpy(b->d_model, &hm, sizeof hm, hipMemcpyHostToDevice) == hipSuccess;
@@ -378,6 +381,8 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   std::vector<Real> q0((size_t)n * NQ);
   for (int e2 = 0; e2 < n; e2++) for (int k = 0; k < NQ; k++) q0[(size_t)e2 * NQ + k] = hm.qpos0[k];
   ok = ok && hipMemcpy(b->B.qpos, q0.data(), q0.size() * sizeof(Real), hipMemcpyHostToDevice) == hipSuccess;
+  { std::vector<int> ps((size_t)n * 5, 0); for (int e2 = 0; e2 < n; e2++) ps[(size_t)e2 * 5] = -1;       // DM_F_PUSH_STATE: no episode seen yet
+    ok = ok && hipMemcpy(b->d_push_state, ps.data(), ps.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess; }
   if (!ok) { dm_batch_destroy(b); return fail(DM_EHIP, "dm_batch_create: upload failed"); }
   b->B.mocap_cfg = b->d_cfg; b->B.mocap_vel = b->d_vel; b->B.mocap_dt = mc->dt; b->B.n_frames = mc->n_frames; b->B.n_envs = n; b->B.env_offset = 0;
   b->B.reward_mode = 0; b->B.autoreset = 0; b->B.action_mode = 0; b->B.seed = 0; b->B.diag = 1;
@@ -548,9 +553,10 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
   // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches;
-  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set; and those of a multi-clip batch, with or without it)
+  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set; those of a multi-clip batch, with or without it; and those
+  //  of a batch with a push schedule set, whose k_push precedes every step launch)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && !multi_clip(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && !multi_clip(b) && !push_on(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -723,12 +729,21 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
       b->redo_mode = mode; b->redo_phase = 0;
     }
   }
+  // the push schedule's launch ahead of a part's step launches, on the part's stream (k_push: push_kernel.h); off: nothing is launched
+  auto push = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count) {
+    if (!push_on(b)) return;
+    const dm_push_desc& d = b->push;
+    const PushArgs P{b->d_push_state, b->d_push_force, d.bodies, d.wait_min, d.wait_max, d.duration_min, d.duration_max, d.force_min, d.force_max, d.z_min, d.z_max,
+                     b->timestep64 * (double)nsub, lo, count};
+    hipLaunchKernelGGL(k_push, dim3(count), dim3(64), 0, st, b->d_model, Bp, P);
+  };
   // The launches of one part [lo, lo + count) of the batch (a pipelined sub-batch, or the whole batch) on stream `st`, with the descriptor Bp.  Packed: the
   // packed kernel counts the environments beyond its capacities into the first counter of `pair` (this call's phase), the redo launch steps them one
   // per wave and clears the other one for the next call.
   auto launch_part = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count, int* pair, const dmp::PolicyArgs* pa) {
     constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
     const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
+    push(st, Bp, lo, count);
     if (clips) {
       if (packed) {
         const dim3 grid((count + SLOTS - 1) / SLOTS);
@@ -756,7 +771,7 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   if (b->prof && packed) {
     HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
     launch_part(b->stream, b->B, 0, b->n, b->B.redo_count, nullptr);
-  } else if (b->prof) { hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof); terminate(b->stream, b->B, 0, b->n); }
+  } else if (b->prof) { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof); terminate(b->stream, b->B, 0, b->n); }
   else if (piped) {
     // Sub-batch h's launch of THIS call depends on its own launch of the previous call (stream order on ps[h]) and on the
     // caller's inputs (ev_in), not on the other sub-batches: while the last, cheap workgroups of one sub-batch drain, the
@@ -785,8 +800,8 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
     // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of redo counters is clean — pair 0's
     //  two are cleared above once if a pipelined step used them before)
     launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, fused);
-  } else if (clips) { hipLaunchKernelGGL(KC.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, ca); terminate(b->stream, b->B, 0, b->n); }
-  else { hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
+  } else if (clips) { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(KC.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, ca); terminate(b->stream, b->B, 0, b->n); }
+  else { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
   HIPCHK(hipGetLastError());
   for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
   if (packed) b->redo_phase ^= 1;
@@ -855,9 +870,9 @@ extern "C" int dm_batch_get_obs(dm_batch* b, double* obs, int32_t kind) {
 }
 
 // field -> device array, element count, and whether its elements are `Real` (float64 at the ABI) or int32
-static int field_ptr(dm_batch* b, int field, void** p, size_t* count, bool* is_real) {
+static int field_ptr(dm_batch* b, int field, void** p, size_t* count, bool* is_real, size_t* esize) {
   const size_t n = b->n;
-  *is_real = false;
+  *is_real = false; *esize = 0;
   switch (field) {
     case DM_F_QPOS: *p = b->B.qpos; *count = n * NQ; *is_real = true; break;
     case DM_F_QVEL: *p = b->B.qvel; *count = n * NV; *is_real = true; break;
@@ -878,17 +893,20 @@ static int field_ptr(dm_batch* b, int field, void** p, size_t* count, bool* is_r
     case DM_F_EPISODE_STEPS: *p = b->d_ep_steps; *count = n; break;
     case DM_F_DONE_REASON: *p = b->d_done_reason; *count = n; break;
     case DM_F_CLIP: *p = b->d_clip; *count = n; break;
+    case DM_F_PUSH_STATE: *p = b->d_push_state; *count = n * 5; break;
+    case DM_F_PUSH_FORCE: *p = b->d_push_force; *count = n * 3; *esize = sizeof(double); break;   // float64 on the device in both libraries: copied as it is
     default: return fail(DM_EINVAL, "unknown field");
   }
+  if (!*esize) *esize = *is_real ? sizeof(Ext) : 4;      // bytes per element at the ABI
   return DM_OK;
 }
 extern "C" int dm_batch_get(dm_batch* b, int32_t field, void* out, size_t bytes, int32_t kind) {
   if (!b || !out) return fail(DM_EINVAL, "dm_batch_get: null argument");
   HIPCHK(hipSetDevice(b->device));
   if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  void* p; size_t cnt; bool real; int rc;
-  if ((rc = field_ptr(b, field, &p, &cnt, &real))) return rc;
-  const size_t need = cnt * (real ? sizeof(Ext) : 4);
+  void* p; size_t cnt, esz; bool real; int rc;
+  if ((rc = field_ptr(b, field, &p, &cnt, &real, &esz))) return rc;
+  const size_t need = cnt * esz;
   if (bytes != need) return fail(DM_EINVAL, "dm_batch_get: buffer size does not match the field");
   if (real && sizeof(Real) != sizeof(Ext)) {       // float32 build: widen on the device, then copy
     Ext* dst = kind == DM_PTR_DEVICE ? (Ext*)out : b->d_cvt;
@@ -903,9 +921,9 @@ extern "C" int dm_batch_set(dm_batch* b, int32_t field, const void* in, size_t b
   if (!b || !in) return fail(DM_EINVAL, "dm_batch_set: null argument");
   HIPCHK(hipSetDevice(b->device));
   if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-  void* p; size_t cnt; bool real; int rc;
-  if ((rc = field_ptr(b, field, &p, &cnt, &real))) return rc;
-  const size_t need = cnt * (real ? sizeof(Ext) : 4);
+  void* p; size_t cnt, esz; bool real; int rc;
+  if ((rc = field_ptr(b, field, &p, &cnt, &real, &esz))) return rc;
+  const size_t need = cnt * esz;
   if (bytes != need) return fail(DM_EINVAL, "dm_batch_set: buffer size does not match the field");
   if (field == DM_F_XIPOS || field == DM_F_COM_Z || field == DM_F_NCON || field == DM_F_NEFC || field == DM_F_CONTACT_GEOMS || field == DM_F_SOLVER_ITER)
     return fail(DM_EINVAL, "dm_batch_set: derived field is read-only");
@@ -990,6 +1008,48 @@ extern "C" int dm_batch_truncations(dm_batch* b, int32_t* count, int32_t* index,
   if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
   return DM_OK;
 }
+// ---- external pushes (include/dmenv.h; push_kernel.h, kernels_push.hip) ---------------------------------------------------------------------------------
+static bool finite64(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
+extern "C" int dm_batch_push(dm_batch* b, const int32_t* body, const double* impulse, const uint8_t* mask, int32_t kind) {
+  if (!b || !body || !impulse || (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE)) return fail(DM_EINVAL, "dm_batch_push: null batch, body or impulse, or bad ptr_kind");
+  if (kind == DM_PTR_HOST)
+    for (int e = 0; e < b->n; e++) {
+      if (body[e] < 0 || body[e] >= NB) return fail(DM_EINVAL, "dm_batch_push: body outside 0..13");
+      for (int k = 0; k < 3; k++) if (!finite64(impulse[(size_t)e * 3 + k])) return fail(DM_EINVAL, "dm_batch_push: non-finite impulse");
+    }
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  const void *bd, *ip, *mk; int rc;
+  if ((rc = stage_in(b, b->d_fidx_in, body, (size_t)b->n * 4, kind, &bd))) return rc;
+  if ((rc = stage_in(b, b->d_qvel_in, impulse, (size_t)b->n * 3 * 8, kind, &ip))) return rc;
+  if ((rc = stage_in(b, b->d_mask, mask, (size_t)b->n, kind, &mk))) return rc;
+  hipLaunchKernelGGL(k_push_now, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (const int*)bd, (const double*)ip, (const unsigned char*)mk);
+  HIPCHK(hipGetLastError());
+  if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
+  return DM_OK;
+}
+extern "C" int dm_batch_set_push_schedule(dm_batch* b, const dm_push_desc* d) {
+  dm_push_desc p{};
+  if (d && d->bodies != 0u) {      // (the description is judged before `b` is looked at: a bad one can then be shown to be refused without a device)
+    p = *d;
+    if (p.bodies & ~0x3ffeu) return fail(DM_EINVAL, "dm_batch_set_push_schedule: bodies is a mask over model bodies 1..13 (bits 1..13)");
+    if (p.wait_min < 0 || p.wait_max < p.wait_min) return fail(DM_EINVAL, "dm_batch_set_push_schedule: 0 <= wait_min <= wait_max");
+    if (p.duration_min < 1 || p.duration_max < p.duration_min) return fail(DM_EINVAL, "dm_batch_set_push_schedule: 1 <= duration_min <= duration_max");
+    if (!finite64(p.force_min) || !finite64(p.force_max) || !(p.force_min >= 0) || !(p.force_max >= p.force_min)) return fail(DM_EINVAL, "dm_batch_set_push_schedule: 0 <= force_min <= force_max, finite");
+    if (!(p.z_min >= -1) || !(p.z_max >= p.z_min) || !(p.z_max <= 1)) return fail(DM_EINVAL, "dm_batch_set_push_schedule: -1 <= z_min <= z_max <= 1");
+  }
+  if (!b) return fail(DM_EINVAL, "dm_batch_set_push_schedule: null batch");
+  HIPCHK(hipSetDevice(b->device));
+  if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
+  std::vector<int> ps((size_t)b->n * 5, 0);
+  for (int e = 0; e < b->n; e++) ps[(size_t)e * 5] = -1;
+  HIPCHK(hipMemcpyAsync(b->d_push_state, ps.data(), ps.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemsetAsync(b->d_push_force, 0, (size_t)b->n * 3 * sizeof(double), b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));              // (the host vector is read until the copy is done)
+  b->push = p;
+  return DM_OK;
+}
+
 extern "C" int dm_batch_join(dm_batch* b) {
   if (!b) return fail(DM_EINVAL, "null batch");
   HIPCHK(hipSetDevice(b->device));

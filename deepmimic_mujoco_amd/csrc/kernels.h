@@ -12,6 +12,8 @@
 //   kernels_clips.hip / kernels_packed_clips.hip   the kernels of MULTI-CLIP batches (dm_mocap_create_set: one clip per env, step_rules.h ClipArgs): the one-env and
 //                       the packed step kernels, and the clip forms of k_reset, k_terminate, k_state_features and k_imitation_terms; units of their own with the
 //                       options of dmenv.hip / kernels_packed.hip.  They pick the stable-PD instantiation by the action mode at run time.
+//   kernels_push.hip    external pushes (push_kernel.h): k_push_now behind dm_batch_push and k_push, the random schedule's launch ahead of every per-step launch;
+//                       a unit of its own with dmenv.hip's options, launched only where a push is asked for
 //   kernels_packed.hip  the four-environments-per-wavefront per-step kernels (slot_kernel.h / slot_step.h): compiled with their own backend options
 //                       (csrc/build.py PACKED_FLAGS — one wave per SIMD with the whole register file wants a scheduler that goes for
 //                       instruction-level parallelism, the two-waves-per-SIMD one-env kernels do not: profiles/r04_ab_kernel_variants.md)
@@ -113,3 +115,8 @@ __global__ void k_step_redo_clips(const dm::DevModel<Real>* __restrict__ Mp, dm:
 __global__ void k_clip_clamp(dm::Batch<Real> B, dm::ClipArgs<Real> ca);
 __global__ void k_reset_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, int mode, int hard, const unsigned char* __restrict__ mask, dm::ClipArgs<Real> ca);
 __global__ void k_terminate_clips(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, TermArgs T, Ext* __restrict__ obs, unsigned char* __restrict__ done, dm::ClipArgs<Real> ca);
+// ---- kernels_push.hip: external pushes (push_kernel.h), one wave per environment -----------------------------------------------------------------------
+namespace dm { struct PushArgs; }
+__global__ void k_push_now(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const int* __restrict__ body, const double* __restrict__ impulse,
+                           const unsigned char* __restrict__ mask);
+__global__ void k_push(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, dm::PushArgs P);

@@ -238,6 +238,13 @@ class DPEnv(object):
     def viewer_setup(self):
         pass
 
+    def push(self, body, impulse):
+        """An external push, now (Batch.push): the impulse (3 numbers, N s, world frame) at the centre of mass of `body` — a body's name or its model id
+        1..13 — changes qvel by M^-1 J_b^T p.  A force F held over one `step` is the impulse F * frame_skip * model.opt.timestep before it."""
+        if isinstance(body, str):
+            body = int(fall_body_mask([body])).bit_length() - 1
+        self._batch.push(np.array([int(body)], dtype=np.int32), np.asarray(impulse, dtype=np.float64).reshape(1, 3))
+
     def _sync_frame_idx(self):
         self._batch.set(A.F_FRAME_IDX, np.array([max(self.idx_curr, 0)], dtype=np.int32))
         self._batch.set(A.F_FRAME_INIT, np.array([self.idx_init], dtype=np.int32))
@@ -413,8 +420,12 @@ class DPVecEnv(object):
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
                  step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False,
-                 horizon_termination=False, clip_weights=None, clip_mode="fixed"):
-        """motion: a clip, or a LIST of clips (names / files): the batch is then multi-clip (clips.ClipSet, dm_mocap_create_set) — env e imitates clip
+                 horizon_termination=False, clip_weights=None, clip_mode="fixed", perturb=None):
+        """perturb: external pushes on a random schedule (perturb.PushSchedule, a dict of its arguments, or the trainers' "bodies=...,force=a:b,..." string;
+        None: off) — a random force on a random body of the set for a few env steps, again and again over every episode (DeepMimic's perturbations).  While
+        it is on, one more launch precedes every step launch; horizon launches and the step queue run as step launches.  `push` applies scripted impulses
+        at any time, `push_state()` reads the schedule's records.
+        motion: a clip, or a LIST of clips (names / files): the batch is then multi-clip (clips.ClipSet, dm_mocap_create_set) — env e imitates clip
         (env_offset + e) % K (`clip_ids`, `set_clip_ids`) and, with clip_mode="episode", every reset that sets the frame cursor first draws the episode's clip
         with the probabilities clip_weights (None: uniform).  `mocap` / `mocap_dt` / `mocap_data_len` are then the FIRST clip's, `clip_set` the whole set, and
         frame_skip="mocap" (the imitation reward's default) is taken from the first clip's dt for every env: clips of another dt (walk 0.0333 s, spinkick
@@ -551,6 +562,12 @@ class DPVecEnv(object):
             b.set_option(A.OPT_TRUNCATION_LOG, int(truncation_log))
         if self.horizon_termination:
             b.set_option(A.OPT_HORIZON_TERMINATION, 1)
+        self.perturb = None
+        if perturb is not None:
+            from .perturb import PushSchedule
+            self.perturb = PushSchedule.coerce(perturb)
+            if self.perturb is not None:
+                b.set_push_schedule(self.perturb)
         rowless = not (contacts or limits)          # no constraint rows: every wave costs the same, the packed kernel wins at any batch size
         auto = packed is None and batch_factory is None and (self.num_envs >= PACKED_FROM_ENVS or (rowless and self.num_envs >= 256)) and dtype == 64
         # a horizon launch (Batch.rollout, rollout.SegmentCollector) may use the packed kernel at ANY batch size: there a wave does not wait
@@ -558,7 +575,7 @@ class DPVecEnv(object):
         # (with early termination on there is no horizon launch unless `horizon_termination`: a horizon is step launches, for which the per-step choice above holds)
         self.horizon_packed_ok = (packed is None and batch_factory is None and self.num_envs >= 256 and dtype == 64
                                   and (self.horizon_termination or not (self.fall_body_mask or self.max_episode_steps))
-                                  and not many)      # (a multi-clip batch's horizons are step launches too)
+                                  and not many and perturb is None)      # (a multi-clip batch's horizons are step launches too, and so are those under a push schedule)
         if packed or auto:
             b.set_option(A.OPT_PACKED, 2 if (packed is not True and packed == 2) else 1)     # (packed=2: per-step launches with the three-set code, see the docstring)
         if auto:
@@ -593,6 +610,16 @@ class DPVecEnv(object):
     def set_clip_ids(self, ids):
         """Assign the environments' clips (values outside the set raise).  The frame cursors are left alone: follow with `reset` or `batch.set_state`."""
         self._batch.set(A.F_CLIP, ids)
+
+    def push(self, body, impulse, mask=None):
+        """Scripted pushes, now (Batch.push): env e's velocity takes impulse[e] (N s, world frame) at the centre of mass of model body body[e] (1..13; 0: none);
+        body [N] int32, impulse [N,3] float64, mask [N] uint8 or None — numpy arrays or device tensors.  A force F held over one env step is the impulse
+        F * frame_skip * model.opt.timestep before that step."""
+        self._batch.push(body, impulse, mask)
+
+    def push_state(self):
+        """(state int32 [N,5] {episode_seen, wait, left, body, count}, force float64 [N,3]) of the push schedule (`perturb`): F_PUSH_STATE and F_PUSH_FORCE"""
+        return self._batch.get(A.F_PUSH_STATE), self._batch.get(A.F_PUSH_FORCE)
 
     def done_reason(self, out=None):
         """int32 [N]: why the last step ended each environment's episode — bits termination.DONE_STEP (COM band, clip end), DONE_FALL, DONE_TIME_LIMIT; 0

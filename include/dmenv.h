@@ -294,6 +294,48 @@ int dm_batch_set_state(dm_batch* b, const double* qpos, const double* qvel, cons
  * `hard` is nonzero (sim.reset() semantics); reset_model_init() called on its own keeps them. */
 int dm_batch_reset(dm_batch* b, int32_t mode, int32_t hard, const uint8_t* mask, int32_t ptr_kind);
 
+/* EXTERNAL PUSHES (DeepMimic's perturbations, code.md:949-952 Perturb / PerturbManager).  Additive: the ABI version stays 9 and the options enum is untouched.
+ * A push is an IMPULSE p (N s, world frame) at the centre of mass xipos_b of model body b (1..13), at the state the env is in:
+ *     dqvel = M(q)^-1 J_b(q)^T p
+ * M is the step's own mass matrix, armature included; J_b the 3 x 34 translational Jacobian of the point xipos_b: for hinge dof d of a body on the chain
+ * root -> b the column axis_world_d x (xipos_b - xpos_body(d)) (this model's joints sit at their body's frame origin), the identity columns for the root's
+ * translation, xmat_root[:, k] x (xipos_b - xpos_root) for the root's rotation (body-frame angular velocity, MuJoCo's free joint), zero off the chain.
+ * Only qvel changes: qpos, time, qacc_warmstart, the cursors and the parked kinematics (position-only: dm_batch_set(DM_F_QVEL) does not invalidate them
+ * either) are untouched.  Contacts and joint limits are ignored by the impulse; the next step's constraint solve meets the new velocity.  A zero impulse
+ * changes nothing, bit for bit.
+ * A FORCE F held over an env step is applied as the single impulse F h BEFORE that step, h = timestep * n_substeps: the product F h is formed in float64
+ * from the model descriptor's timestep and then converted to the library's arithmetic type.  This is the first-order splitting of MuJoCo's xfrc_applied:
+ * exact for one unconstrained Euler step, not identical under RK4, whose stages would each see the force.
+ *
+ * dm_batch_push — the scripted form: one launch (k_push_now, one wave per env) now, on the batch's stream; runs what is queued and joins the pipelined
+ * parts first.  body [N] int32, impulse [N,3] float64, mask [N] or NULL (every env).  body[e] == 0 or mask[e] == 0 leaves env e untouched, bit for bit.
+ * Host pointers: a body outside 0..13 or a non-finite impulse is DM_EINVAL (nothing is launched), and the call waits for the launch.  Device arrays are not
+ * read back: an out-of-range body or a non-finite impulse leaves its env untouched. */
+int dm_batch_push(dm_batch* b, const int32_t* body, const double* impulse, const uint8_t* mask, int32_t ptr_kind);
+/* The RANDOM SCHEDULE.  While one is set, every per-step launch of dm_batch_step — every layout (one env or four per wave), dm_batch_step_act, host or device
+ * pointers, a profiled step — is PRECEDED by one launch, k_push (one wave per env), on the same stream (a pipelined part's on that part's stream over its env
+ * range).  dm_batch_rollout and DM_OPT_STEP_QUEUE then issue step launches (dm_batch_queue_stats stays 0), with DM_OPT_HORIZON_TERMINATION too, as for action
+ * modes 3 and 4.  Off (the default), nothing is launched and nothing changes.
+ * For env e with ep = DM_F_EPISODE[e] (every reset path advances it) and u_k(j) = the env's counter-based RNG at (seed, env_offset + e, ep, 256 + 8 j + k)
+ * (indices 0, 1..35, 64..97 and 128 are the resets'), on the record DM_F_PUSH_STATE[e] = {episode_seen, wait, left, body, count}:
+ *   1. episode_seen != ep:  episode_seen = ep, count = 0, left = 0, wait = wait_min + min(floor(u_0(0) (wait_max - wait_min + 1)), wait_max - wait_min)
+ *   2. left == 0 and wait > 0:  wait -= 1; done
+ *   3. left == 0 and wait == 0:  push j = count begins: left = the same integer draw from u_1(j) over the duration range; body = the
+ *      floor(u_2(j) popcount(bodies))-th set bit of `bodies`, ascending, clamped; |F| = force_min + u_3(j) (force_max - force_min); phi = 2 pi u_4(j);
+ *      z = z_min + u_5(j) (z_max - z_min); F = |F| (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), all in float64, stored in DM_F_PUSH_FORCE[e]; count += 1
+ *   4. left > 0:  the impulse F h on `body` is applied; left -= 1; if that makes it 0, wait is drawn from u_0(count)
+ * Steps 1, 3 and 4 may follow one another in one launch.  The streams are keyed by the global env id: sharding (option 100) does not change them. */
+typedef struct {
+  uint32_t bodies;                       /* bit b = 1..13, as DM_OPT_FALL_BODIES; other bits: DM_EINVAL */
+  int32_t wait_min, wait_max;            /* env steps between pushes, 0 <= min <= max */
+  int32_t duration_min, duration_max;    /* env steps a force is held, 1 <= min <= max */
+  double force_min, force_max;           /* N, 0 <= min <= max, finite */
+  double z_min, z_max;                   /* the direction's vertical component, -1 <= min <= max <= 1 (0, 0 = horizontal) */
+} dm_push_desc;
+/* NULL or bodies == 0: off.  Setting it (on or off) runs what is queued, joins the pipelined parts and clears every env's record to episode_seen = -1
+ * (the other entries and DM_F_PUSH_FORCE to 0).  DM_EINVAL: a bound outside the ranges above. */
+int dm_batch_set_push_schedule(dm_batch* b, const dm_push_desc* desc);
+
 /* Replaces: DPEnv.step(action) (src/dp_env_v3.py:106-132) = do_simulation(action, n) [ctrl <- action; n x mj_step]
  * + _get_obs() + reward + is_done(), for every environment of the batch in one launch.
  * action [N,28], obs [N,56], reward [N] float64; done [N] uint8. */
@@ -324,10 +366,12 @@ enum {
                               is on; readable and writable; dm_batch_reset zeroes it for the masked envs */
   DM_F_DONE_REASON = 18,/* int32 [N] why the LAST step ended the episode (maintained like DM_F_EPISODE_STEPS): DM_DONE_STEP, or
                            DM_DONE_FALL | DM_DONE_TIME_LIMIT (both may be set); 0 where the env is not done */
-  DM_F_CLIP = 19        /* int32 [N] the env's clip in the batch's clip set (0 on a single-clip batch).  Writable: values outside [0, n_clips) are DM_EINVAL (device
+  DM_F_CLIP = 19,       /* int32 [N] the env's clip in the batch's clip set (0 on a single-clip batch).  Writable: values outside [0, n_clips) are DM_EINVAL (device
                            pointers are read back for the check).  A write leaves the cursors alone — follow it with dm_batch_reset or dm_batch_set_state —
                            except that a cursor naming a table row beyond the new clip is set to that clip's last frame (DM_F_FRAME_INIT always,
                            DM_F_FRAME_IDX in reward modes 0, 1 and 3), so that a step taken in between stays inside the clip's rows */
+  DM_F_PUSH_STATE = 20, /* int32 [N,5] the push schedule's record {episode_seen, wait, left, body, count} (dm_batch_set_push_schedule); readable and writable */
+  DM_F_PUSH_FORCE = 21  /* double [N,3] the force (N, world frame) of the env's current or last scheduled push; float64 in both libraries; readable and writable */
 };
 int dm_batch_get(dm_batch* b, int32_t field, void* out, size_t bytes, int32_t ptr_kind);
 /* Read the truncation log (DM_OPT_TRUNCATION_LOG = C > 0).  Runs what is queued and joins the pipelined parts first, like dm_batch_join.  count [1]

@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --clip-weights, --clip-mode, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --clip-weights, --clip-mode, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms, --perturb and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk", help="the clip to imitate, or a comma-separated list (walk,spinkick,kick): one policy on a set of clips, env e on clip e mod K")
     ap.add_argument("--clip-weights", default=None, help="with a list of motions: comma-separated draw probabilities of --clip-mode episode (up to their sum; default uniform)")
     ap.add_argument("--clip-mode", default="fixed", choices=["fixed", "episode"],
@@ -35,6 +35,10 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
     ap.add_argument("--log-reward-terms", action="store_true",
                     help="--reward imitation: log the reward's five errors (ErrPose, ErrVel, ErrEndEff, ErrRoot, ErrCom) of the states each segment ends in, "
                          "from one more launch per segment")
+    ap.add_argument("--perturb", default=None, metavar="bodies=...,force=a:b,duration=a:b,wait=a:b[,z=a:b]",
+                    help="DeepMimic's external pushes on a random schedule: a force of a..b newtons on a random body of the set (a set name of --fall-contact, or body names / "
+                         "ids joined by +), held for duration a..b env steps, a..b env steps after the last one; z: range of the direction's vertical component "
+                         "(default horizontal).  Works with --task evaluate too: a checkpoint's episode length and return under pushes")
     if autoreset_help:
         ap.add_argument("--autoreset", default="init", help=autoreset_help)
     if frame_skip_help:
@@ -66,6 +70,12 @@ def check_env_args(ap, args):
             ap.error("--horizon-termination runs early termination inside the horizon launch: it needs --fall-contact or --max-episode-steps")
         if args.action_mode in ("spd-target", "spd-mocap") or args.obs_mode == "deepmimic":
             ap.error("--horizon-termination: --action-mode spd-* and --obs-mode deepmimic have no horizon launch")
+    if getattr(args, "perturb", None):
+        from deepmimic_mujoco_amd.perturb import PushSchedule
+        try:
+            PushSchedule.parse(args.perturb)
+        except ValueError as e:
+            ap.error("--perturb: %s" % e)
     if getattr(args, "log_reward_terms", False) and getattr(args, "reward", None) != "imitation":
         ap.error("--log-reward-terms takes the imitation reward apart: it needs --reward imitation")
 
@@ -78,7 +88,7 @@ def env_kwargs(args):
                 reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
                 frame_skip=fs if fs in (None, "mocap") else int(fs),
                 fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps,
-                horizon_termination=bool(getattr(args, "horizon_termination", False)))
+                horizon_termination=bool(getattr(args, "horizon_termination", False)), perturb=getattr(args, "perturb", None))
 
 
 def init_device(dist_backend):
