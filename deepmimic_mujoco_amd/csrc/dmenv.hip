@@ -294,19 +294,17 @@ template <class T> static hipError_t dalloc(T** p, size_t n) { hipError_t e = hi
 extern "C" void dm_batch_destroy(dm_batch* b) {
   if (!b) return;
   hipSetDevice(b->device);
-  b->q.clear();          // queued steps are dropped, not run: their buffers belong to the caller and may be gone
-  pipe_join(b);
+  b->queue.q.clear();    // queued steps are dropped, not run: their buffers belong to the caller and may be gone
+  b->pipe.join(b->stream);
   if (b->stream) hipStreamSynchronize(b->stream);
-  for (int h = 0; h < DM_MAX_PIPELINE; h++) { if (b->ps[h]) hipStreamDestroy(b->ps[h]); if (b->ev_done[h]) hipEventDestroy(b->ev_done[h]); }
-  if (b->ev_in) hipEventDestroy(b->ev_in);
+  b->pipe.destroy(); b->trunc.release();
   void* ptrs[] = {b->d_model, b->B.qpos, b->B.qvel, b->B.qws, b->B.time, b->B.ctrl, b->B.xipos, b->B.comz, b->B.frame_idx, b->B.frame_init,
                   b->B.ncon, b->B.nefc, b->B.cong, b->B.status, b->B.solver_iter, b->B.episode, b->d_cfg, b->d_vel, b->d_action, b->d_obs,
-                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->d_rows, b->d_ord_cnt, b->d_ord_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_clip, b->d_clip_rec, b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->d_push_state, b->d_push_force};
+                  b->d_mask, b->d_cvt, b->d_qpos_in, b->d_qvel_in, b->d_fidx_in, b->d_debug, b->d_prof, b->B.aovf, b->B.cycle, b->d_imit, b->d_order, b->B.kin, b->B.kin_ok, b->B.redo_list, b->B.redo_count, b->B.redo_why, b->d_B, b->queue.d_rows, b->ord.d_cnt, b->ord.d_list, b->d_rbuf, b->d_ep_steps, b->d_done_reason, b->d_clip, b->d_clip_rec, b->d_push_state, b->d_push_force};
   for (void* p : ptrs) if (p) hipFree(p);
   if (b->h_out) hipHostFree(b->h_out);
   if (b->h_action) hipHostFree(b->h_action);
-  if (b->ev0) hipEventDestroy(b->ev0);
-  if (b->ev1) hipEventDestroy(b->ev1);
+  if (b->timing.ev0) hipEventDestroy(b->timing.ev0); if (b->timing.ev1) hipEventDestroy(b->timing.ev1);
   if (b->own_stream && b->stream) hipStreamDestroy(b->stream);
   delete b;
 }
@@ -344,8 +342,8 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   A(b->B.aovf, (size_t)n * AOVF_COLS * 64);
   A(b->B.kin, (size_t)n * KIN_DOUBLES); A(b->B.kin_ok, n);
   A(b->B.redo_list, n); A(b->B.redo_count, 2 * DM_MAX_PIPELINE); A(b->B.redo_why, 8);
-  A(b->d_ord_cnt, DM_MAX_PIPELINE * 3 * ORD_BUCKETS);
-  A(b->d_ord_list, (size_t)3 * ORD_BUCKETS * n);                      // (768 B per env of address space, 8 B of it touched per step; allocated here so that no step call can run out of memory half-way through its parts)
+  A(b->ord.d_cnt, DM_MAX_PIPELINE * 3 * ORD_BUCKETS);
+  A(b->ord.d_list, (size_t)3 * ORD_BUCKETS * n);                      // (768 B per env of address space, 8 B of it touched per step; allocated here so that no step call can run out of memory half-way through its parts)
   A(b->d_ep_steps, n); A(b->d_done_reason, n);
   A(b->d_qpos_in, (size_t)n * NQ); A(b->d_qvel_in, (size_t)n * NV); A(b->d_fidx_in, n); A(b->d_debug, DM_DEBUG_DOUBLES);
   if (sizeof(Real) != sizeof(Ext)) A(b->d_cvt, (size_t)n * NB * 3);   // largest Real field per env: xipos (42)
@@ -386,7 +384,7 @@ extern "C" int dm_batch_create(const dm_model* m, const dm_mocap* mc, int32_t n,
   if (!ok) { dm_batch_destroy(b); return fail(DM_EHIP, "dm_batch_create: upload failed"); }
   b->B.mocap_cfg = b->d_cfg; b->B.mocap_vel = b->d_vel; b->B.mocap_dt = mc->dt; b->B.n_frames = mc->n_frames; b->B.n_envs = n; b->B.env_offset = 0;
   b->B.reward_mode = 0; b->B.autoreset = 0; b->B.action_mode = 0; b->B.seed = 0; b->B.diag = 1;
-  hipEventCreate(&b->ev0); hipEventCreate(&b->ev1);
+  hipEventCreate(&b->timing.ev0); hipEventCreate(&b->timing.ev1);
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) == hipSuccess && cus > 0) b->resident_waves = cus * 4 * DM_STEP_WAVES; }
   *out = b;
   return DM_OK;
@@ -403,11 +401,11 @@ extern "C" int dm_batch_set_stream(dm_batch* b, void* s) {
 
 extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
   if (!b) return fail(DM_EINVAL, "null batch");
-  if (!b->q.empty()) { HIPCHK(hipSetDevice(b->device)); const int rc = flush_queue(b); if (rc != DM_OK) return rc; }   /* queued steps ran under the old options */
+  if (!b->queue.q.empty()) { HIPCHK(hipSetDevice(b->device)); const int rc = flush_queue(b); if (rc != DM_OK) return rc; }   /* queued steps ran under the old options */
   switch (opt) {
     case DM_OPT_STEP_QUEUE:
       if (v < 0 || v > DM_MAX_STEP_QUEUE) return fail(DM_EINVAL, "step queue depth must be 0..DM_MAX_STEP_QUEUE");
-      b->queue_cap = (int)v; break;
+      b->queue.cap = (int)v; break;
     case DM_OPT_REWARD_MODE:
       if (v < 0 || v > 4) return fail(DM_EINVAL, "reward mode must be 0..4");
       if (v >= 3 && !b->d_imit) return fail(DM_EINVAL, "reward modes 3 and 4 need dm_mocap_set_imitation() before dm_batch_create()");
@@ -422,54 +420,25 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
     case DM_OPT_MAX_EPISODE_STEPS:
       if (v < 0 || v > 0x7fffffff) return fail(DM_EINVAL, "DM_OPT_MAX_EPISODE_STEPS must be 0 (off) or a positive step count");
       b->max_episode_steps = (int)v; break;
-    case DM_OPT_TRUNCATION_LOG: {
+    case DM_OPT_TRUNCATION_LOG:
       if (v < 0 || v > 0x7fffffff) return fail(DM_EINVAL, "DM_OPT_TRUNCATION_LOG must be 0 (off) or a capacity in records");
       HIPCHK(hipSetDevice(b->device));
       if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
       HIPCHK(hipStreamSynchronize(b->stream));       /* (a termination launch still appending to the old log) */
-      void* old[] = {b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
-      for (void* p : old) if (p) hipFree(p);
-      b->d_trunc_count = b->d_trunc_index = nullptr; b->d_trunc_qpos = b->d_trunc_qvel = nullptr; b->trunc_cap = 0; b->trunc_tick = 0;
-      if (v > 0) {
-        const size_t c = (size_t)v;
-        const bool ok = hipMalloc((void**)&b->d_trunc_count, sizeof(int)) == hipSuccess && hipMalloc((void**)&b->d_trunc_index, c * 4 * sizeof(int)) == hipSuccess &&
-                        hipMalloc((void**)&b->d_trunc_qpos, c * NQ * sizeof(double)) == hipSuccess && hipMalloc((void**)&b->d_trunc_qvel, c * NV * sizeof(double)) == hipSuccess;
-        if (!ok) {
-          void* part[] = {b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel};
-          for (void* p : part) if (p) hipFree(p);
-          b->d_trunc_count = b->d_trunc_index = nullptr; b->d_trunc_qpos = b->d_trunc_qvel = nullptr;
-          (void)hipGetLastError();
-          return fail(DM_ENOMEM, "DM_OPT_TRUNCATION_LOG: hipMalloc failed");
-        }
-        /* cleared on the batch's stream, ahead of every later launch (a pipelined part's waits for this stream at the time of its call) */
-        HIPCHK(hipMemsetAsync(b->d_trunc_count, 0, sizeof(int), b->stream)); HIPCHK(hipMemsetAsync(b->d_trunc_index, 0, c * 4 * sizeof(int), b->stream));
-        HIPCHK(hipMemsetAsync(b->d_trunc_qpos, 0, c * NQ * sizeof(double), b->stream)); HIPCHK(hipMemsetAsync(b->d_trunc_qvel, 0, c * NV * sizeof(double), b->stream));
-        b->trunc_cap = (int)v;
-      }
+      if (const int rc = b->trunc.resize((int)v, b->stream)) return rc;
       break;
-    }
     case DM_OPT_HORIZON_TERMINATION:
       if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_HORIZON_TERMINATION must be 0 or 1");
       b->horizon_term = v != 0; break;
     case DM_OPT_CLIP_MODE:
       if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_CLIP_MODE must be 0 (fixed) or 1 (episode)");
       b->clip_mode = (int)v; break;
-    case DM_OPT_PIPELINE: {
+    case DM_OPT_PIPELINE:
       if (v < 1 || v > DM_MAX_PIPELINE) return fail(DM_EINVAL, "pipeline depth must be 1..DM_MAX_PIPELINE");
       HIPCHK(hipSetDevice(b->device));
       if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
-      for (int h = 0; h < (int)v && v > 1; h++) {
-        if (!b->ps[h]) HIPCHK(hipStreamCreateWithFlags(&b->ps[h], hipStreamNonBlocking));
-        if (!b->ev_done[h]) HIPCHK(hipEventCreateWithFlags(&b->ev_done[h], hipEventDisableTiming));
-      }
-      if (v > 1 && !b->ev_in) HIPCHK(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
-      b->pipe = (int)v;
-      b->B.order = nullptr;   /* the stored dispatch order belongs to the previous partition: identity for the next launch */
-      for (int h = 0; h < DM_MAX_PIPELINE; h++) b->ord_valid[h] = false;   /* ... and so do the tickets of the per-step launches */
-      b->redo_mode = -1;      /* sub-batches beyond the new depth keep whatever their redo counters last held: the next packed step re-zeroes all
-                                 2 * DM_MAX_PIPELINE counters and restarts the phase (everything in flight was joined above) */
+      if (const int rc = set_pipeline(b, (int)v)) return rc;
       break;
-    }
     case 106: b->horizon_mode = v < 0 ? -1 : (v != 0 ? 1 : 0); break;   /* dm_batch_rollout on the packed path: 1 one launch per horizon, 0 step launches, -1 (default) by batch size */
     case DM_OPT_PACKED: case 105:                                   /* 1: four environments per wavefront (k_step_packed) where it covers the configuration; 2: the same, per-step launches with the three-set code */
       if (v < 0 || v > 2) return fail(DM_EINVAL, "DM_OPT_PACKED must be 0, 1 or 2");
@@ -531,9 +500,7 @@ extern "C" int dm_batch_reset(dm_batch* b, int32_t mode, int32_t hard, const uin
   const void* mk; int rc;
   if ((rc = stage_in(b, b->d_mask, mask, (size_t)b->n, kind, &mk))) return rc;
   HIPCHK(hipMemsetAsync(b->B.kin_ok, 0, (size_t)b->n, b->stream));
-  if (multi_clip(b)) hipLaunchKernelGGL(k_reset_clips, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk, clip_args(b));
-  else
-  hipLaunchKernelGGL(k_reset, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk);
+  launch_clip_or_plain(b, k_reset, k_reset_clips, dim3(b->n), dim3(64), b->stream, b->d_model, b->B, (int)mode, (int)hard, (const unsigned char*)mk);
   hipLaunchKernelGGL(k_zero_masked, dim3((b->n + 255) / 256), dim3(256), 0, b->stream, b->d_ep_steps, (const unsigned char*)mk, b->n);   // DM_F_EPISODE_STEPS
   HIPCHK(hipGetLastError());
   if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
@@ -561,83 +528,59 @@ static bool rollout_as_one_launch(const dm_batch* b) {
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
 }
-static int ensure_rows(dm_batch* b, int T) {
-  if (T <= b->rows_cap) return DM_OK;
-  HIPCHK(hipStreamSynchronize(b->stream));            // (a launch still reading the old table)
-  if (b->d_rows) HIPCHK(hipFree(b->d_rows));
-  b->d_rows = nullptr; b->rows_cap = 0;
-  const int cap = (T + 255) / 256 * 256;
-  HIPCHK(hipMalloc((void**)&b->d_rows, (size_t)cap * sizeof(StepRow)));
-  b->rows_cap = cap;
-  return DM_OK;
+// the termination arguments of the part [lo, lo + count) for a launch whose first step has the truncation log's tick `first_tick`
+static TermArgs term_args(const dm_batch* b, int lo, int count, int first_tick) {
+  return TermArgs{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count,
+                  b->trunc.d_count, b->trunc.d_index, b->trunc.d_qpos, b->trunc.d_qvel, b->trunc.cap, first_tick};
 }
-// T steps of every environment in ONE launch (k_rollout_packed) on the batch's stream; b->d_rows[0 .. T) has been written on that stream.
+// the push schedule's arguments for the part [lo, lo + count) ahead of a step of nsub substeps
+static PushArgs push_args(const dm_batch* b, int nsub, int lo, int count) {
+  const dm_push_desc& d = b->push;
+  return PushArgs{b->d_push_state, b->d_push_force, d.bodies, d.wait_min, d.wait_max, d.duration_min, d.duration_max, d.force_min, d.force_max, d.z_min, d.z_max,
+                  b->timestep64 * (double)nsub, lo, count};
+}
+// T steps of every environment in ONE launch (k_rollout_packed) on the batch's stream; b->queue.d_rows[0 .. T) has been written on that stream.
 // With early termination on (rollout_as_one_launch: DM_OPT_HORIZON_TERMINATION then) the launch is k_rollout_packed_term, whose steps count as T
 // step calls on the truncation log's clock: step t's records carry the tick a dm_batch_step call in its place would have had.
+static const dmp::PolicyArgs NOPOL{nullptr, nullptr, nullptr, 0, 0ull, 0ull};      // no policy step
 static int launch_horizon(dm_batch* b, int T, int nsub, const dmp::PolicyArgs& pa) {
   hipLaunchKernelGGL(k_put_batch, dim3(1), dim3(64), 0, b->stream, b->B, b->d_B);
-  if (b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
-  if (term_on(b)) {
-    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, 0, b->n,
-                      b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->trunc_cap, b->trunc_tick};
-    if (b->trunc_cap > 0) b->trunc_tick += T;
-    hipLaunchKernelGGL(k_rollout_packed_term, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->d_rows, (int)nsub, 0, b->n, (int)T, pa, b->prof ? b->d_prof : (long long*)nullptr, ta);
-  } else
-  hipLaunchKernelGGL(k_rollout_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->d_rows, (int)nsub, 0, b->n, (int)T, pa, b->prof ? b->d_prof : (long long*)nullptr);
-  if (b->timing) { HIPCHK(hipEventRecord(b->ev1, b->stream)); b->ev_pending = true; }
+  if (const int rc = b->timing.start(b->stream)) return rc;
+  long long* const clk = b->prof ? b->d_prof : (long long*)nullptr;
+  if (term_on(b))
+    hipLaunchKernelGGL(k_rollout_packed_term, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk, term_args(b, 0, b->n, b->trunc.take_ticks(T)));
+  else
+    hipLaunchKernelGGL(k_rollout_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk);
+  if (const int rc = b->timing.stop(b->stream)) return rc;
   // dispatch order for the next launch: environments with similar row counts share a wave (and, for per-step launches, longest first)
   if (b->reorder && b->has_rows) {
-    const int parts = b->pipe > 1 ? b->pipe : 1;
-    for (int h = 0; h < parts; h++) {
-      const int lo = (int)((long long)b->n * h / parts), hi = (int)((long long)b->n * (h + 1) / parts);
-      if (hi > lo) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->d_order, lo, hi - lo);
+    for (int h = 0; h < b->pipe.depth; h++) {
+      const Pipeline::Part p = b->pipe.part(b->n, h);
+      if (p.count > 0) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->d_order, p.lo, p.count);
     }
     b->B.order = b->d_order;
   }
-  HIPCHK(hipGetLastError());
-  return DM_OK;
+  HIPCHK(hipGetLastError()); return DM_OK;
 }
-int flush_queue(dm_batch* b) {
-  const int T = (int)b->q.size();
-  if (T == 0) return DM_OK;
-  HIPCHK(hipSetDevice(b->device));
-  if (pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
-  int rc = ensure_rows(b, T);
-  if (rc != DM_OK) return rc;
+void StepQueue::upload(hipStream_t stream) {
+  const int T = (int)q.size();
   for (int t0 = 0; t0 < T; t0 += ROW_CHUNK) {
     StepRowChunk c;
     const int cnt = T - t0 < ROW_CHUNK ? T - t0 : ROW_CHUNK;
-    for (int k = 0; k < cnt; k++) c.r[k] = b->q[t0 + k];
+    for (int k = 0; k < cnt; k++) c.r[k] = q[t0 + k];
     for (int k = cnt; k < ROW_CHUNK; k++) c.r[k] = StepRow{nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(k_put_rows, dim3(1), dim3(ROW_CHUNK), 0, b->stream, c, b->d_rows + t0, cnt);
+    hipLaunchKernelGGL(k_put_rows, dim3(1), dim3(ROW_CHUNK), 0, stream, c, d_rows + t0, cnt);
   }
-  const int nsub = b->q_nsub;
-  b->q.clear();                                        // (before the launch: an error below must not leave the steps queued for a second run)
-  b->queue_flushes += 1; b->queue_steps += T;
-  const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
-  return launch_horizon(b, T, nsub, nopol);
+  q.clear(); flushes += 1; steps += T;                 // (cleared before the horizon launch: an error there must not leave the steps queued for a second run)
 }
-
-// Self-ordering per-step launches (env_step.h dispatch_env / order_ticket): the descriptor a step launch of part h = [lo, ...) gets — it reads the
-// tickets the part's previous launch left (phase p), its envs take theirs from phase p + 1, its first workgroup clears phase p + 2 for the launch
-// after it.  `st` = the stream the launch goes to.  A part's tickets stay a permutation of the part whatever runs in between (horizon launches,
-// resets: only their keys grow stale); a new partition (DM_OPT_PIPELINE) starts afresh.
-// The part's phase and `valid` flag move on only once its launch is known to have gone out (ord_commit after hipGetLastError): a failed launch leaves the
-// descriptor where the last successful one put it, so the next launch reads tickets somebody really counted.
-static int ord_bind(dm_batch* b, Batch<Real>& Bh, int h, int lo, hipStream_t st) {
-  int* cnt = b->d_ord_cnt + (size_t)h * 3 * ORD_BUCKETS;
-  if (!b->ord_valid[h]) { HIPCHK(hipMemsetAsync(cnt, 0, 3 * ORD_BUCKETS * sizeof(int), st)); b->ord_phase[h] = 0; }
-  const int p = b->ord_phase[h], pn = (p + 1) % 3, pz = (p + 2) % 3;
-  const size_t n = (size_t)b->n;
-  Bh.ord_in = b->ord_valid[h] ? cnt + p * ORD_BUCKETS : nullptr;
-  Bh.ordl_in = b->d_ord_list + (size_t)p * ORD_BUCKETS * n + lo;
-  Bh.ord_out = cnt + pn * ORD_BUCKETS;
-  Bh.ordl_out = b->d_ord_list + (size_t)pn * ORD_BUCKETS * n + lo;
-  Bh.ord_zero = cnt + pz * ORD_BUCKETS;
-  Bh.ord_stride = b->n;
-  return DM_OK;
+int flush_queue(dm_batch* b) {
+  const int T = (int)b->queue.q.size(); if (T == 0) return DM_OK;
+  HIPCHK(hipSetDevice(b->device));
+  if (b->pipe.join(b->stream)) return fail(DM_EHIP, "pipeline join failed");
+  if (const int rc = b->queue.ensure_rows(T, b->stream)) return rc;
+  b->queue.upload(b->stream);
+  return launch_horizon(b, T, b->queue.nsub, NOPOL);
 }
-static void ord_commit(dm_batch* b, int h) { b->ord_phase[h] = (b->ord_phase[h] + 1) % 3; b->ord_valid[h] = true; }
 
 // the bytes of a dm_batch_step call's buffers overlap the bytes of ANY buffer of a queued call, in whatever role: the same tensors step after step, a view that
 // starts elsewhere in one of them, a queued call's observations handed in as this call's action
@@ -645,7 +588,7 @@ static bool overlaps_queued(const dm_batch* b, const double* action, const doubl
   const size_t n = (size_t)b->n;
   const char* p[4] = {(const char*)action, (const char*)obs, (const char*)reward, (const char*)done};
   const size_t len[4] = {n * NU * sizeof(Ext), n * NOBS * sizeof(Ext), n * sizeof(Ext), n};
-  for (const StepRow& r : b->q) {
+  for (const StepRow& r : b->queue.q) {
     const char* qp[4] = {(const char*)r.action, (const char*)r.obs, (const char*)r.reward, (const char*)r.done};
     for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) if (p[i] < qp[j] + len[j] && qp[j] < p[i] + len[i]) return true;
   }
@@ -655,17 +598,49 @@ static bool overlaps_queued(const dm_batch* b, const double* action, const doubl
 // the kernels of a step call: action modes 3 and 4 have their own instantiations (kernels_spd.hip, kernels_packed_spd.hip), DM_OPT_PACKED = 2 the packed
 // kernels with the three-set code; every one is launched exactly like its counterpart
 struct StepKernels {
-  decltype(&k_step_packed) packed; decltype(&k_step_packed_act) packed_act; decltype(&k_step_packed_prof) packed_prof;
+  static constexpr bool has_prof = true; decltype(&k_step_packed) packed; decltype(&k_step_packed_act) packed_act; decltype(&k_step_packed_prof) packed_prof;
   decltype(&k_step_redo) redo; decltype(&k_step_narrow) narrow; decltype(&k_step_act) act; decltype(&k_step) single; decltype(&k_step_prof) prof;
 };
 // ... and a multi-clip batch's (kernels_clips.hip, kernels_packed_clips.hip): the same launches with the clip argument last; one set for every action mode
-// (they pick the controller at run time), none with per-stage profiling
+// (they pick the controller at run time), none with per-stage profiling (step_impl refuses that combination before anything is launched)
 struct ClipStepKernels {
-  decltype(&k_step_packed_clips) packed; decltype(&k_step_packed_act_clips) packed_act; decltype(&k_step_redo_clips) redo; decltype(&k_step_narrow_clips) narrow;
+  static constexpr bool has_prof = false; decltype(&k_step_packed_clips) packed; decltype(&k_step_packed_act_clips) packed_act; decltype(&k_step_redo_clips) redo; decltype(&k_step_narrow_clips) narrow;
   decltype(&k_step_act_clips) act; decltype(&k_step_clips) single;
 };
 static ClipStepKernels clip_step_kernels(bool ext) {
   return {ext ? k_step_packed_ext_clips : k_step_packed_clips, ext ? k_step_packed_act_ext_clips : k_step_packed_act_clips, k_step_redo_clips, k_step_narrow_clips, k_step_act_clips, k_step_clips};
+}
+// which of a table's kernels steps a part: four envs per wave (or that profiled), the two-tier one-env kernel (narrow / act), all 64 columns in registers (option 102 = 0), that profiled (101)
+enum StepSelect { SEL_PACKED, SEL_PACKED_PROF, SEL_NARROW, SEL_SINGLE, SEL_PROF };
+// what the launches of one step call share: the buffers (the caller's, or a host-pointer step's staging block), the substep count, the select, the truncation log's tick
+struct StepCall { const Ext* a; Ext* o; Ext* r; unsigned char* dn; int nsub; StepSelect sel; int tick; };
+// THE per-step launch sequence, the only place one goes out from: the launches of one part [lo, lo + count) of the batch (a pipelined sub-batch, or the whole
+// batch) on stream `st` with the descriptor Bp, over the kernel table K and its trailing arguments (none, or the clip argument).
+//   push       the schedule's launch ahead of the part's step launches (k_push: push_kernel.h); off: nothing is launched
+//   step       `pa`: a fused policy step (the act kernels), or null.  Packed: the kernel counts the environments beyond its capacities into redo.count, the
+//              redo launch steps them one per wave and clears redo.next for the next call (RedoCounters)
+//   terminate  early termination on: k_terminate on the same stream (a fused policy step would act on the observation of an episode it may still end: step_impl passes no `pa` then)
+template <class Table, class... Tail>
+static void launch_part(const dm_batch* b, const Table& K, const StepCall& c, hipStream_t st, const Batch<Real>& Bp, int lo, int count, RedoCounters::Pair redo, const dmp::PolicyArgs* pa, Tail... tail) {
+  constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
+  const dim3 envs(count), slots((count + SLOTS - 1) / SLOTS), wave(64);
+  if (push_on(b)) hipLaunchKernelGGL(k_push, envs, wave, 0, st, b->d_model, Bp, push_args(b, c.nsub, lo, count));
+  switch (c.sel) {
+    case SEL_PACKED_PROF: if constexpr (Table::has_prof) hipLaunchKernelGGL(K.packed_prof, slots, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, count, redo.count, b->d_prof); break;
+    case SEL_PACKED:
+      if (pa) hipLaunchKernelGGL(K.packed_act, slots, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, count, redo.count, *pa, tail...);
+      else hipLaunchKernelGGL(K.packed, slots, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, count, redo.count, tail...);
+      break;
+    case SEL_NARROW:
+      if (pa) hipLaunchKernelGGL(K.act, envs, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, count, *pa, tail...);
+      else hipLaunchKernelGGL(K.narrow, envs, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, count, tail...);
+      break;
+    case SEL_SINGLE: hipLaunchKernelGGL(K.single, envs, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, tail...); break;      // (the whole batch: these two kernels take no part)
+    case SEL_PROF: if constexpr (Table::has_prof) hipLaunchKernelGGL(K.prof, envs, wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, b->d_prof); break;
+  }
+  if ((c.sel == SEL_PACKED || c.sel == SEL_PACKED_PROF) && b->has_rows)
+    hipLaunchKernelGGL(K.redo, dim3(REDO_BLOCKS), wave, 0, st, b->d_model, Bp, c.a, c.o, c.r, c.dn, c.nsub, lo, (const int*)redo.count, redo.next, pa ? *pa : NOPOL, tail...);
+  if (term_on(b)) launch_clip_or_plain(b, k_terminate, k_terminate_clips, envs, wave, st, b->d_model, Bp, term_args(b, lo, count, c.tick), c.o, c.dn);
 }
 static StepKernels step_kernels(bool spd, bool ext) {
   if (spd) return {ext ? k_step_packed_ext_spd : k_step_packed_spd, ext ? k_step_packed_act_ext_spd : k_step_packed_act_spd, k_step_packed_prof_spd,
@@ -679,137 +654,76 @@ static int step_impl(dm_batch* b, const double* action, double* obs, double* rew
   if (pol && (kind != DM_PTR_DEVICE || b->prof || !b->two_tier)) return fail(DM_EINVAL, "dm_batch_step_act: device pointers, the two-tier kernel and no profiling");
   if (b->prof && multi_clip(b)) return fail(DM_EUNSUPPORTED, "dm_batch_step: the profiling kernels (option 101) do not cover a multi-clip batch");
   HIPCHK(hipSetDevice(b->device));
-  if (b->queue_cap > 0 && can_queue(b, kind, pol)) {
+  StepQueue& Q = b->queue;
+  if (Q.cap > 0 && can_queue(b, kind, pol)) {
     // DM_OPT_STEP_QUEUE: remember the call; the queued steps run as ONE horizon launch (flush_queue).  A call that names a buffer an
     // earlier queued call names (the same action / output tensors step after step) runs that earlier call first: a caller that reuses
     // buffers has, by the pipelined contract, joined in between and sees plain step-by-step behaviour.
-    const bool reuse = (nsub != b->q_nsub && !b->q.empty()) || overlaps_queued(b, action, obs, reward, done);
-    if (reuse || (int)b->q.size() >= b->queue_cap) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
-    b->q.push_back(StepRow{action, obs, reward, done}); b->q_nsub = nsub;
-    return DM_OK;
+    const bool reuse = (nsub != Q.nsub && !Q.q.empty()) || overlaps_queued(b, action, obs, reward, done);
+    if (reuse || (int)Q.q.size() >= Q.cap) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
+    Q.q.push_back(StepRow{action, obs, reward, done}); Q.nsub = nsub; return DM_OK;
   }
-  if (!b->q.empty()) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
+  if (!Q.q.empty()) { const int rc = flush_queue(b); if (rc != DM_OK) return rc; }
   const Ext* a = action;
   if (kind == DM_PTR_HOST) {
     memcpy(b->h_action, action, (size_t)b->n * NU * sizeof(Ext));
     HIPCHK(hipMemcpyAsync(b->d_action, b->h_action, (size_t)b->n * NU * sizeof(Ext), hipMemcpyHostToDevice, b->stream));
     a = b->d_action;
   }
-  Ext* o = kind == DM_PTR_DEVICE ? obs : b->d_obs;
-  Ext* r = kind == DM_PTR_DEVICE ? reward : b->d_reward;
-  unsigned char* dn = kind == DM_PTR_DEVICE ? done : b->d_done;
-  const bool piped = b->pipe > 1 && kind == DM_PTR_DEVICE && !b->prof && b->two_tier;
-  if (!piped && pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
-  if (b->timing) { if (b->ev_pending) { hipEventSynchronize(b->ev1); hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1); } if (!piped) HIPCHK(hipEventRecord(b->ev0, b->stream)); }
+  const bool dev = kind == DM_PTR_DEVICE;      // outputs: the caller's tensors, or the staging block
+  Pipeline& P = b->pipe;
+  const bool piped = P.depth > 1 && kind == DM_PTR_DEVICE && !b->prof && b->two_tier;
+  if (!piped && P.join(b->stream)) return fail(DM_EHIP, "pipeline join failed");
+  int rc = DM_OK; b->timing.collect();
+  if (!piped && (rc = b->timing.start(b->stream)) != DM_OK) return rc;
   const bool reorder = b->reorder && b->has_rows && b->n > b->resident_waves;   // more envs than resident waves: later rounds exist, their tail matters
   const bool packed = packed_covers(b);      // this call runs on the packed kernels (profiled or not)
-  const StepKernels K = step_kernels(b->B.action_mode >= 3, b->packed_ext);
-  const bool clips = multi_clip(b);          // the third axis: the clip forms, launched exactly like their counterparts with the clip argument last
-  const ClipStepKernels KC = clip_step_kernels(b->packed_ext);
-  const ClipArgs<Real> ca = clip_args(b);
-  // early termination: the plain step launches, then k_terminate on the same stream; a fused policy step would act on the observation of an episode
-  // k_terminate may still end, so the policy runs as a launch of its own behind it (below)
   const bool term = term_on(b);
-  const int tick = b->trunc_tick;            // the truncation log's clock: this call's index since the log was cleared
-  if (b->trunc_cap > 0) b->trunc_tick += 1;
-  const dmp::PolicyArgs* fused = term ? nullptr : pol;
-  auto terminate = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count) {
-    if (!term) return;
-    const TermArgs ta{b->d_ep_steps, b->d_done_reason, b->fall_bodies, b->max_episode_steps, lo, count,
-                      b->d_trunc_count, b->d_trunc_index, b->d_trunc_qpos, b->d_trunc_qvel, b->trunc_cap, tick};
-    if (clips) hipLaunchKernelGGL(k_terminate_clips, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn, ca);
-    else
-    hipLaunchKernelGGL(k_terminate, dim3(count), dim3(64), 0, st, b->d_model, Bp, ta, o, dn);
-  };
-  if (packed) {
-    const int mode = piped ? 1 : 0;
-    if (mode != b->redo_mode) {      // (rare: the first packed step, or a host-pointer step between pipelined ones; every earlier launch is ordered before this stream here)
-      if (piped && pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
-      HIPCHK(hipMemsetAsync(b->B.redo_count, 0, 2 * DM_MAX_PIPELINE * sizeof(int), b->stream));
-      b->redo_mode = mode; b->redo_phase = 0;
-    }
-  }
-  // the push schedule's launch ahead of a part's step launches, on the part's stream (k_push: push_kernel.h); off: nothing is launched
-  auto push = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count) {
-    if (!push_on(b)) return;
-    const dm_push_desc& d = b->push;
-    const PushArgs P{b->d_push_state, b->d_push_force, d.bodies, d.wait_min, d.wait_max, d.duration_min, d.duration_max, d.force_min, d.force_max, d.z_min, d.z_max,
-                     b->timestep64 * (double)nsub, lo, count};
-    hipLaunchKernelGGL(k_push, dim3(count), dim3(64), 0, st, b->d_model, Bp, P);
-  };
-  // The launches of one part [lo, lo + count) of the batch (a pipelined sub-batch, or the whole batch) on stream `st`, with the descriptor Bp.  Packed: the
-  // packed kernel counts the environments beyond its capacities into the first counter of `pair` (this call's phase), the redo launch steps them one
-  // per wave and clears the other one for the next call.
-  auto launch_part = [&](hipStream_t st, const Batch<Real>& Bp, int lo, int count, int* pair, const dmp::PolicyArgs* pa) {
-    constexpr int REDO_BLOCKS = 1024;     // (round 5: 64 persistent one-wave workgroups took 5 ms to walk the 1 100 overflows a standing population of 8 192 envs produces per step on the lean kernel; an empty launch of 1 024 costs the same few microseconds)
-    const dmp::PolicyArgs nopol{nullptr, nullptr, nullptr, 0, 0ull, 0ull};
-    push(st, Bp, lo, count);
-    if (clips) {
-      if (packed) {
-        const dim3 grid((count + SLOTS - 1) / SLOTS);
-        int* rc = pair + b->redo_phase; int* rn = pair + (1 - b->redo_phase);
-        if (pa) hipLaunchKernelGGL(KC.packed_act, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, *pa, ca);
-        else hipLaunchKernelGGL(KC.packed, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, ca);
-        if (b->has_rows) hipLaunchKernelGGL(KC.redo, dim3(REDO_BLOCKS), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pa ? *pa : nopol, ca);
-      }
-      else if (pa) hipLaunchKernelGGL(KC.act, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, *pa, ca);
-      else hipLaunchKernelGGL(KC.narrow, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, ca);
-    }
-    else if (packed) {
-      const dim3 grid((count + SLOTS - 1) / SLOTS);
-      int* rc = pair + b->redo_phase; int* rn = pair + (1 - b->redo_phase);
-      if (b->prof) hipLaunchKernelGGL(K.packed_prof, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, b->d_prof);
-      else if (pa) hipLaunchKernelGGL(K.packed_act, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc, *pa);
-      else hipLaunchKernelGGL(K.packed, grid, dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, rc);
-      if (b->has_rows) hipLaunchKernelGGL(K.redo, dim3(REDO_BLOCKS), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, (const int*)rc, rn, pa ? *pa : nopol);
-    }
-    else if (pa) hipLaunchKernelGGL(K.act, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count, *pa);
-    else hipLaunchKernelGGL(K.narrow, dim3(count), dim3(64), 0, st, b->d_model, Bp, a, o, r, dn, (int)nsub, lo, count);
-    terminate(st, Bp, lo, count);
+  const StepCall c{a, dev ? obs : b->d_obs, dev ? reward : b->d_reward, dev ? done : b->d_done, (int)nsub, packed ? (b->prof ? SEL_PACKED_PROF : SEL_PACKED) : b->prof ? SEL_PROF : b->two_tier ? SEL_NARROW : SEL_SINGLE, b->trunc.take_ticks(1)};
+  const dmp::PolicyArgs* fused = term ? nullptr : pol;      // (launch_part: with termination on the policy runs behind it, below)
+  if (packed && (rc = b->redo.begin_step(piped, b->B.redo_count, P, b->stream)) != DM_OK) return rc;
+  // part h of this call through THE launch sequence, over the plain table or — the third axis — a multi-clip batch's, with the clip argument last
+  auto part = [&](hipStream_t st, const Batch<Real>& Bp, Pipeline::Part p, int h) {
+    const RedoCounters::Pair redo = b->redo.pair(b->B.redo_count, h);
+    if (multi_clip(b)) launch_part(b, clip_step_kernels(b->packed_ext), c, st, Bp, p.lo, p.count, redo, fused, clip_args(b));
+    else launch_part(b, step_kernels(b->B.action_mode >= 3, b->packed_ext), c, st, Bp, p.lo, p.count, redo, fused);
   };
   unsigned ord_bound = 0;               // parts whose launch of this call took a ticket descriptor (committed below, after the launches went out)
-  if (b->prof && packed) {
-    HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
-    launch_part(b->stream, b->B, 0, b->n, b->B.redo_count, nullptr);
-  } else if (b->prof) { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(K.prof, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, b->d_prof); terminate(b->stream, b->B, 0, b->n); }
-  else if (piped) {
+  if (piped) {
     // Sub-batch h's launch of THIS call depends on its own launch of the previous call (stream order on ps[h]) and on the
     // caller's inputs (ev_in), not on the other sub-batches: while the last, cheap workgroups of one sub-batch drain, the
     // next sub-batch's fill the freed wave slots, across calls.  Nothing is inserted into the caller's stream here — it joins
     // (dm_batch_join, or any other entry point) when it needs the outputs.
-    HIPCHK(hipEventRecord(b->ev_in, b->stream));
-    for (int h = 0; h < b->pipe; h++) {
-      const int lo = (int)((long long)b->n * h / b->pipe), hi = (int)((long long)b->n * (h + 1) / b->pipe);
-      if (hi <= lo) continue;
-      HIPCHK(hipStreamWaitEvent(b->ps[h], b->ev_in, 0));
+    HIPCHK(hipEventRecord(P.ev_in, b->stream));
+    for (int h = 0; h < P.depth; h++) {
+      const Pipeline::Part p = P.part(b->n, h);
+      if (p.count <= 0) continue;
+      HIPCHK(hipStreamWaitEvent(P.ps[h], P.ev_in, 0));
       Batch<Real> Bh = b->B;                                                   // this part's launch orders itself from the tickets its previous launch left
-      if (reorder) { const int rc2 = ord_bind(b, Bh, h, lo, b->ps[h]); if (rc2 != DM_OK) return rc2; ord_bound |= 1u << h; }
-      if (b->timing && h == 0) HIPCHK(hipEventRecord(b->ev0, b->ps[0]));     // timing: sub-batch 0's kernel on ITS stream
-      launch_part(b->ps[h], Bh, lo, hi - lo, b->B.redo_count + 2 * h, fused);
-      if (b->timing && h == 0) { HIPCHK(hipEventRecord(b->ev1, b->ps[0])); b->ev_pending = true; }
-      HIPCHK(hipEventRecord(b->ev_done[h], b->ps[h]));
+      if (reorder) { if ((rc = b->ord.bind(Bh, b->n, h, p.lo, P.ps[h])) != DM_OK) return rc; ord_bound |= 1u << h; }
+      if (h == 0 && (rc = b->timing.start(P.ps[0])) != DM_OK) return rc;     // timing: sub-batch 0's kernel on ITS stream
+      part(P.ps[h], Bh, p, h);
+      if (h == 0 && (rc = b->timing.stop(P.ps[0])) != DM_OK) return rc;
+      HIPCHK(hipEventRecord(P.ev_done[h], P.ps[h]));
     }
-    b->pipe_pending = true;
-  } else if (b->two_tier) {
+    P.pending = true;
+  } else {
     // (one launch over the whole batch.  With a pipeline depth configured the tickets are kept per part — a pipelined launch must find exactly its
     //  part's envs in them, otherwise two streams could step one env at once — so this launch takes none and falls back to the stored order: DM_OPT 104
     //  has no effect on host-pointer steps and other unpipelined launches of a batch whose DM_OPT_PIPELINE is above 1 — a performance matter only,
-    //  results do not depend on the dispatch order; include/dmenv.h says so.)
+    //  results do not depend on the dispatch order; include/dmenv.h says so.  The profiled and the single-tier kernels take no tickets either.)
+    if (c.sel == SEL_PACKED_PROF) HIPCHK(hipMemsetAsync(b->d_prof, 0, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), b->stream));
     Batch<Real> Bh = b->B;
-    if (reorder && b->pipe <= 1) { const int rc2 = ord_bind(b, Bh, 0, 0, b->stream); if (rc2 != DM_OK) return rc2; ord_bound |= 1u; }
-    // (a step that is not pipelined has joined every sub-batch stream: all of them are idle, so ONE pair of redo counters is clean — pair 0's
-    //  two are cleared above once if a pipelined step used them before)
-    launch_part(b->stream, Bh, 0, b->n, b->B.redo_count, fused);
-  } else if (clips) { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(KC.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub, ca); terminate(b->stream, b->B, 0, b->n); }
-  else { push(b->stream, b->B, 0, b->n); hipLaunchKernelGGL(K.single, dim3(b->n), dim3(64), 0, b->stream, b->d_model, b->B, a, o, r, dn, (int)nsub); terminate(b->stream, b->B, 0, b->n); }
+    if (reorder && P.depth <= 1 && !b->prof && b->two_tier) { if ((rc = b->ord.bind(Bh, b->n, 0, 0, b->stream)) != DM_OK) return rc; ord_bound |= 1u; }
+    part(b->stream, Bh, Pipeline::Part{0, b->n}, 0);
+  }
   HIPCHK(hipGetLastError());
-  for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) ord_commit(b, h);
-  if (packed) b->redo_phase ^= 1;
-  if (b->timing && !piped) { HIPCHK(hipEventRecord(b->ev1, b->stream)); b->ev_pending = true; }
+  for (int h = 0; h < DM_MAX_PIPELINE; h++) if ((ord_bound >> h) & 1u) b->ord.commit(h);
+  if (packed) b->redo.advance();
+  if (!piped && (rc = b->timing.stop(b->stream)) != DM_OK) return rc;
   if (pol && term) {      // the policy's step on the observations the termination launch left: one launch over the whole batch, behind every part
-    if (pipe_join(b)) return fail(DM_EHIP, "pipeline join failed");
-    const int rc2 = dm_policy_act(pol->P, o, pol->action, pol->vpred, b->n, pol->stochastic, pol->seed, pol->counter, (void*)b->stream);
-    if (rc2 != DM_OK) return rc2;
+    if (P.join(b->stream)) return fail(DM_EHIP, "pipeline join failed");
+    if ((rc = dm_policy_act(pol->P, c.o, pol->action, pol->vpred, b->n, pol->stochastic, pol->seed, pol->counter, (void*)b->stream)) != DM_OK) return rc;
   }
   if (kind == DM_PTR_HOST) {
     HIPCHK(hipMemcpyAsync(b->h_out, b->d_obs, b->out_bytes, hipMemcpyDeviceToHost, b->stream));
@@ -850,9 +764,9 @@ extern "C" int dm_batch_rollout(dm_batch* b, double* action, double* obs, double
     }
     return DM_OK;
   }
-  const int rc = ensure_rows(b, (int)T);
+  const int rc = b->queue.ensure_rows((int)T, b->stream);
   if (rc != DM_OK) return rc;
-  hipLaunchKernelGGL(k_fill_rows, dim3(((int)T + 63) / 64), dim3(64), 0, b->stream, b->d_rows, (const Ext*)action, obs, reward, done, (int)T, n);
+  hipLaunchKernelGGL(k_fill_rows, dim3(((int)T + 63) / 64), dim3(64), 0, b->stream, b->queue.d_rows, (const Ext*)action, obs, reward, done, (int)T, n);
   dmp::PolicyArgs pa{weights, action, vpred, (int)stochastic, (unsigned long long)seed, (unsigned long long)counter};
   return launch_horizon(b, (int)T, (int)nsub, pa);
 }
@@ -967,15 +881,15 @@ extern "C" int dm_batch_read_profile(dm_batch* b, long long* out_host) {   /* [N
   HIPCHK(hipMemcpy(out_host, b->d_prof, (size_t)b->n * dm::PROF_SLOTS * sizeof(long long), hipMemcpyDeviceToHost));
   return DM_OK;
 }
-extern "C" int dm_batch_enable_timing(dm_batch* b, int32_t on) { if (!b) return fail(DM_EINVAL, "null batch"); b->timing = on != 0; b->ev_pending = false; return DM_OK; }
+extern "C" int dm_batch_enable_timing(dm_batch* b, int32_t on) { if (!b) return fail(DM_EINVAL, "null batch"); b->timing.on = on != 0; b->timing.pending = false; return DM_OK; }
 extern "C" int dm_batch_last_step_ms(dm_batch* b, float* ms) {
   if (!b || !ms) return fail(DM_EINVAL, "null argument");
   HIPCHK(hipSetDevice(b->device));
   if (settle(b)) return fail(DM_EHIP, "dm_batch_last_step_ms: running the queued steps failed");      // (queued steps are timed by the launch that runs them)
-  if (!b->ev_pending) return fail(DM_EINVAL, "no timed step recorded");
-  HIPCHK(hipEventSynchronize(b->ev1));
-  HIPCHK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
-  *ms = b->last_ms;
+  if (!b->timing.pending) return fail(DM_EINVAL, "no timed step recorded");
+  HIPCHK(hipEventSynchronize(b->timing.ev1));
+  HIPCHK(hipEventElapsedTime(&b->timing.last_ms, b->timing.ev0, b->timing.ev1));
+  *ms = b->timing.last_ms;
   return DM_OK;
 }
 extern "C" int dm_batch_redo_total(dm_batch* b, int64_t* out) {
@@ -990,21 +904,21 @@ extern "C" int dm_batch_redo_total(dm_batch* b, int64_t* out) {
 }
 extern "C" int dm_batch_queue_stats(dm_batch* b, int64_t* out) {
   if (!b || !out) return fail(DM_EINVAL, "dm_batch_queue_stats: null argument");
-  out[0] = b->queue_flushes; out[1] = b->queue_steps; out[2] = (int64_t)b->q.size();
+  out[0] = b->queue.flushes; out[1] = b->queue.steps; out[2] = (int64_t)b->queue.q.size();
   return DM_OK;
 }
 extern "C" int dm_batch_truncations(dm_batch* b, int32_t* count, int32_t* index, double* qpos, double* qvel, int32_t cap, int32_t clear, int32_t kind) {
   if (!b || !count || cap < 0 || (kind != DM_PTR_HOST && kind != DM_PTR_DEVICE)) return fail(DM_EINVAL, "dm_batch_truncations: null batch or count, negative cap, or bad ptr_kind");
-  if (b->trunc_cap <= 0) return fail(DM_EINVAL, "dm_batch_truncations: the truncation log is off (DM_OPT_TRUNCATION_LOG)");
+  if (b->trunc.cap <= 0) return fail(DM_EINVAL, "dm_batch_truncations: the truncation log is off (DM_OPT_TRUNCATION_LOG)");
   HIPCHK(hipSetDevice(b->device));
   if (settle(b)) return fail(DM_EHIP, "pipeline join failed");
   const hipMemcpyKind k = kind == DM_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t m = (size_t)(cap < b->trunc_cap ? cap : b->trunc_cap);
-  HIPCHK(hipMemcpyAsync(count, b->d_trunc_count, sizeof(int32_t), k, b->stream));
-  if (index && m) HIPCHK(hipMemcpyAsync(index, b->d_trunc_index, m * 4 * sizeof(int32_t), k, b->stream));
-  if (qpos && m) HIPCHK(hipMemcpyAsync(qpos, b->d_trunc_qpos, m * NQ * sizeof(double), k, b->stream));
-  if (qvel && m) HIPCHK(hipMemcpyAsync(qvel, b->d_trunc_qvel, m * NV * sizeof(double), k, b->stream));
-  if (clear) { HIPCHK(hipMemsetAsync(b->d_trunc_count, 0, sizeof(int), b->stream)); b->trunc_tick = 0; }
+  const size_t m = (size_t)(cap < b->trunc.cap ? cap : b->trunc.cap);
+  HIPCHK(hipMemcpyAsync(count, b->trunc.d_count, sizeof(int32_t), k, b->stream));
+  if (index && m) HIPCHK(hipMemcpyAsync(index, b->trunc.d_index, m * 4 * sizeof(int32_t), k, b->stream));
+  if (qpos && m) HIPCHK(hipMemcpyAsync(qpos, b->trunc.d_qpos, m * NQ * sizeof(double), k, b->stream));
+  if (qvel && m) HIPCHK(hipMemcpyAsync(qvel, b->trunc.d_qvel, m * NV * sizeof(double), k, b->stream));
+  if (clear) { HIPCHK(hipMemsetAsync(b->trunc.d_count, 0, sizeof(int), b->stream)); b->trunc.tick = 0; }
   if (kind == DM_PTR_HOST) HIPCHK(hipStreamSynchronize(b->stream));
   return DM_OK;
 }

@@ -145,11 +145,8 @@ extern "C" int dm_batch_state_features(dm_batch* b, const double* qpos, const do
   const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_p = st.in(phase, (size_t)n * sizeof(double));
   const int i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NSTATE * sizeof(double));
   if ((rc = st.commit())) return rc;
-  if (multi_clip(b)) hipLaunchKernelGGL(k_state_features_clips, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
-                                        st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o), clip_args(b));
-  else
-  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
-                     st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
+  launch_clip_or_plain(b, k_state_features, k_state_features_clips, dim3(n), dim3(64), b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                       st.ptr<const double>(i_p), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());
   return st.finish();
 }
@@ -192,11 +189,8 @@ extern "C" int dm_batch_imitation_terms(dm_batch* b, const double* qpos, const d
   const int i_q = st.in(qpos, (size_t)n * NQ * sizeof(double)), i_v = st.in(qvel, (size_t)n * NV * sizeof(double)), i_f = st.in(frame, (size_t)n * sizeof(int32_t));
   const int i_c = st.in(cycle, (size_t)n * sizeof(int32_t)), i_id = st.in(env_ids, (size_t)n * sizeof(int32_t)), i_o = st.out(out, (size_t)n * DM_NTERMS * sizeof(double));
   if ((rc = st.commit())) return rc;
-  if (multi_clip(b)) hipLaunchKernelGGL(k_imitation_terms_clips, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
-                                        st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o), clip_args(b));
-  else
-  hipLaunchKernelGGL(k_imitation_terms, dim3(n), dim3(64), 0, b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
-                     st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
+  launch_clip_or_plain(b, k_imitation_terms, k_imitation_terms_clips, dim3(n), dim3(64), b->stream, b->d_model, b->B, st.ptr<const double>(i_q), st.ptr<const double>(i_v),
+                       st.ptr<const int>(i_f), st.ptr<const int>(i_c), st.ptr<const int>(i_id), st.ptr<Ext>(i_o));
   HIPCHK(hipGetLastError());
   return st.finish();
 }
