@@ -31,6 +31,8 @@ ACTION_RAW, ACTION_P_CONTROL, ACTION_PD, ACTION_SPD_TARGET, ACTION_SPD_MOCAP = 0
 OPT_CLIP_MODE = 13
 CLIP_FIXED, CLIP_EPISODE = 0, 1
 MAX_CLIPS = 32
+# 1: action modes 3 and 4 run inside the horizon launch and the step queue (k_rollout_packed_spd, k_rollout_packed_term_spd) instead of sending them back to step launches
+OPT_HORIZON_SPD = 14
 MAX_PIPELINE = 8
 MAX_STEP_QUEUE = 256
 # per-environment capacities of the OPT_PACKED path (include/dmenv.h DM_PACKED_*)

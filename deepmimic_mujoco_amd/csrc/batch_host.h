@@ -130,6 +130,8 @@ struct dm_batch {
   unsigned fall_bodies = 0; int max_episode_steps = 0; int *d_ep_steps = nullptr, *d_done_reason = nullptr;   // [N] DM_F_EPISODE_STEPS, DM_F_DONE_REASON
   // DM_OPT_HORIZON_TERMINATION: the horizon launch and the step queue run with termination inside (k_rollout_packed_term) instead of falling back to step launches
   bool horizon_term = false;
+  // DM_OPT_HORIZON_SPD: in action modes 3 and 4 the horizon launch and the step queue run with the controller inside (kernels_rollout_spd.hip) instead of falling back to step launches
+  bool horizon_spd = false;
   // the clip set (dm_mocap_create_set; step_rules.h ClipArgs): n_clips > 1 makes the batch multi-clip — its launches are the clip kernels (kernels_clips.hip,
   // kernels_packed_clips.hip).  d_clip is DM_F_CLIP (all 0 on a single-clip batch); clip_frames: the clips' lengths, for the host's range checks
   int n_clips = 1, clip_mode = 0; int* d_clip = nullptr; dm::ClipRec<Real>* d_clip_rec = nullptr; std::vector<int> clip_frames;

@@ -6,10 +6,10 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
-SOURCES = ["dmenv.hip", "views.hip", "learner.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_rollout_term.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "kernels_clips.hip", "kernels_packed_clips.hip", "kernels_push.hip", "push_kernel.h", "packed_body.h", "host_common.h", "batch_host.h", "kernels.h", "env_kernel.h", "step_rules.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "policy_wave_launch_order.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "slot_term.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h", "floor_contact.h", "term_kernel.h", "terms_kernel.h", "view_stage.h"]
+SOURCES = ["dmenv.hip", "views.hip", "learner.hip", "kernels_packed.hip", "kernels_rollout.hip", "kernels_rollout_term.hip", "kernels_rollout_spd.hip", "kernels_spd.hip", "kernels_packed_spd.hip", "kernels_clips.hip", "kernels_packed_clips.hip", "kernels_push.hip", "push_kernel.h", "packed_body.h", "host_common.h", "batch_host.h", "kernels.h", "env_kernel.h", "step_rules.h", "env_step.h", "model_host.h", "topology.h", "wave.h", "policy_kernel.h", "policy_wave_launch_order.h", "rng.h", "mlp_tile.h", "vf_kernel.h", "pg_kernel.h", "disc_kernel.h", "slot_kernel.h", "slot_step.h", "slot_term.h", "render.h", "render_kernel.h", "state_features.h", "state_kernel.h", "floor_contact.h", "term_kernel.h", "terms_kernel.h", "view_stage.h"]
 OUT = os.path.join(HERE, "libdmenv.so")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-shift-count-negative", "-Wno-implicit-const-int-float-conversion"]
-# Eleven translation units (kernels.h lists them), each with the backend options its kernels want (round 4, A/B in profiles/r04_ab_kernel_variants.md):
+# Twelve translation units (kernels.h lists them), each with the backend options its kernels want (round 4, A/B in profiles/r04_ab_kernel_variants.md):
 #   kernels_packed.hip — four environments per wavefront: ONE wave per SIMD with the whole register file.  The default scheduling strategy (max-occupancy: keep
 #                        register pressure low) buys nothing there; scheduling for instruction-level parallelism hides more of a lone wave's LDS / f64 latencies
 #                        (+1.0 .. +1.6 % env-steps/s), register-class priority in the greedy allocator +0.4 %.
@@ -28,10 +28,11 @@ ROLLOUT_FLAGS = PACKED_FLAGS + ["-mllvm", "-amdgpu-load-store-vectorizer=false",
 if os.environ.get("DM_ROLLOUT_FLAGS") is not None:
     ROLLOUT_FLAGS = os.environ["DM_ROLLOUT_FLAGS"].split()
 #   kernels_rollout_term.hip — k_rollout_packed_term (the horizon launch with early termination inside: slot_term.h) with the same options, beside it: k_rollout_packed's code object is not touched.
+#   kernels_rollout_spd.hip — the two horizon launches of action modes 3 and 4 (DM_OPT_HORIZON_SPD), likewise: the same options, beside them.
 #   kernels_spd.hip / kernels_packed_spd.hip — the step kernels of action modes 3 and 4, with the options of the units whose kernels they mirror.
 #   kernels_clips.hip / kernels_packed_clips.hip — the kernels of multi-clip batches (one clip per env), likewise.
 #   kernels_push.hip — the two launches of external pushes (push_kernel.h), one wave per env: defaults.
-UNITS = [("dmenv.hip", []), ("views.hip", []), ("learner.hip", []), ("kernels_packed.hip", PACKED_FLAGS), ("kernels_rollout.hip", ROLLOUT_FLAGS), ("kernels_rollout_term.hip", ROLLOUT_FLAGS), ("kernels_spd.hip", []), ("kernels_packed_spd.hip", PACKED_FLAGS), ("kernels_clips.hip", []), ("kernels_packed_clips.hip", PACKED_FLAGS), ("kernels_push.hip", [])]
+UNITS = [("dmenv.hip", []), ("views.hip", []), ("learner.hip", []), ("kernels_packed.hip", PACKED_FLAGS), ("kernels_rollout.hip", ROLLOUT_FLAGS), ("kernels_rollout_term.hip", ROLLOUT_FLAGS), ("kernels_rollout_spd.hip", ROLLOUT_FLAGS), ("kernels_spd.hip", []), ("kernels_packed_spd.hip", PACKED_FLAGS), ("kernels_clips.hip", []), ("kernels_packed_clips.hip", PACKED_FLAGS), ("kernels_push.hip", [])]
 
 
 def hipcc():

@@ -430,6 +430,9 @@ extern "C" int dm_batch_set_option(dm_batch* b, int32_t opt, int64_t v) {
     case DM_OPT_HORIZON_TERMINATION:
       if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_HORIZON_TERMINATION must be 0 or 1");
       b->horizon_term = v != 0; break;
+    case DM_OPT_HORIZON_SPD:
+      if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_HORIZON_SPD must be 0 or 1");
+      b->horizon_spd = v != 0; break;
     case DM_OPT_CLIP_MODE:
       if (v != 0 && v != 1) return fail(DM_EINVAL, "DM_OPT_CLIP_MODE must be 0 (fixed) or 1 (episode)");
       b->clip_mode = (int)v; break;
@@ -519,11 +522,11 @@ static bool rollout_as_one_launch(const dm_batch* b) {
   // SIMD (8 192 envs on an MI355X; at 4 096 envs 17.3 M env-steps/s against 12.2 M for the one-env steps and 11.4 M for the packed ones).
   // Larger batches run several rounds of waves per step, which balances the slow waves by itself, while a horizon launch has its own
   // end-of-horizon tail (16 384 envs: 19.5 M per step, ~17 M per horizon); without rows there is no slow wave to wait for.
-  // (action modes 3 and 4 — a control evaluation per substep — live in the per-step kernels only: their horizons and queued steps run as step launches;
-  //  so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set; those of a multi-clip batch, with or without it; and those
-  //  of a batch with a push schedule set, whose k_push precedes every step launch)
+  // (action modes 3 and 4 — a control evaluation per substep — run their horizons and queued steps as step launches, unless DM_OPT_HORIZON_SPD asks for the
+  //  horizon kernels that carry the controller; so do those of a batch with early termination on, unless DM_OPT_HORIZON_TERMINATION is set; those of a
+  //  multi-clip batch, with or without either; and those of a batch with a push schedule set, whose k_push precedes every step launch)
   const int simds = b->resident_waves / DM_STEP_WAVES;
-  return packed_covers(b) && !multi_clip(b) && !push_on(b) && b->B.action_mode <= 2 && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
+  return packed_covers(b) && !multi_clip(b) && !push_on(b) && (b->B.action_mode <= 2 || b->horizon_spd) && (!term_on(b) || b->horizon_term) && (b->horizon_mode == 1 || (b->horizon_mode < 0 && b->has_rows && b->n <= 2 * SLOTS * simds));
 }
 static bool can_queue(const dm_batch* b, int kind, const dmp::PolicyArgs* pol) {
   return kind == DM_PTR_DEVICE && !pol && !b->prof && rollout_as_one_launch(b);      // (with timing on, the events bracket the horizon launch)
@@ -543,14 +546,22 @@ static PushArgs push_args(const dm_batch* b, int nsub, int lo, int count) {
 // With early termination on (rollout_as_one_launch: DM_OPT_HORIZON_TERMINATION then) the launch is k_rollout_packed_term, whose steps count as T
 // step calls on the truncation log's clock: step t's records carry the tick a dm_batch_step call in its place would have had.
 static const dmp::PolicyArgs NOPOL{nullptr, nullptr, nullptr, 0, 0ull, 0ull};      // no policy step
+// THE horizon kernels, one row per controller: action modes 0..2 (kernels_rollout.hip, kernels_rollout_term.hip) and modes 3 and 4 (kernels_rollout_spd.hip; reached
+// only with DM_OPT_HORIZON_SPD: rollout_as_one_launch); one column per termination form: none, or the phase inside the loop (the trailing TermArgs)
+struct HorizonKernels { decltype(&k_rollout_packed) plain; decltype(&k_rollout_packed_term) term; };
+static const HorizonKernels& horizon_kernels(const dm_batch* b) {
+  static const HorizonKernels K[2] = {{k_rollout_packed, k_rollout_packed_term}, {k_rollout_packed_spd, k_rollout_packed_term_spd}};
+  return K[b->B.action_mode >= 3 ? 1 : 0];
+}
 static int launch_horizon(dm_batch* b, int T, int nsub, const dmp::PolicyArgs& pa) {
   hipLaunchKernelGGL(k_put_batch, dim3(1), dim3(64), 0, b->stream, b->B, b->d_B);
   if (const int rc = b->timing.start(b->stream)) return rc;
   long long* const clk = b->prof ? b->d_prof : (long long*)nullptr;
+  const HorizonKernels& K = horizon_kernels(b);
   if (term_on(b))
-    hipLaunchKernelGGL(k_rollout_packed_term, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk, term_args(b, 0, b->n, b->trunc.take_ticks(T)));
+    hipLaunchKernelGGL(K.term, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk, term_args(b, 0, b->n, b->trunc.take_ticks(T)));
   else
-    hipLaunchKernelGGL(k_rollout_packed, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk);
+    hipLaunchKernelGGL(K.plain, dim3((b->n + SLOTS - 1) / SLOTS), dim3(64), 0, b->stream, b->d_model, (const Batch<Real>*)b->d_B, (const StepRow*)b->queue.d_rows, (int)nsub, 0, b->n, (int)T, pa, clk);
   if (const int rc = b->timing.stop(b->stream)) return rc;
   // dispatch order for the next launch: environments with similar row counts share a wave (and, for per-step launches, longest first)
   if (b->reorder && b->has_rows) {

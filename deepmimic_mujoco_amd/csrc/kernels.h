@@ -1,5 +1,5 @@
 // kernels.h — what the translation units of libdmenv.so with environment kernels share: the build's arithmetic type and the prototypes of the step
-// kernels that one unit defines and dmenv.hip launches.  The library's ten units (csrc/build.py UNITS):
+// kernels that one unit defines and dmenv.hip launches.  The library's twelve units (csrc/build.py UNITS):
 //   dmenv.hip           one-env step kernels of action modes 0..2, reset / state / ordering / render / state-feature / termination kernels, the batch half of the C ABI
 //                       (host side: models, mocap, batches, options, state, step / rollout / queue, profiling and timing)
 //   views.hip           dm_batch_render, dm_batch_state_features and dm_batch_floor_contacts (host side: one prologue, one staging helper over view_stage.h; kernels in dmenv.hip's unit)
@@ -7,6 +7,8 @@
 //   kernels_rollout.hip the horizon launch (k_rollout_packed + the step bodies it calls): the packed options and the load-store vectoriser off
 //   kernels_rollout_term.hip   the horizon launch with early termination inside (k_rollout_packed_term, DM_OPT_HORIZON_TERMINATION: slot_term.h), with the
 //                       options of kernels_rollout.hip; a unit of its own so that k_rollout_packed stays the code object it was
+//   kernels_rollout_spd.hip    the two horizon launches in action modes 3 and 4 (k_rollout_packed_spd, k_rollout_packed_term_spd, DM_OPT_HORIZON_SPD: slot_rollout's
+//                       SPD switch), with the options of kernels_rollout.hip; a unit of its own for the same reason
 //   kernels_spd.hip / kernels_packed_spd.hip   the one-env and the packed step kernels of action modes 3 and 4 (stable PD control per substep), units
 //                       of their own with the options of dmenv.hip / kernels_packed.hip: the kernels of modes 0..2 carry no controller code
 //   kernels_clips.hip / kernels_packed_clips.hip   the kernels of MULTI-CLIP batches (dm_mocap_create_set: one clip per env, step_rules.h ClipArgs): the one-env and
@@ -73,6 +75,11 @@ __global__ void k_step_packed_prof(const dm::DevModel<Real>* __restrict__ Mp, dm
 struct TermArgs;       // (term_kernel.h)
 __global__ void k_rollout_packed_term(const dm::DevModel<Real>* __restrict__ Mp, const dm::Batch<Real>* __restrict__ Bp, const dm::StepRow* __restrict__ rows, int n_substeps, int first,
                                       int count, int T, dmp::PolicyArgs pa, long long* __restrict__ wave_clk, TermArgs ta);
+// ---- kernels_rollout_spd.hip: the two horizon launches in action modes 3 and 4 (DM_OPT_HORIZON_SPD) --------------------------------------------------------
+__global__ void k_rollout_packed_spd(const dm::DevModel<Real>* __restrict__ Mp, const dm::Batch<Real>* __restrict__ Bp, const dm::StepRow* __restrict__ rows, int n_substeps, int first,
+                                     int count, int T, dmp::PolicyArgs pa, long long* __restrict__ wave_clk);
+__global__ void k_rollout_packed_term_spd(const dm::DevModel<Real>* __restrict__ Mp, const dm::Batch<Real>* __restrict__ Bp, const dm::StepRow* __restrict__ rows, int n_substeps, int first,
+                                          int count, int T, dmp::PolicyArgs pa, long long* __restrict__ wave_clk, TermArgs ta);
 // ---- kernels_packed_spd.hip, kernels_spd.hip: the same launches in action modes 3 and 4 -----------------------------------------------------
 __global__ void k_step_packed_spd(const dm::DevModel<Real>* __restrict__ Mp, dm::Batch<Real> B, const Ext* __restrict__ action, Ext* __restrict__ obs, Ext* __restrict__ reward,
                               unsigned char* __restrict__ done, int n_substeps, int first, int count, int* __restrict__ redo_count);

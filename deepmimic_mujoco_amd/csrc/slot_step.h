@@ -111,7 +111,10 @@ DM_DEV void slot_load_env(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>
 // stages at the start of every substep: kinematics, bias without actuation (-c in s.tau), the mass-matrix stage with h kd on the diagonal,
 // one register solve (every lane of the slot carries the vector, as in slot_smooth_solve).  The factor overwrites the inertias here (r2), so
 // the substep's first RK4 evaluation forms its own kinematics again.  qbar / vbar: dof-distributed targets (dofs 6..33).
-template <class R>
+// CARRY (the horizon launch of modes 3 and 4, k_rollout_packed_spd): kinematics carried over from the previous step (slot_forward) must not reach the evaluation
+// BEHIND this pass, whose inertias the factor has overwritten.  So this pass is their one consumer: where every slot's `kin_ok` flag is set it skips its own
+// kinematics stage — the state is the one the 5-term reward's pass ended the previous step on — and the flag is cleared either way.
+template <class R, bool CARRY = false>
 DM_DEV void slot_spd_control(const DevModel<R>& M, const Batch<R>& B, SlotShared<R>& s, const SlotTables& tb, int env, int sl, const LaneTopo& lt, bool live,
                              const DofVec<R>& qbar, const DofVec<R>& vbar) {
   const R h = M.timestep;
@@ -119,7 +122,13 @@ DM_DEV void slot_spd_control(const DevModel<R>& M, const Batch<R>& B, SlotShared
   for (int c = 0; c < DOF_PASSES; c++) { const int d = sl + SW * c; if (d < NV) s.act[d] = 0; }
   dmw::sync();
   R xip[3];
-  slot_kinematics(M, s, sl, lt, xip);
+  bool skip_kin = false;
+  if constexpr (CARRY) {
+    skip_kin = dmw::ballot(s.kin_ok() != R(0)) == ~0ull;
+    dmw::sync();
+    if (sl == 0) s.kin_ok() = R(0);
+  }
+  if (!skip_kin) slot_kinematics(M, s, sl, lt, xip);
   slot_bias(M, s, tb, sl, lt);
   slot_mass_matrix<R, false, true>(M, s, tb, sl, lt, (const DebugOut*)0);
   R pd[DOF_PASSES], kd[DOF_PASSES];
@@ -294,6 +303,7 @@ DM_DEV R slot_imitation_reward(const DevModel<R>& M, const Batch<R>& B, SlotShar
 // means what it says and the first evaluation may skip its position stage (slot_forward): one kinematics pass in five less with the 5-term
 // reward, bit-identical results.  Without kin_carry (the first step of a launch, the step after an in-wave re-step) the flags are cleared first.
 // SPD: the instantiation for action modes 3 and 4 (slot_spd_control); the kernels of modes 0..2 — the horizon launch among them — instantiate SPD = false.
+// CARRY + SPD (k_rollout_packed_spd): the first substep's control pass is what consumes the carried kinematics (slot_spd_control), not the first evaluation.
 // CLIPS: NoClips, or the ClipArgs of a multi-clip batch (step_rules.h).  The clip view is per slot; it is built where the clip is read — the action front end, the
 // reward epilogue, the reset — and is not alive across the substeps between them: the constraint solve has no registers to give.
 template <class R, bool PROF, bool CARRY, int MAXR, bool SPD, class CLIPS = NoClips>
@@ -323,7 +333,7 @@ DM_DEV bool slot_env_step_impl(const DevModel<R>& M, const Batch<R>& B, SlotShar
   R xip[3];
   int why = 0;
   for (int k = 0; k < n_substeps; k++) {
-    if constexpr (SPD) slot_spd_control(M, B, s, tb, env, sl, lt, live, qbar, vbar);
+    if constexpr (SPD) slot_spd_control<R, CARRY>(M, B, s, tb, env, sl, lt, live, qbar, vbar);
     slot_rk4_step<R, PROF, CARRY, MAXR>(M, s, tb, sl, lane, lt, xip, why, prof);
   }
   const bool ovf = dmw::row_ballot(why != 0, lane) != 0u;
@@ -459,13 +469,13 @@ template <class R> union SlotOrOne {
   struct { Shared<R> s; StepScratch<R> x; } one;
 };
 // (a real call: the one-env step keeps its own register allocation and spill slots, the hot loop around it is compiled as if it were not there)
-template <class R, int NR>
+template <class R, int NR, bool SPD = false>
 DM_DEV_CALL64 void restep_one_env(const DevModel<R>* M, const Batch<R>* B, Shared<R>* s, StepScratch<R>* x, int env, int lane, const double* action, double* obs,
                                     double* reward, unsigned char* done, int n_substeps DM_CALL_SLOT_PARAM) {
   DM_CALL_SLOT_TOUCH(0);
   using dmw::uniform_ptr; using dmw::in_lds; using dmw::in_global; using dmw::in_constant;
   const Batch<R> Bv = *in_constant(B);                  // (the struct's pointers are generic too: a copy whose members are told to be global)
-  env_step_impl<R, NR, false, false>(*in_constant(M), global_members(Bv), *in_lds(uniform_ptr(s)), *in_lds(uniform_ptr(x)), dmw::uniform(env), lane, in_global(uniform_ptr(action)),
+  env_step_impl<R, NR, false, SPD>(*in_constant(M), global_members(Bv), *in_lds(uniform_ptr(s)), *in_lds(uniform_ptr(x)), dmw::uniform(env), lane, in_global(uniform_ptr(action)),
                   in_global(uniform_ptr(obs)), in_global(uniform_ptr(reward)), in_global(uniform_ptr(done)), dmw::uniform(n_substeps));
 }
 // (the packed step as a call too: its body is then compiled exactly as in k_step_packed — inlined into the horizon loop the register
@@ -473,14 +483,15 @@ DM_DEV_CALL64 void restep_one_env(const DevModel<R>* M, const Batch<R>* B, Share
 // Two instantiations: MAXR = 2 * SW — the lean step of rounds 3-4 (one and two row sets; an environment beyond 32 rows is flagged and re-stepped) — and
 // MAXR = SLOT_MAXROWS — the same step with the partial third row set compiled in (33 .. 40 rows stay in the wave), 8 % slower on everything else (see
 // slot_forward).  slot_rollout picks per wave-step.  Returns (stored ? 1 : 0) | row count of the slot's environment << 8.
-template <class R, int MAXR>
+// SPD: the step and the re-step with the controller of action modes 3 and 4 compiled in (kernels_rollout_spd.hip); every other caller's stay SPD = false.
+template <class R, int MAXR, bool SPD = false>
 DM_DEV_CALL64 int slot_env_step_call(const DevModel<R>* M, const Batch<R>* B, SlotShared<R>* s, SlotTables* tb, int env, int sl, int lane, bool live,
                                      const double* action, double* obs, double* reward, unsigned char* done, int n_substeps, int kin_carry DM_CALL_SLOT_PARAM) {
   using dmw::uniform_ptr; using dmw::in_lds; using dmw::in_global; using dmw::in_constant;
   const Batch<R> Bv = *in_constant(B);
   SlotShared<R>& sr = *in_lds(s);
   DM_CALL_SLOT_TOUCH(env);
-  const bool stored = slot_env_step_impl<R, false, true, MAXR, false>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
+  const bool stored = slot_env_step_impl<R, false, true, MAXR, SPD>(*in_constant(M), global_members(Bv), sr, *in_lds(uniform_ptr(tb)), env, sl, lane, live, in_global(uniform_ptr(action)),
                                                           in_global(uniform_ptr(obs)), in_global(uniform_ptr(reward)), in_global(uniform_ptr(done)), dmw::uniform(n_substeps), (int*)0, (int*)0,
                                                           (long long*)0, dmw::uniform(kin_carry) != 0);
   return (stored ? 1 : 0) | (sr.nefc << 8);
@@ -516,7 +527,7 @@ struct NoTermination { static constexpr bool on = false; };
 template <class T> struct TermSwitch { static constexpr bool on = T::on; };
 template <class T> struct TermSwitch<T&> : TermSwitch<T> {};
 template <class T> struct TermSwitch<const T> : TermSwitch<T> {};
-template <class R, int NR, class POLICY, class TERM = NoTermination>
+template <class R, int NR, bool SPD = false, class POLICY, class TERM = NoTermination>
 DM_DEV void slot_rollout(const DevModel<R>& M_in, const Batch<R>& B, SlotShared<R>* sh, SlotTables& tb, Shared<R>& one_s, StepScratch<R>& one_x,
                          int env, int lane, bool live, const StepRow* rows, int n_substeps, int T, POLICY&& policy, long long* prof_acc = 0, bool policy_clobbers_kin = false,
                          TERM&& term = TERM()) {
@@ -547,8 +558,8 @@ DM_DEV void slot_rollout(const DevModel<R>& M_in, const Batch<R>& B, SlotShared<
     // (measured, round 4: the step body inlined here instead of called — the batch descriptor and tables read afresh every step so that nothing is
     //  hoisted — removes the callee's register save / restore (1.6 KB per lane per call) and is 10 % SLOWER: 15.0 against 16.7 M env-steps/s,
     //  profiles/r04_ab_kernel_variants.md; the loop around the body costs the allocator more than the calls cost the memory system)
-    ret = heavy ? slot_env_step_call<R, SLOT_MAXROWS>(&M, &B, &sh[slot], &tb, env, sl, lane, live, a_t, o_t, r_t, d_t, n_substeps, carry DM_CALL_SLOT_ARG)
-                : slot_env_step_call<R, 2 * SW>(&M, &B, &sh[slot], &tb, env, sl, lane, live, a_t, o_t, r_t, d_t, n_substeps, carry DM_CALL_SLOT_ARG);
+    ret = heavy ? slot_env_step_call<R, SLOT_MAXROWS, SPD>(&M, &B, &sh[slot], &tb, env, sl, lane, live, a_t, o_t, r_t, d_t, n_substeps, carry DM_CALL_SLOT_ARG)
+                : slot_env_step_call<R, 2 * SW, SPD>(&M, &B, &sh[slot], &tb, env, sl, lane, live, a_t, o_t, r_t, d_t, n_substeps, carry DM_CALL_SLOT_ARG);
     const bool stored = (ret & 1) != 0;
     last_rows = (stored || !live) ? (ret >> 8) : SLOT_MAXROWS;       // (an environment that left the packed path: assume it is heavy)
     const int need = (live && !stored) ? 1 : 0;
@@ -558,7 +569,7 @@ DM_DEV void slot_rollout(const DevModel<R>& M_in, const Batch<R>& B, SlotShared<
       any = true;
       const int e = dmw::bcast_i(env, SW * k);
       dmw::sync_mem();
-      restep_one_env<R, NR>(&M, &B, &one_s, &one_x, e, lane, a_t, o_t, r_t, d_t, n_substeps DM_CALL_SLOT_ARG);
+      restep_one_env<R, NR, SPD>(&M, &B, &one_s, &one_x, e, lane, a_t, o_t, r_t, d_t, n_substeps DM_CALL_SLOT_ARG);
       if (lane == 0) dmw::global_counter_next(B.redo_why);       // running total (dm_batch_redo_total)
       dmw::sync_mem();
     }

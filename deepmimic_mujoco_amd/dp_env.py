@@ -420,8 +420,14 @@ class DPVecEnv(object):
     def __init__(self, num_envs, motion="walk", xml_path=None, device=0, reward="alive", autoreset="rsi", seed=0,
                  contacts=True, limits=True, action_mode="raw", env_offset=0, batch_factory=None, frame_skip=None, diagnostics=False, dtype=64, packed=None,
                  step_queue=0, obs_mode="dp_env_v3", fall_contact_bodies=None, max_episode_steps=0, truncation_log=0, reward_terms=False,
-                 horizon_termination=False, clip_weights=None, clip_mode="fixed", perturb=None):
-        """perturb: external pushes on a random schedule (perturb.PushSchedule, a dict of its arguments, or the trainers' "bodies=...,force=a:b,..." string;
+                 horizon_termination=False, clip_weights=None, clip_mode="fixed", perturb=None, horizon_spd=False):
+        """horizon_spd (DM_OPT_HORIZON_SPD; action_mode "spd-target" / "spd-mocap" only, else ValueError; ValueError with obs_mode="deepmimic", which has no
+        horizon launch): keep the one-launch horizon in the two PD-target modes — `Batch.rollout`, the fused collector and the step queue run a horizon
+        kernel with the stable PD controller inside every wavefront's loop, with the step launches' results (bit for bit with packed=2; with packed=True an
+        env-step at 33..40 constraint rows agrees to rounding: include/dmenv.h).  It takes effect where `Batch.rollout` uses one launch per horizon at all (a
+        packed batch); a list of motions and `perturb` pass through, and the library issues step launches for them.  Together with `horizon_termination` the
+        horizon kernel carries both.  Off (default): these modes' horizons and queued steps are step launches.  profiles/spd_horizon.md has the measurements.
+        perturb: external pushes on a random schedule (perturb.PushSchedule, a dict of its arguments, or the trainers' "bodies=...,force=a:b,..." string;
         None: off) — a random force on a random body of the set for a few env steps, again and again over every episode (DeepMimic's perturbations).  While
         it is on, one more launch precedes every step launch; horizon launches and the step queue run as step launches.  `push` applies scripted impulses
         at any time, `push_state()` reads the schedule's records.
@@ -447,7 +453,7 @@ class DPVecEnv(object):
         the fused collector and the step queue run a horizon kernel with the termination rule inside every wavefront's loop (step, termination, then the
         policy's step), with the step launches' results.  The flag takes effect where `Batch.rollout` uses one launch per horizon at all (a packed batch: `packed=True` / 2, the automatic choice, or a collector that
         picks the packed horizon — `horizon_packed_ok`); on a one-env batch it changes nothing.  ValueError for the two combinations that never have a horizon launch: the
-        "spd-target" / "spd-mocap" action modes and obs_mode="deepmimic".
+        "spd-target" / "spd-mocap" action modes without `horizon_spd`, and obs_mode="deepmimic".
         reward="imitation": the 5-term reward of code.md:1017-1143 (imitation.py) against the frame after the current one.
         frame_skip: sim steps per env step (src/dp_env_v3.py:108-112 hard-codes 1); "mocap" = floor(mocap_dt / timestep), the
         commented intent of :107-110, so that one env step spans one mocap frame.  Default (None): 1, except "mocap" for the
@@ -467,7 +473,7 @@ class DPVecEnv(object):
         faster at any size.
         action_mode: one of ACTION_MODES.  "spd-target" / "spd-mocap": the action is a PD target pose, tracked by a stable PD controller evaluated at every
         simulation substep (include/dmenv.h DM_OPT_ACTION_MODE); `action_space` is then the hinges' joint range ("spd-target") — informative, not enforced.
-        These two modes run on the per-step kernels: horizon launches and the step queue fall back to step launches with identical results.
+        These two modes run on the per-step kernels: horizon launches and the step queue fall back to step launches with identical results, unless `horizon_spd`.
         "p-control", "pd" and "spd-mocap" track the mocap frame the env is at as the env step starts — the frame its `reward` counts from: the frame cursor
         itself, but (cursor + drawn frame) % n_frames with reward="v2-pose" and (cursor // update interval + drawn frame) % n_frames with "v1-quat",
         whose cursors count the episode's steps.
@@ -479,10 +485,16 @@ class DPVecEnv(object):
         every `step` is executed at once, as in the closed loop."""
         self.num_envs = int(num_envs)
         self.horizon_termination = bool(horizon_termination)
+        self.horizon_spd = bool(horizon_spd)
+        if self.horizon_spd:                       # (refused before anything touches a device)
+            if action_mode not in ("spd-target", "spd-mocap"):
+                raise ValueError("horizon_spd=True runs the stable PD controller inside the horizon launch: it needs action_mode \"spd-target\" or \"spd-mocap\", not %r" % (action_mode,))
+            if obs_mode == "deepmimic":
+                raise ValueError("horizon_spd=True: obs_mode=\"deepmimic\" takes a features launch after every step, there is no horizon launch to run the controller in")
         if self.horizon_termination:               # (refused before anything touches a device)
             if not (fall_body_mask(fall_contact_bodies) or int(max_episode_steps)):
                 raise ValueError("horizon_termination=True runs early termination inside the horizon launch: it needs fall_contact_bodies or max_episode_steps")
-            if action_mode in ("spd-target", "spd-mocap"):
+            if action_mode in ("spd-target", "spd-mocap") and not self.horizon_spd:
                 raise ValueError("horizon_termination=True: action_mode=%r runs on the per-step kernels, there is no horizon launch to terminate in" % (action_mode,))
             if obs_mode == "deepmimic":
                 raise ValueError("horizon_termination=True: obs_mode=\"deepmimic\" takes a features launch after every step, there is no horizon launch to terminate in")
@@ -562,6 +574,8 @@ class DPVecEnv(object):
             b.set_option(A.OPT_TRUNCATION_LOG, int(truncation_log))
         if self.horizon_termination:
             b.set_option(A.OPT_HORIZON_TERMINATION, 1)
+        if self.horizon_spd:
+            b.set_option(A.OPT_HORIZON_SPD, 1)
         self.perturb = None
         if perturb is not None:
             from .perturb import PushSchedule

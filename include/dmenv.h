@@ -151,7 +151,8 @@ enum {
                                tau = p + d - h kd a,  ctrl = tau / gear;  actuator force = gear * clamp(ctrl, ctrlrange)
                              The target is not clamped.  DM_F_CTRL (and the control cost of reward modes 2 and 4) is the last substep's
                              unclamped ctrl.  Modes 3 and 4 run on the per-step kernels, one-env and DM_OPT_PACKED, with or without the
-                             fused policy step; dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches for them (see there). */
+                             fused policy step; dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches for them (see there), unless
+                             DM_OPT_HORIZON_SPD (below). */
   DM_OPT_SEED = 4,
   DM_OPT_DIAGNOSTICS = 5, /* 1 (default): every step also stores sim.data.xipos and the contact (geom1, geom2) list (DM_F_XIPOS,
                              DM_F_CONTACT_GEOMS: 848 B per env-step); 0: state, obs, reward, done and the row / contact counts only —
@@ -192,7 +193,7 @@ enum {
                              queued, i.e. degenerates to one launch per call.  Results are bit-identical to unqueued DM_OPT_PACKED
                              steps.  Queuing applies where dm_batch_rollout uses one launch per horizon (DM_OPT_PACKED on, reward modes
                              0..3, action modes 0..2, constraint rows, at most two packed waves per SIMD); elsewhere — action modes 3 and
-                             4 among it: nothing is queued, dm_batch_queue_stats stays 0 — calls launch at once as without it.
+                             4 among it, unless DM_OPT_HORIZON_SPD: nothing is queued, dm_batch_queue_stats stays 0 — calls launch at once as without it.
                              dm_batch_destroy() DROPS what is still queued (the buffers belong to the caller and may be gone). */
   DM_OPT_FALL_BODIES = 9, /* DeepMimic's early termination by fall contact (--fall_contact_bodies).  A bit mask over model bodies, bit b for
                              body b = 1..13; 0 (default): off.  An environment FALLS when a geom of a body in the mask touches the floor
@@ -210,7 +211,7 @@ enum {
                              the fresh episode's observation row.  Host-pointer steps copy out after this launch.  The step kernels carry
                              no termination code: with both options 0 nothing is launched and nothing changes.  Neither do the horizon
                              launch and the step queue, unless DM_OPT_HORIZON_TERMINATION: while an option is on and that one is not, dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches
-                             (as for action modes 3 and 4; dm_batch_queue_stats stays 0), and dm_batch_step_act and the policy rows of
+                             (as for action modes 3 and 4 unless DM_OPT_HORIZON_SPD; dm_batch_queue_stats stays 0), and dm_batch_step_act and the policy rows of
                              dm_batch_rollout run as the plain step launch, the termination launch, then the launch behind dm_policy_act
                              on the returned observations (over the whole batch, after the parts of a pipelined step have joined): the
                              result of dm_batch_step followed by dm_policy_act, bit for bit. */
@@ -229,7 +230,7 @@ enum {
   DM_OPT_HORIZON_TERMINATION = 12 /* 0 (default): as described under DM_OPT_MAX_EPISODE_STEPS — while early termination is on, dm_batch_rollout and
                              DM_OPT_STEP_QUEUE issue step launches, each followed by the termination launch.  1: early termination no longer keeps a
                              batch from the one-launch horizon.  Where dm_batch_rollout would use one launch per horizon without termination
-                             (DM_OPT_PACKED on, action modes 0..2, constraint rows, at most two packed waves per SIMD — the conditions are unchanged)
+                             (DM_OPT_PACKED on, action modes 0..2 — 3 and 4 with DM_OPT_HORIZON_SPD —, constraint rows, at most two packed waves per SIMD — the conditions are unchanged)
                              it does so with it, and DM_OPT_STEP_QUEUE queues again (dm_batch_queue_stats counts): the launch is a second horizon
                              kernel (k_rollout_packed_term) with the termination rule inside every wavefront's loop.  Order within a step of the
                              horizon: the step (with its in-wave re-steps), then termination on the state it left, then — dm_batch_rollout with
@@ -247,7 +248,7 @@ enum {
                              horizon launch while DM_OPT_PACKED 1's step launches hand it to the one-env code, whose float64 sums differ in the last
                              bits (with or without termination; measured 1e-14 on observations): done flags, reasons, counters, cursors and the
                              records' ticks and environments stay equal, float rows and state agree to rounding.  Values other than 0 and 1: DM_EINVAL.  Without early termination, and for
-                             everything that is not a horizon launch (dm_batch_step unqueued, dm_batch_step_act, action modes 3 and 4), the option
+                             everything that is not a horizon launch (dm_batch_step unqueued, dm_batch_step_act, action modes 3 and 4 unless DM_OPT_HORIZON_SPD), the option
                              changes nothing.  Measured on an MI355X (profiles/term_horizon.md): a 128-step fused rollout 1.66x faster at 4096 envs, 1.38x at 8192. */
 };
 /* bits of DM_F_DONE_REASON */
@@ -270,7 +271,25 @@ enum {
  * drawn as always, over that clip's n_frames, and DM_F_CLIP is stored with the cursors.  On a single-clip batch the option is accepted and changes
  * nothing.  Other values: DM_EINVAL. */
 #define DM_OPT_CLIP_MODE 13
-#define DM_MAX_CLIPS 32      /* clips of a clip set (dm_mocap_create_set) */
+/* DM_OPT_HORIZON_SPD: an option of dm_batch_set_option like those of the enum above, for action modes 3 and 4 (DM_OPT_ACTION_MODE).  0 (default): as
+ * described there — dm_batch_rollout and DM_OPT_STEP_QUEUE issue step launches in those modes (the fused policy step inside them), and dm_batch_queue_stats
+ * stays 0.  1: action modes 3 and 4 no longer keep a batch from the one-launch horizon.  Where dm_batch_rollout would use one launch per horizon in modes
+ * 0..2 (DM_OPT_PACKED on, a single-clip batch without a push schedule, constraint rows, at most two packed waves per SIMD, early termination off or
+ * DM_OPT_HORIZON_TERMINATION on — the conditions are unchanged) it does so in modes 3 and 4, and DM_OPT_STEP_QUEUE queues again (dm_batch_queue_stats
+ * counts): the launch is a horizon kernel with the stable PD controller inside every wavefront's loop (k_rollout_packed_spd; with early termination on and
+ * DM_OPT_HORIZON_TERMINATION 1, k_rollout_packed_term_spd).  Order within a step of the horizon: at the start of every substep the control pass on the state
+ * that substep starts at, then the substep; after the last substep the step's epilogue; the in-wave re-steps of environments beyond the packed capacities,
+ * by the one-env code with the same controller; then — DM_OPT_HORIZON_TERMINATION — termination on the state the step left; then — dm_batch_rollout with
+ * weights — the policy's step.  DM_F_CTRL is the last substep's unclamped ctrl, as after a step launch.  The result is bit for bit the step launches' where
+ * both forms run the same step code: DM_OPT_PACKED 2, or DM_OPT_PACKED 1 while no environment holds 33..40 constraint rows.  An env-step at 33..40 rows stays
+ * on the packed three-set code in any horizon launch while DM_OPT_PACKED 1's step launches hand it to the one-env code, whose float64 sums differ in the last
+ * bits: discrete outputs stay equal, float rows and state agree to rounding (with termination, the caveat of DM_OPT_HORIZON_TERMINATION about a geom within
+ * rounding of the touch boundary holds as well).  The policy rows are bit for bit those of dm_batch_step_act step after step (with early termination on:
+ * of dm_batch_step, the termination launch and dm_policy_act).  A multi-clip batch and a batch with a push schedule still run step launches, with the
+ * option too; in action modes 0..2 the option changes nothing: a batch that leaves it 0 never runs the second pair of horizon kernels.  Values other than
+ * 0 and 1: DM_EINVAL.  Measurements: profiles/spd_horizon.md. */
+#define DM_OPT_HORIZON_SPD 14
+#define DM_MAX_CLIPS 32     /* clips of a clip set (dm_mocap_create_set) */
 /* further option ids (diagnostics / tests; defaults are what the timed path uses):
  *   100 global id of env 0 of this batch (multi-GPU sharding: RNG streams are keyed by the global env id)
  *   101 per-stage shader-clock profile (k_step_prof + dm_batch_read_profile)
@@ -528,7 +547,7 @@ int dm_batch_step_act(dm_batch* b, const double* action, double* obs, double* re
  * horizon is ONE launch: every wavefront steps its four environments T times at its own pace, so the horizon lasts as long as the slowest
  * wave's sum over T steps instead of the sum of every step's slowest wave (4 096 envs: 17.3 M env-steps/s against 12.2 M through
  * dm_batch_step); an environment that exceeds the packed path's capacities in some step is re-stepped inside its wave by the one-env code.
- * Otherwise — always in action modes 3 and 4, whose controller lives in the per-step kernels — T step launches are issued: the results are those
+ * Otherwise — in action modes 3 and 4 unless DM_OPT_HORIZON_SPD, whose horizon kernels carry the controller — T step launches are issued: the results are those
  * of T dm_batch_step / dm_batch_step_act calls, bit for bit.  `weights`, when given, must be 16-byte aligned (DM_EINVAL otherwise). */
 int dm_batch_rollout(dm_batch* b, double* action, double* obs, double* reward, uint8_t* done, int32_t T, int32_t n_substeps,
                      const float* weights, float* vpred, int32_t stochastic, uint64_t seed, uint64_t counter);

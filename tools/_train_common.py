@@ -8,7 +8,7 @@ from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
 
 
 def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None):
-    """--motion, --clip-weights, --clip-mode, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --bootstrap-time-limit, --log-reward-terms, --perturb and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
+    """--motion, --clip-weights, --clip-mode, --obs-mode, --action-mode, --fall-contact, --max-episode-steps, --horizon-termination, --horizon-spd, --bootstrap-time-limit, --log-reward-terms, --perturb and, of --reward, --autoreset and --frame-skip, those whose help text (the scripts' differ) is given."""
     ap.add_argument("--motion", default="walk", help="the clip to imitate, or a comma-separated list (walk,spinkick,kick): one policy on a set of clips, env e on clip e mod K")
     ap.add_argument("--clip-weights", default=None, help="with a list of motions: comma-separated draw probabilities of --clip-mode episode (up to their sum; default uniform)")
     ap.add_argument("--clip-mode", default="fixed", choices=["fixed", "episode"],
@@ -28,7 +28,10 @@ def add_env_args(ap, reward_help=None, autoreset_help=None, frame_skip_help=None
                     help="the episode's time limit in env steps (0 = none).  Without --bootstrap-time-limit a time-limit done is a done like any other: the state it cuts off is worth 0")
     ap.add_argument("--horizon-termination", action="store_true",
                     help="run early termination inside the horizon launch (DM_OPT_HORIZON_TERMINATION) instead of a termination launch behind every step launch: "
-                         "needs --fall-contact or --max-episode-steps, and an action / observation mode with a horizon launch (not spd-*, not --obs-mode deepmimic)")
+                         "needs --fall-contact or --max-episode-steps, and an action / observation mode with a horizon launch (not --obs-mode deepmimic; spd-* only with --horizon-spd)")
+    ap.add_argument("--horizon-spd", action="store_true",
+                    help="--action-mode spd-target / spd-mocap: run the stable PD controller inside the horizon launch (DM_OPT_HORIZON_SPD) instead of one step launch per step; "
+                         "not with --obs-mode deepmimic")
     ap.add_argument("--bootstrap-time-limit", action="store_true",
                     help="treat a time-limit end as a truncation (DeepMimic's agent): the value target bootstraps from the critic's value of the state the limit cut off, "
                          "where a fall keeps 0.  Needs --max-episode-steps")
@@ -65,10 +68,15 @@ def check_env_args(ap, args):
             ap.error("--clip-weights: one weight per motion (%d), got %d" % (len(motions(args)), len(w)))
     if getattr(args, "bootstrap_time_limit", False) and not args.max_episode_steps > 0:
         ap.error("--bootstrap-time-limit bootstraps the value where the time limit ends an episode: it needs --max-episode-steps M with M > 0")
+    if getattr(args, "horizon_spd", False):
+        if args.action_mode not in ("spd-target", "spd-mocap"):
+            ap.error("--horizon-spd runs the stable PD controller inside the horizon launch: it needs --action-mode spd-target or spd-mocap")
+        if args.obs_mode == "deepmimic":
+            ap.error("--horizon-spd: --obs-mode deepmimic has no horizon launch")
     if getattr(args, "horizon_termination", False):
         if args.fall_contact == "none" and not args.max_episode_steps > 0:
             ap.error("--horizon-termination runs early termination inside the horizon launch: it needs --fall-contact or --max-episode-steps")
-        if args.action_mode in ("spd-target", "spd-mocap") or args.obs_mode == "deepmimic":
+        if (args.action_mode in ("spd-target", "spd-mocap") and not getattr(args, "horizon_spd", False)) or args.obs_mode == "deepmimic":
             ap.error("--horizon-termination: --action-mode spd-* and --obs-mode deepmimic have no horizon launch")
     if getattr(args, "perturb", None):
         from deepmimic_mujoco_amd.perturb import PushSchedule
@@ -88,7 +96,7 @@ def env_kwargs(args):
                 reward=args.reward, action_mode=args.action_mode, obs_mode=args.obs_mode,
                 frame_skip=fs if fs in (None, "mocap") else int(fs),
                 fall_contact_bodies=None if args.fall_contact == "none" else args.fall_contact, max_episode_steps=args.max_episode_steps,
-                horizon_termination=bool(getattr(args, "horizon_termination", False)), perturb=getattr(args, "perturb", None))
+                horizon_termination=bool(getattr(args, "horizon_termination", False)), horizon_spd=bool(getattr(args, "horizon_spd", False)), perturb=getattr(args, "perturb", None))
 
 
 def init_device(dist_backend):
