@@ -12,27 +12,33 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 
+def load_lib(directory, so_name):
+    """builds a testbench library (tests/emu/testbench.mk has the flags) and loads it, with the prototypes of the emu_* entry points, which all three have"""
+    subprocess.check_call(["make", "-C", directory, "-s"])
+    L = C.CDLL(os.path.join(directory, so_name))
+    u8p = C.POINTER(C.c_uint8)
+    L.emu_create.restype = C.c_void_p
+    L.emu_create.argtypes = [C.POINTER(A.ModelDesc), A._dp, A._dp, C.c_int, C.c_int, C.c_uint, C.c_double]
+    L.emu_destroy.argtypes = [C.c_void_p]
+    L.emu_invalidate_kin.argtypes = [C.c_void_p]
+    L.emu_set_option.argtypes = [C.c_void_p, C.c_int, C.c_longlong]
+    L.emu_set_imitation.argtypes = [C.c_void_p, A._dp, A._dp]
+    L.emu_field.restype = C.c_void_p
+    L.emu_field.argtypes = [C.c_void_p, C.c_int]
+    L.emu_step.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, u8p, C.c_int]
+    L.emu_set_state.argtypes = [C.c_void_p, A._dp, A._dp, A._ip, u8p]
+    L.emu_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p]
+    L.emu_redo_total.argtypes = [C.c_void_p]; L.emu_redo_total.restype = C.c_long
+    L.emu_rollout.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, u8p, C.c_int, C.c_int]
+    L.emu_debug_forward.argtypes = [C.c_void_p, C.c_int, A._dp]
+    L.emu_dispatch.argtypes = [C.c_int, C.c_int, C.c_int, A._ip, A._ip, A._ip, C.c_int, A._ip, C.c_int, A._ip, A._ip]
+    return L
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-        L = C.CDLL(os.path.join(_HERE, "libdmemu.so"))
-        L.emu_create.restype = C.c_void_p
-        L.emu_create.argtypes = [C.POINTER(A.ModelDesc), A._dp, A._dp, C.c_int, C.c_int, C.c_uint, C.c_double]
-        L.emu_destroy.argtypes = [C.c_void_p]
-        L.emu_invalidate_kin.argtypes = [C.c_void_p]
-        L.emu_set_option.argtypes = [C.c_void_p, C.c_int, C.c_longlong]
-        L.emu_set_imitation.argtypes = [C.c_void_p, A._dp, A._dp]
-        L.emu_field.restype = C.c_void_p
-        L.emu_field.argtypes = [C.c_void_p, C.c_int]
-        L.emu_step.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, C.POINTER(C.c_uint8), C.c_int]
-        L.emu_set_state.argtypes = [C.c_void_p, A._dp, A._dp, A._ip, C.POINTER(C.c_uint8)]
-        L.emu_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
-        L.emu_redo_total.argtypes = [C.c_void_p]; L.emu_redo_total.restype = C.c_long
-        L.emu_rollout.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, C.POINTER(C.c_uint8), C.c_int, C.c_int]
-        L.emu_debug_forward.argtypes = [C.c_void_p, C.c_int, A._dp]
-        L.emu_dispatch.argtypes = [C.c_int, C.c_int, C.c_int, A._ip, A._ip, A._ip, C.c_int, A._ip, C.c_int, A._ip, A._ip]
-        _LIB = L
+        _LIB = load_lib(_HERE, "libdmemu.so")
     return _LIB
 
 

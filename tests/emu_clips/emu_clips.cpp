@@ -1,7 +1,7 @@
 // emu_clips.cpp — TEST INFRASTRUCTURE: the wave testbench's front end for the clip instantiations of the step and reset routines (step_rules.h ClipArgs;
-// the device's kernels_clips.hip / kernels_packed_clips.hip), both lane layouts.  The fibre runner, the EmuBatch and the emu_* entry points are those of
-// ../emu/emu_main.cpp, compiled into this library as they are (which includes ../emu/wave_testbench.h and the unmodified kernel source); the emuc_* entry
-// points below add the clip set beside an EmuBatch, as the device keeps its ClipArgs beside the Batch.
+// the device's kernels_clips.hip / kernels_packed_clips.hip), both lane layouts.  The EmuBatch and the emu_* entry points are those of ../emu/emu_main.cpp,
+// compiled into this library as they are (with it the fibre runner of ../emu/wave_fibres.h, the host batch of ../emu/host_batch.h and the unmodified kernel
+// source); the emuc_* entry points below add the clip set beside an EmuBatch, as the device keeps its ClipArgs beside the Batch.
 #include "../emu/emu_main.cpp"
 
 namespace {
@@ -48,12 +48,12 @@ void emuc_step(void* h, const double* action, double* obs, double* reward, unsig
     for (int first = 0; first < n; first += SLOTS)
       run_wave([&](int lane) {
         const int slot = lane >> 4, sl = lane & 15;
-        stage_slot_tables(e->slot_tabs, lane);
+        stage_slot_tables(e->tabs, lane);
         int pos = first + slot;
         const bool live = pos < n;
         if (!live) pos = n - 1;
-        if (e->packed_ext) slot_env_step<double, false, false, SLOT_MAXROWS>(e->M, e->B, e->slots[slot], e->slot_tabs, pos, sl, lane, live, action, obs, reward, done, nsub, e->B.redo_count, e->B.redo_list, (long long*)0, false, ca);
-        else slot_env_step<double, false, false, 2 * SW>(e->M, e->B, e->slots[slot], e->slot_tabs, pos, sl, lane, live, action, obs, reward, done, nsub, e->B.redo_count, e->B.redo_list, (long long*)0, false, ca);
+        if (e->packed_ext) slot_env_step<double, false, false, SLOT_MAXROWS>(e->M, e->B, e->slots[slot], e->tabs, pos, sl, lane, live, action, obs, reward, done, nsub, e->B.redo_count, e->B.redo_list, (long long*)0, false, ca);
+        else slot_env_step<double, false, false, 2 * SW>(e->M, e->B, e->slots[slot], e->tabs, pos, sl, lane, live, action, obs, reward, done, nsub, e->B.redo_count, e->B.redo_list, (long long*)0, false, ca);
       });
     e->redo_total += e->B.redo_count[0];
     for (int i = 0; i < e->B.redo_count[0]; i++) {

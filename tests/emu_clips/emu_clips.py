@@ -2,12 +2,11 @@
 routines on CPU fibres, behind the interface of deepmimic_mujoco_amd.batch.Batch(..., clips=ClipSet) that the clip tests use."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from deepmimic_mujoco_amd import _abi as A
-from tests.emu.emu import EmuBatch
+from tests.emu.emu import EmuBatch, load_lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -17,8 +16,7 @@ _u8p = C.POINTER(C.c_uint8)
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-        L = C.CDLL(os.path.join(_HERE, "libdmemu_clips.so"))
+        L = load_lib(_HERE, "libdmemu_clips.so")        # (with the prototypes of the EmuBatch entry points compiled into this library)
         L.emuc_create.restype = C.c_void_p
         L.emuc_create.argtypes = [C.POINTER(A.ModelDesc), A._dp, A._dp, C.c_int, C.c_int, C.c_uint, C.c_int, A._ip, A._ip, A._dp, A._dp]
         L.emuc_set_imitation.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, A._dp, A._dp]
@@ -28,11 +26,6 @@ def lib():
         L.emuc_set_clip_mode.argtypes = [C.c_void_p, C.c_int]
         L.emuc_step.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, _u8p, C.c_int]
         L.emuc_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, _u8p]
-        # the EmuBatch entry points compiled into this library
-        L.emu_set_option.argtypes = [C.c_void_p, C.c_int, C.c_longlong]
-        L.emu_invalidate_kin.argtypes = [C.c_void_p]
-        L.emu_field.restype = C.c_void_p; L.emu_field.argtypes = [C.c_void_p, C.c_int]
-        L.emu_set_state.argtypes = [C.c_void_p, A._dp, A._dp, A._ip, _u8p]
         _LIB = L
     return _LIB
 

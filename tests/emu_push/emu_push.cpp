@@ -1,5 +1,6 @@
-// emu_push.cpp — TEST INFRASTRUCTURE: the wave testbench's front end for external pushes (csrc/push_kernel.h; the device's kernels_push.hip).  The fibre
-// runner, the EmuBatch and the emu_* entry points are those of ../emu/emu_main.cpp, compiled into this library as they are; the emup_* entry points below run the
+// emu_push.cpp — TEST INFRASTRUCTURE: the wave testbench's front end for external pushes (csrc/push_kernel.h; the device's kernels_push.hip).  The EmuBatch
+// and the emu_* entry points are those of ../emu/emu_main.cpp, compiled into this library as they are (with it the fibre runner of ../emu/wave_fibres.h and the
+// host batch of ../emu/host_batch.h); the emup_* entry points below run the
 // two kernels' waves (push_now_wave, push_schedule_wave — the unmodified kernel source) one environment after another, with the schedule's records kept by the
 // caller beside the EmuBatch, as the device keeps its PushArgs beside the Batch.
 #include "../emu/emu_main.cpp"

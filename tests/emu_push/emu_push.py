@@ -2,13 +2,12 @@
 deepmimic_mujoco_amd.batch.Batch (push, set_push_schedule, the two push fields) that the push tests use."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd.perturb import PushSchedule
-from tests.emu.emu import EmuBatch
+from tests.emu.emu import EmuBatch, load_lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -18,20 +17,9 @@ _u8p = C.POINTER(C.c_uint8)
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-        L = C.CDLL(os.path.join(_HERE, "libdmemu_push.so"))
+        L = load_lib(_HERE, "libdmemu_push.so")        # (with the prototypes of the EmuBatch entry points compiled into this library)
         L.emup_push.argtypes = [C.c_void_p, A._ip, A._dp, _u8p]
         L.emup_schedule.argtypes = [C.c_void_p, C.POINTER(A.PushDesc), A._ip, A._dp, C.c_double]
-        # the EmuBatch entry points compiled into this library
-        L.emu_create.restype = C.c_void_p
-        L.emu_create.argtypes = [C.POINTER(A.ModelDesc), A._dp, A._dp, C.c_int, C.c_int, C.c_uint, C.c_double]
-        L.emu_destroy.argtypes = [C.c_void_p]
-        L.emu_set_option.argtypes = [C.c_void_p, C.c_int, C.c_longlong]
-        L.emu_invalidate_kin.argtypes = [C.c_void_p]
-        L.emu_field.restype = C.c_void_p; L.emu_field.argtypes = [C.c_void_p, C.c_int]
-        L.emu_step.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, _u8p, C.c_int]
-        L.emu_set_state.argtypes = [C.c_void_p, A._dp, A._dp, A._ip, _u8p]
-        L.emu_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, _u8p]
         _LIB = L
     return _LIB
 

@@ -6,12 +6,9 @@
 //   in.bin (float64): n, F | body_pos [14,3], body_ipos [14,3], body_mass [14], body_inertia [14,9], jnt_axis [29,3] (the model constants the
 //   kinematics and the reward read) | params [32] | table [F,112] | n x { qpos [35], qvel [34], frame, cycle }
 //   out.bin: [n, 28] float64; a frame outside [0, F) gives a row of NaNs, as on the device
-#include <ucontext.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <vector>
 
 #include "wave_testbench.h"
@@ -27,43 +24,9 @@ inline float wave_sum(float v) {
 // kernel source, unmodified
 #include "env_step.h"
 
-namespace dmw {
-static WaveBench g_bench;
-WaveBench& bench() { return g_bench; }
-}  // namespace dmw
+#include "wave_fibres.h"      // the fibre runner: dmw::bench(), run_wave
 
 namespace {
-constexpr size_t STACK = 1 << 20;
-ucontext_t g_main, g_fib[64];
-bool g_done[64];
-std::function<void(int)>* g_body;
-char* g_stacks;
-
-void yield_to_main() { swapcontext(&g_fib[dmw::g_bench.cur_lane], &g_main); }
-void fibre_entry() {
-  const int l = dmw::g_bench.cur_lane;
-  (*g_body)(l);
-  g_done[l] = true;
-  swapcontext(&g_fib[l], &g_main);
-}
-// run body(lane) on 64 fibres to completion
-void run_wave(std::function<void(int)> body) {
-  if (!g_stacks) g_stacks = (char*)malloc(STACK * 64);
-  g_body = &body;
-  dmw::g_bench.arrived = 0; dmw::g_bench.gen = 0; dmw::g_bench.yield_fn = yield_to_main;
-  for (int l = 0; l < 64; l++) {
-    g_done[l] = false;
-    getcontext(&g_fib[l]);
-    g_fib[l].uc_stack.ss_sp = g_stacks + STACK * l; g_fib[l].uc_stack.ss_size = STACK; g_fib[l].uc_link = &g_main;
-    makecontext(&g_fib[l], fibre_entry, 0);
-  }
-  for (;;) {
-    bool all = true;
-    for (int l = 0; l < 64; l++) if (!g_done[l]) { all = false; dmw::g_bench.cur_lane = l; swapcontext(&g_main, &g_fib[l]); }
-    if (all) break;
-  }
-}
-
 using namespace dm;
 
 template <class R>

@@ -4,7 +4,6 @@ kernel source on CPU fibres under the sanitizers, slot_rollout with the controll
 step launches run them, bit for bit.  tests/test_gpu_horizon_spd.py has the device."""
 import os
 import re
-import shutil
 import subprocess
 import time
 
@@ -16,6 +15,7 @@ from deepmimic_mujoco_amd import DPVecEnv
 from deepmimic_mujoco_amd import termination as T
 from tests import helpers as H
 from tests import horizon_term_cases as HC
+from tests.emu import hostprog as HP
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -100,32 +100,12 @@ def test_train_tools_take_and_check_the_flag(capsys):
 MANY_ENV = 4          # the env that starts in a many-row state: the first slot of the second wave
 
 
-def _arrays(cm, mc, table, params, cfg, idx, q, v, act4, act3):
-    """the host program's input, in the order its main() reads (int32 / float64 arrays)"""
-    i = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
-    d = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-    return [i([cm.nbody, cm.njnt, cm.nq, cm.nv, cm.nu, cm.ngeom, cm.npair, cm.iterations]),
-            i(cm.body_parentid), i(cm.body_dofnum), d(cm.body_pos), d(cm.body_ipos), d(cm.body_mass), d(cm.body_inertia), d(cm.body_invweight0),
-            i(cm.jnt_type), i(cm.jnt_bodyid), i(cm.jnt_limited), d(cm.jnt_axis), d(cm.jnt_range),
-            d(cm.dof_armature), d(cm.dof_damping), d(cm.dof_invweight0),
-            i(cm.geom_type), i(cm.geom_bodyid), i(cm.geom_condim), d(cm.geom_pos), d(cm.geom_mat), d(cm.geom_size), d(cm.geom_margin), d(cm.geom_friction),
-            i(cm.pair_geom), i(cm.actuator_dofid), d(cm.actuator_gear), d(cm.actuator_ctrlrange),
-            d([cm.timestep] + list(cm.gravity) + [cm.tolerance] + list(cm.solref) + list(cm.solimp) + [cm.meaninertia, float(mc.dt)]),
-            d(mc.data_config), d(mc.data_vel), d(table), d(params), i(cfg), d(q), d(v), i(idx), d(act4), d(act3)]
-
-
 def test_horizon_with_the_controller_equals_step_launches_on_the_wave_testbench(tmp_path):
     """6 envs (one full wave and one with two spare slots), 3 steps (5 ran longer than the termination twin: 148 s against 90 s) of 2 substeps of walk under the 5-term reward, RSI auto-reset, float64; action mode 4 then
     mode 3, each without and with the termination phase (the "deepmimic" fall set and a limit of 3 steps).  The program fails unless every horizon held a
     step taken with carried kinematics, an in-wave re-step of the env that starts in a helpers.many_row_states state, and an auto-reset that a step follows
     (mode 4 then reads the fresh cursor)."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/spd_rollout_host.cpp")
-    exe = str(tmp_path / "spd_rollout_host")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-DDM_WAVE_TESTBENCH", "-ffp-contract=off", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "tests", "emu"), "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "spd_rollout_host.cpp"), "-o", exe])
+    exe = HP.build_host("spd_rollout_host.cpp", tmp_path / "spd_rollout_host", testbench=True, sanitize=True, opt=("-O1",))
     n, Tn, nsub, limit = 6, 3, 2, 3
     cm, mc = H.compiled_model(), H.mocap("walk")
     from deepmimic_mujoco_amd.imitation import ImitationSpec
@@ -137,9 +117,9 @@ def test_horizon_with_the_controller_equals_step_launches_on_the_wave_testbench(
     act4, act3 = off, mc.data_config[idx][None, :, 7:] + off          # mode 4: offsets from the frame the env is at; mode 3: target poses around the starting frames
     cfg = [n, Tn, nsub, HC.STATE_SEED, T.fall_body_mask("deepmimic"), limit, 1, 3, mc.data_config.shape[0], MANY_ENV]
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(fin, "wb") as f:
-        for a in _arrays(cm, mc, table, params, cfg, idx, q, v, act4, act3):
-            f.write(np.int32(0 if a.dtype == np.int32 else 1).tobytes()); f.write(np.int64(a.size).tobytes()); f.write(a.tobytes())
+    # the program's input, in the order its main() reads: the model, the clip, the reward's table and parameters, the run, the states, the actions of both modes
+    HP.write_arrays(fin, HP.model_arrays(cm, mc.dt) + [HP.f64(mc.data_config), HP.f64(mc.data_vel), HP.f64(table), HP.f64(params), HP.i32(cfg), HP.f64(q), HP.f64(v),
+                                                       HP.i32(idx), HP.f64(act4), HP.f64(act3)])
     t0 = time.time()
     r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=1500)
     print(r.stdout.strip())

@@ -4,7 +4,6 @@ fibres under the sanitizers, the horizon with the termination phase inside again
 tests/test_gpu_horizon_termination.py has the device."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ from deepmimic_mujoco_amd import DPVecEnv
 from deepmimic_mujoco_amd import termination as T
 from tests import helpers as H
 from tests import horizon_term_cases as HC
+from tests.emu import hostprog as HP
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -75,31 +75,11 @@ def test_train_tools_take_and_check_the_flag(capsys):
 
 
 # ---- the twin on the wave testbench -----------------------------------------------------------------------------------------------------------
-def _arrays(cm, mc, table, params, cfg, idx, q, v, act):
-    """the host program's input, in the order its main() reads (int32 / float64 arrays)"""
-    i = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
-    d = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-    return [i([cm.nbody, cm.njnt, cm.nq, cm.nv, cm.nu, cm.ngeom, cm.npair, cm.iterations]),
-            i(cm.body_parentid), i(cm.body_dofnum), d(cm.body_pos), d(cm.body_ipos), d(cm.body_mass), d(cm.body_inertia), d(cm.body_invweight0),
-            i(cm.jnt_type), i(cm.jnt_bodyid), i(cm.jnt_limited), d(cm.jnt_axis), d(cm.jnt_range),
-            d(cm.dof_armature), d(cm.dof_damping), d(cm.dof_invweight0),
-            i(cm.geom_type), i(cm.geom_bodyid), i(cm.geom_condim), d(cm.geom_pos), d(cm.geom_mat), d(cm.geom_size), d(cm.geom_margin), d(cm.geom_friction),
-            i(cm.pair_geom), i(cm.actuator_dofid), d(cm.actuator_gear), d(cm.actuator_ctrlrange),
-            d([cm.timestep] + list(cm.gravity) + [cm.tolerance] + list(cm.solref) + list(cm.solimp) + [cm.meaninertia, float(mc.dt)]),
-            d(mc.data_config), d(mc.data_vel), d(table), d(params), i(cfg), d(q), d(v), i(idx), d(act)]
-
-
 def test_horizon_with_termination_equals_step_launches_on_the_wave_testbench(tmp_path):
     """10 envs (two full waves and one with two spare slots), 7 steps of walk under the 5-term reward, RSI auto-reset, the "deepmimic" fall set and a limit
     of 3 steps, float64; then the same with the fall set off and the truncation log on.  The program fails unless the horizon held a fall, a time-limit
     end, a step-own done, a re-step and a truncation record."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/term_rollout_host.cpp")
-    exe = str(tmp_path / "term_rollout_host")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-DDM_WAVE_TESTBENCH", "-ffp-contract=off", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "tests", "emu"), "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "term_rollout_host.cpp"), "-o", exe])
+    exe = HP.build_host("term_rollout_host.cpp", tmp_path / "term_rollout_host", testbench=True, sanitize=True, opt=("-O1",))
     n, Tn, limit = 10, 7, 3
     cm, mc = H.compiled_model(), H.mocap("walk")
     from deepmimic_mujoco_amd.imitation import ImitationSpec
@@ -108,9 +88,9 @@ def test_horizon_with_termination_equals_step_launches_on_the_wave_testbench(tmp
     act = HC.actions(Tn, n)
     cfg = [n, Tn, 1, HC.STATE_SEED, T.fall_body_mask("deepmimic"), limit, 1, 3, mc.data_config.shape[0]]      # n, T, substeps, seed, fall set, limit, RSI, imitation, frames
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(fin, "wb") as f:
-        for a in _arrays(cm, mc, table, params, cfg, idx, q, v, act):
-            f.write(np.int32(0 if a.dtype == np.int32 else 1).tobytes()); f.write(np.int64(a.size).tobytes()); f.write(a.tobytes())
+    # the program's input, in the order its main() reads: the model, the clip, the reward's table and parameters, the run, the states, the actions
+    HP.write_arrays(fin, HP.model_arrays(cm, mc.dt) + [HP.f64(mc.data_config), HP.f64(mc.data_vel), HP.f64(table), HP.f64(params), HP.i32(cfg), HP.f64(q), HP.f64(v),
+                                                       HP.i32(idx), HP.f64(act)])
     r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=1500)
     print(r.stdout.strip())
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -12,7 +12,6 @@ does not return take their bar from the column they add up to, which they cannot
   [24..28)  the end effectors' squared distances, whose sum / 4 is column 2                                -> 4 bar[2]
 The observed ratios are recorded in profiles/terms_kernels.md."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -22,6 +21,7 @@ from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import imitation as IM
 from deepmimic_mujoco_amd.batch import Batch
 from tests import helpers as H
+from tests.emu import hostprog as HP
 from tests import terms_numpy as TN
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -162,13 +162,7 @@ def test_reward_from_errors():
 # ---- the lane code on the wave testbench ------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def terms_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/terms_host.cpp")
-    out = str(tmp_path_factory.mktemp("terms_host") / "terms_host")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-DDM_WAVE_TESTBENCH", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "tests", "emu"), "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "terms_host.cpp"), "-o", out])
+    out = HP.build_host("terms_host.cpp", tmp_path_factory.mktemp("terms_host") / "terms_host", testbench=True, opt=("-O1", "-g"))
     return out
 
 
@@ -272,12 +266,7 @@ def test_method_refuses_bad_arguments_before_the_library():
 
 # ---- the fourth view's staging layout, under the sanitizers ------------------------------------------------------------------------------
 def test_terms_staging_layout_under_the_sanitizers(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/terms_stage_host.cpp")
-    exe = str(tmp_path / "terms_stage_host")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), os.path.join(ROOT, "tests", "terms_stage_host.cpp"), "-o", exe])
+    exe = HP.build_host("terms_stage_host.cpp", tmp_path / "terms_stage_host", sanitize=True, opt=("-O1", "-g"))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     # 5 sizes x 2 callers x 2^6 presence masks of the six arrays dm_batch_imitation_terms declares

@@ -2,7 +2,6 @@
 (tests/render_numpy.py) against analytic cases, csrc/render.h built for the host against that restatement, tile_images and
 the frame writer.  The GPU kernels are checked against the same restatement in tests/test_gpu_render.py."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,6 +12,7 @@ from deepmimic_mujoco_amd.humanoid import humanoid_visual
 from deepmimic_mujoco_amd.mjcf import load_visual
 from tests import helpers as H
 from tests import render_numpy as RN
+from tests.emu import hostprog as HP
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN_XML = os.path.join(ROOT, "tests", "golden", "dp_env_v3.xml")
@@ -131,12 +131,7 @@ def test_a_geom_above_a_floor_point_shadows_it():
 # ---- csrc/render.h on the host ----------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def render_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/render_host.cpp")
-    out = str(tmp_path_factory.mktemp("render_host") / "render_host")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "render_host.cpp"), "-o", out])
+    out = HP.build_host("render_host.cpp", tmp_path_factory.mktemp("render_host") / "render_host", abi=True)
     return out
 
 

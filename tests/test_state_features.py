@@ -5,7 +5,6 @@ those matrices in test_restatement_agrees_with_the_package_kinematics): of the q
 product and the sign rule, not the composition down the tree — that is the kernel's kinematics, checked on the GPU against the same
 restatement (tests/test_gpu_state.py)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 from deepmimic_mujoco_amd import _abi as A
 from tests import helpers as H
 from tests import state_numpy as SN
+from tests.emu import hostprog as HP
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 CLIPS = ("walk", "spinkick", "dance_b")
@@ -135,11 +135,7 @@ def test_package_layout_and_phase_of():
 # ---- csrc/state_features.h on the host --------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def state_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/state_host.cpp")
-    out = str(tmp_path_factory.mktemp("state_host") / "state_host")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), os.path.join(ROOT, "tests", "state_host.cpp"), "-o", out])
+    out = HP.build_host("state_host.cpp", tmp_path_factory.mktemp("state_host") / "state_host")
     return out
 
 

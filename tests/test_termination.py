@@ -3,7 +3,6 @@ contact list, csrc/floor_contact.h built for the host against that restatement i
 the ABI constants."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,6 +12,7 @@ from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import termination as T
 from tests import floor_numpy as FN
 from tests import helpers as H
+from tests.emu import hostprog as HP
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NEAR_CAP = 0.005               # share of (state, geom) pairs that may lie within FN.BAND of the boundary (the inputs alone: 0.09 %)
@@ -55,11 +55,7 @@ def test_inputs_keep_clear_of_the_boundary():
 # ---- csrc/floor_contact.h on the host ---------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def floor_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/floor_host.cpp")
-    out = str(tmp_path_factory.mktemp("floor_host") / "floor_host")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), os.path.join(ROOT, "tests", "floor_host.cpp"), "-o", out])
+    out = HP.build_host("floor_host.cpp", tmp_path_factory.mktemp("floor_host") / "floor_host")
     return out
 
 

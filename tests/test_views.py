@@ -2,8 +2,6 @@
 its object only for tensors), and csrc/view_stage.h built for the host under the address and undefined-behaviour sanitizers
 (tests/stage_host.cpp)."""
 import ctypes as C
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -11,8 +9,8 @@ import pytest
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd.batch import Batch, _view_args
+from tests.emu import hostprog as HP
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 N_BATCH = 6
 F64, I32 = np.float64, np.int32
 
@@ -104,12 +102,7 @@ def test_the_methods_keep_their_own_rules_before_the_helper():
 
 # ---- csrc/view_stage.h on the host, under the sanitizers --------------------------------------------------------------------------------
 def test_staging_layout_under_the_sanitizers(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler to build tests/stage_host.cpp")
-    exe = str(tmp_path / "stage_host")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "deepmimic_mujoco_amd", "csrc"), os.path.join(ROOT, "tests", "stage_host.cpp"), "-o", exe])
+    exe = HP.build_host("stage_host.cpp", tmp_path / "stage_host", sanitize=True, opt=("-O1", "-g"))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     # 5 sizes x 2 callers x (2^7 + 2^5 + 2^3) presence masks of render, state features and floor contacts
