@@ -108,9 +108,7 @@ def situations(case):
 
 def prepare(b, case):
     """Put a batch (device or testbench) into the case's start: zero warm start and time, the states, the two cursors."""
-    n = case["n"]
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(case["q"], case["v"], frame_idx=case["init"])
+    H.start(b, case["init"], case["q"], case["v"])
     if case["reward_mode"] in (2, 4):
         assert np.all(b.get(A.F_FRAME_IDX) == 0) and np.array_equal(b.get(A.F_FRAME_INIT), case["init"])
         b.set(A.F_FRAME_IDX, case["cursor"])

@@ -61,10 +61,7 @@ def actions(T, n=N, seed=3):
     return np.random.RandomState(seed).randn(T, n, 28) * ACTION_SCALE
 
 
-def prepare(b, frame, q, v):
-    n = q.shape[0]
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=frame)
+prepare = H.start                    # prepare(b, frame, q, v): zero warm start and time, the states at the clips' frames
 
 
 def oracle_rows(reward_mode, action_mode, nsub=1, T=T_ORACLE, n=N):

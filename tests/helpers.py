@@ -53,6 +53,62 @@ def varied_states(n, seed=0, clip="walk"):
     return idx, q, v, ws, ctrl
 
 
+# ---- a batch's state: the pieces every test of a batch shares (tests/gpu_batch.py has those that need torch) --------------------------------
+STATE = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE)
+TERM_FIELDS = (A.F_EPISODE_STEPS, A.F_DONE_REASON)
+
+
+def start(b, idx, q, v, ws=None, steps0=None):
+    """the batch into a known state: warm start `ws` (zeros), time 0, (q, v) at the mocap frames `idx`, the episodes' step counters at `steps0`"""
+    b.set(A.F_QACC_WARMSTART, np.zeros((b.n, 34)) if ws is None else ws); b.set(A.F_TIME, np.zeros(b.n))
+    b.set_state(q, v, frame_idx=idx)
+    if steps0 is not None:
+        b.set(A.F_EPISODE_STEPS, steps0)
+
+
+def state_of(b, fields=STATE):
+    return {f: b.get(f) for f in fields}
+
+
+def put_state(b, s, ep_steps=None):
+    """the batch into the state `s` (state_of of another batch)"""
+    b.set(A.F_QACC_WARMSTART, s[A.F_QACC_WARMSTART]); b.set(A.F_TIME, s[A.F_TIME])
+    b.set_state(s[A.F_QPOS], s[A.F_QVEL], frame_idx=s[A.F_FRAME_IDX])
+    for f in (A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE):
+        b.set(f, s[f])
+    if ep_steps is not None:
+        b.set(A.F_EPISODE_STEPS, ep_steps)
+
+
+def _first_difference(x, y):
+    """where two arrays of one size start to differ: the index, by bytes (a NaN's pattern and the sign of a zero count)"""
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    if x.size != y.size or x.dtype != y.dtype:
+        return "shape %s %s against %s %s" % (x.shape, x.dtype, y.shape, y.dtype)
+    bad = np.nonzero((x.reshape(x.size, 1).view(np.uint8) != y.reshape(y.size, 1).view(np.uint8)).any(1))[0]
+    return "%d of %d values differ, first at %s" % (len(bad), x.size, list(np.unravel_index(bad[0], y.shape or (1,))))
+
+
+def assert_bits(got, ref, what=""):
+    """two dicts of arrays, bit for bit (`.tobytes()`); a failure names the key and the first differing index: (step, env, ...) of a row array,
+    (env, ...) of a state field"""
+    assert got.keys() == ref.keys(), (what, sorted(map(str, got)), sorted(map(str, ref)))
+    for k in ref:
+        if np.asarray(got[k]).tobytes() != np.asarray(ref[k]).tobytes():
+            raise AssertionError("%s %s: %s" % (what, k, _first_difference(got[k], ref[k])))
+
+
+def assert_bits_or_close(got, ref, tol):
+    """integer, bool and uint8 arrays bit for bit; floating arrays finite and within `tol`, relative to max(1, |x|)"""
+    assert got.keys() == ref.keys()
+    for k in ref:
+        if ref[k].dtype.kind in "iub":
+            np.testing.assert_array_equal(got[k], ref[k], err_msg=str(k))
+        else:
+            err = np.abs(got[k] - ref[k]) / np.maximum(1.0, np.abs(ref[k]))
+            assert np.isfinite(got[k]).all() and err.max() <= tol, "%s: %d values differ, by at most %.3e (relative to max(1, |x|))" % (k, (err > 0).sum(), err.max())
+
+
 def oracle_model(max_efc=63, **opts):
     from oracle import oracle as O
     om = O.Model()
@@ -117,8 +173,7 @@ def compare_rollout(batch, om, idx, q, v, steps, seed=0, reward_mode=0, n_subste
     from oracle import oracle as O
     n = q.shape[0]
     mc = mocap(clip)
-    batch.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); batch.set(A.F_TIME, np.zeros(n))
-    batch.set_state(q, v, frame_idx=idx)
+    start(batch, idx, q, v)
     ods = [O.Data(om) for _ in range(n)]
     for e in range(n):
         ods[e].reset(); ods[e].set_state(q[e], v[e])

@@ -15,32 +15,22 @@ Bars.  float64 library: helpers.compare_rollout's (1e-9 relative; the warm start
 Action mode 2 has the largest figures in every form (its gains multiply the state's rounding), mode 1 the smallest (DM_F_CTRL 1e-15)."""
 import numpy as np
 import pytest
-import torch
 
 from deepmimic_mujoco_amd import _abi as A
-from deepmimic_mujoco_amd import Batch, DPVecEnv, MlpPolicy
+from deepmimic_mujoco_amd import Batch, DPVecEnv
 from tests import action_reward_cases as AR
 from tests import float32_cases as F32
 from tests import helpers as H
+from tests import gpu_batch as GB
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 TOL = 1e-9
 N = 13                                    # three full packed waves and one with three spare slots
 ACTIONS, REWARDS = (1, 2, 3, 4), (0, 1, 2, 3, 4)
 UNCOVERED = [(am, rm) for am in ACTIONS for rm in (2, 4)]      # the pairs of tests/test_action_reward.py
 
-# launch form -> (DM_OPT_PACKED, fused policy step, how the T steps are issued)
-FORMS = {
-    "narrow": (0, False, "step"),
-    "packed": (1, False, "step"),
-    "packed-ext": (2, False, "step"),
-    "rollout": (1, False, "rollout"),       # dm_batch_rollout: a horizon launch in action modes 1 and 2, step launches in 3 and 4
-    "queue": (1, False, "queue"),           # DM_OPT_STEP_QUEUE: likewise
-    "narrow-act": (0, True, "step"),
-    "packed-act": (1, True, "step"),
-    "rollout-act": (1, True, "rollout"),
-}
+# the launch forms of tests/gpu_batch.py run here ("rollout", "queue": a horizon launch in action modes 1 and 2, step launches in 3 and 4)
+FORMS = {k: GB.FORMS[k] for k in ("narrow", "packed", "packed-ext", "rollout", "queue", "narrow-act", "packed-act", "rollout-act")}
 _PACKED = {}
 
 
@@ -54,33 +44,24 @@ def _make(case, packed, dtype=64):
 
 def _run(form, case):
     """The case through one launch form -> (what the form produced, as action_reward_cases.check takes it; the action rows it consumed)."""
-    packed, policy, how = FORMS[form]
+    lf = FORMS[form]
     n, T, nsub = case["n"], case["T"], case["nsub"]
-    b = _make(case, packed)
-    if how == "step" and not policy:
+    b = _make(case, lf.packed)
+    if lf.issue == "step" and not lf.policy:
         got = AR.run_steps(b, case)
         b.close()
         return got, case["acts"]
     AR.prepare(b, case)
-    ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=DEV)
-    ac[:T] = torch.as_tensor(case["acts"], device=DEV); ac[T] = ac[T - 1]          # open loop: every row given; with a policy rows 1.. are overwritten
-    ob = torch.zeros((T, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((T, n), dtype=torch.float64, device=DEV)
-    dn = torch.zeros((T, n), dtype=torch.uint8, device=DEV); vp = torch.zeros((T, n), dtype=torch.float32, device=DEV)
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack() if policy else None
+    ac, ob, rew, dn, vp = GB.horizon_rows(T, n, act=case["acts"]); ac[T] = ac[T - 1]   # open loop: every row given; with a policy rows 1.. are overwritten
+    pol, W = GB.fused_policy() if lf.policy else (None, None)
     got = dict(ctrl=[None] * T, cursors=[None] * T)
-    if how == "rollout":
-        b.rollout(ac, (ob, rew, dn), nsub, W, vp if policy else None, True, pol._seed, 7)
-    elif how == "queue":
-        b.set_option(A.OPT_STEP_QUEUE, 2 * T)
-        for t in range(T):
-            b.step(ac[t], nsub, (ob[t], rew[t], dn[t]))
-        got["queued"] = b.queue_stats()
-    else:
-        for t in range(T):
-            b.step_act(ac[t], nsub, (ob[t], rew[t], dn[t]), W, ac[t + 1], vp[t], True, pol._seed, 7 + t)
+
+    def between(t):
+        if lf.issue == "queue":             # nothing read from the batch: every call stays queued
+            got["queued"] = b.queue_stats()
+        else:
             got["ctrl"][t] = b.get(A.F_CTRL); got["cursors"][t] = b.get(A.F_FRAME_IDX)
-    b.join(); b.sync()
+    GB.issue_steps(b, lf, ac, ob, rew, dn, nsub, pol=pol, W=W, vp=vp, between=between)
     got["queue_stats"] = b.queue_stats()
     got["ctrl"][T - 1] = b.get(A.F_CTRL); got["cursors"][T - 1] = b.get(A.F_FRAME_IDX)
     got.update(obs=ob.cpu().numpy(), reward=rew.cpu().numpy(), done=dn.cpu().numpy(), init=b.get(A.F_FRAME_INIT), qpos=b.get(A.F_QPOS),

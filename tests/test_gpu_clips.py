@@ -53,8 +53,7 @@ def test_every_clip_through_one_horizon_launch_matches_oracle(clip):
     idx = np.concatenate([[F - 3, F - 2], rng.randint(0, F, size=n - 2)]).astype(np.int32)
     q = mc.data_config[idx].copy(); v = mc.data_vel[idx].copy()
     q[n // 2:, 7:] += 0.05 * rng.randn(n - n // 2, 28)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=idx)
+    H.start(b, idx, q, v)
     acts = rng.randn(steps + 1, n, 28) * 0.3
     dev = "cuda:0"
     ac = torch.as_tensor(acts, dtype=torch.float64, device=dev).contiguous()

@@ -7,23 +7,17 @@ import pytest
 import torch
 
 from deepmimic_mujoco_amd import _abi as A
-from deepmimic_mujoco_amd import Batch, MlpPolicy
+from deepmimic_mujoco_amd import Batch
 from tests import float32_cases as F
 from tests import helpers as H
+from tests import gpu_batch as GB
+from tests.gpu_batch import horizon_rows
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 T = F.T
 
-# launch form -> (DM_OPT_PACKED, DM_OPT_PIPELINE, dm_batch_rollout, DM_OPT_STEP_QUEUE)
-FORMS = {
-    "narrow": (0, 1, False, 0),             # k_step_narrow: one env per wave, three waves per workgroup in this build
-    "narrow-pipe2": (0, 2, False, 0),       # ... as two pipelined sub-batches
-    "packed": (1, 1, False, 0),             # k_step_packed + k_step_redo: 33 .. 40 rows go to the redo kernel
-    "packed-ext": (2, 1, False, 0),         # k_step_packed_ext: the three-set code in the per-step launch
-    "horizon": (1, 1, True, 0),             # dm_batch_rollout, T steps in one launch, re-steps inside the wave
-    "queue": (1, 1, False, 3),              # three queued dm_batch_step calls run as one horizon launch
-}
+# this file's launch-form ids -> tests/gpu_batch.py FORMS ("horizon": dm_batch_rollout, T steps in one launch, re-steps inside the wave)
+FORMS = {"narrow": "narrow", "narrow-pipe2": "narrow-pipe2", "packed": "packed", "packed-ext": "packed-ext", "horizon": "rollout", "queue": "queue-3"}
 IN_WAVE = ("packed-ext", "horizon", "queue")            # forms whose packed code holds DM_PACKED_MAXROWS = 40 rows
 SETS = ("A", "n1", "n4", "n5", "n13")
 
@@ -35,14 +29,12 @@ def make(n, mode=0):
     return b
 
 
-def start(b, ids):
+def start_envs(b, ids):
     c = F.inputs()
-    n = len(ids)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(c["q"][ids], c["v"][ids], frame_idx=c["idx"][ids])
+    GB.start(b, c["idx"][ids], c["q"][ids], c["v"][ids])
 
 
-def state_of(b):
+def physics_of(b):
     return dict(qpos=b.get(A.F_QPOS), qvel=b.get(A.F_QVEL), qacc_warmstart=b.get(A.F_QACC_WARMSTART), nefc=b.get(A.F_NEFC), ncon=b.get(A.F_NCON),
                 geoms=b.get(A.F_CONTACT_GEOMS)[:, :F.MAXCON], frame=b.get(A.F_FRAME_IDX), cycle=b.get(A.F_CYCLE), time=b.get(A.F_TIME))
 
@@ -50,31 +42,24 @@ def state_of(b):
 def run_form(form, ids, mode, acts=None, per_step_state=True):
     """T lock-step steps of the envs `ids` of set A through one launch form -> rows (obs, reward, done as numpy), the state after every step where the
     form lets it be read between steps (else only the last: a list with None before it), the initial evaluation's counts, the redo counters."""
-    packed, pipe, rollout, queue = FORMS[form]
+    lf = GB.FORMS[FORMS[form]]
     n = len(ids)
     acts = F.inputs()["acts"][:, ids] if acts is None else acts
     steps = acts.shape[0]
     b = make(n, mode)
-    b.set_option(A.OPT_PACKED, packed); b.set_option(A.OPT_PIPELINE, pipe)
-    if queue:
-        b.set_option(A.OPT_STEP_QUEUE, queue)
-    start(b, ids)
+    b.set_option(A.OPT_PACKED, lf.packed); b.set_option(A.OPT_PIPELINE, lf.pipeline)
+    start_envs(b, ids)
     first = dict(nefc=b.get(A.F_NEFC), ncon=b.get(A.F_NCON), geoms=b.get(A.F_CONTACT_GEOMS)[:, :F.MAXCON])
-    ac = torch.zeros((steps + 1, n, 28), dtype=torch.float64, device=DEV); ac[:steps] = torch.as_tensor(acts, device=DEV)
-    ob = torch.zeros((steps, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((steps, n), dtype=torch.float64, device=DEV)
-    dn = torch.zeros((steps, n), dtype=torch.uint8, device=DEV)
+    ac, ob, rew, dn, _vp = horizon_rows(steps, n, act=acts)
     states = []
-    if rollout:
-        b.rollout(ac, (ob, rew, dn), 1)
-    else:
-        for t in range(steps):
-            b.step(ac[t], 1, (ob[t], rew[t], dn[t]))
-            if per_step_state and not queue:
-                b.join(); b.sync()
-                states.append(state_of(b))
-    b.join(); b.sync()
+    queue = lf.issue == "queue"
+
+    def read_state(_t):
+        b.join(); b.sync()
+        states.append(physics_of(b))
+    GB.issue_steps(b, lf, ac, ob, rew, dn, 1, between=read_state if per_step_state and not queue else None)
     if len(states) < steps:
-        states = [None] * (steps - 1) + [state_of(b)]
+        states = [None] * (steps - 1) + [physics_of(b)]
     qs = b.queue_stats() if queue else None
     redo = b.redo_reasons()
     b.close()
@@ -190,7 +175,7 @@ def test_every_launch_form_three_steps(form, mode):
         assert_envelope(out, name, ids, mode, what)
         redo = out["redo"]
         print("%s set %s: redo [total, candidates, box slots, contacts, rows, PGS test] %s" % (what, name, redo))
-        if FORMS[form][0] == 0:
+        if GB.FORMS[FORMS[form]].packed == 0:
             assert redo[0] == 0
             continue
         n32, n40, sure, slack = row_redo_counts(ids)
@@ -273,26 +258,22 @@ def test_horizon_with_policy_replays_open_loop_bit_for_bit(n):
     ids = F.case_sets()["n13"] if n == 13 else np.arange(64)
     TT = 8
     c = F.inputs()
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack()
+    pol, W = GB.fused_policy()
     for mode in (3, 0):
         res = []
         acts = None
         for with_policy in (True, False):
             b = make(n, mode); b.set_option(A.OPT_PACKED, 1)
-            start(b, ids)
-            ac = torch.zeros((TT + 1, n, 28), dtype=torch.float64, device=DEV)
-            ac[0] = torch.as_tensor(c["acts"][0, ids], device=DEV)
+            start_envs(b, ids)
+            ac, ob, rew, dn, vp = horizon_rows(TT, n, a0=c["acts"][0, ids])
             if not with_policy:
                 ac[:] = acts
-            ob = torch.zeros((TT, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((TT, n), dtype=torch.float64, device=DEV)
-            dn = torch.zeros((TT, n), dtype=torch.uint8, device=DEV); vp = torch.zeros((TT, n), dtype=torch.float32, device=DEV)
             b.rollout(ac, (ob, rew, dn), 1, W if with_policy else None, vp if with_policy else None, True, pol._seed, 7)
             b.join(); b.sync()
             if with_policy:
                 acts = ac.clone()
                 assert bool(torch.isfinite(acts).all()) and float(acts[1:].abs().max()) > 0, "the policy wrote no actions"
-            res.append((ob.cpu().numpy(), rew.cpu().numpy(), dn.cpu().numpy(), state_of(b)))
+            res.append((ob.cpu().numpy(), rew.cpu().numpy(), dn.cpu().numpy(), physics_of(b)))
             b.close()
         (o1, r1, d1, s1), (o2, r2, d2, s2) = res
         assert np.isfinite(o1).all()
@@ -317,15 +298,13 @@ def test_autoreset_inside_a_horizon_lands_on_the_rounded_mocap_frame():
     ids = np.arange(n)
     acts = F.f64r(np.random.RandomState(12).randn(TT, n, 28) * 0.5)
     b = make(n, 3); b.set_option(A.OPT_PACKED, 1); b.set_option(A.OPT_AUTORESET, 1); b.set_option(A.OPT_SEED, seed)
-    start(b, ids)
+    start_envs(b, ids)
     ep = b.get(A.F_EPISODE).copy()
-    ac = torch.zeros((TT + 1, n, 28), dtype=torch.float64, device=DEV); ac[:TT] = torch.as_tensor(acts, device=DEV)
-    ob = torch.zeros((TT, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((TT, n), dtype=torch.float64, device=DEV)
-    dn = torch.zeros((TT, n), dtype=torch.uint8, device=DEV)
+    ac, ob, rew, dn, _vp = horizon_rows(TT, n, act=acts)
     b.rollout(ac, (ob, rew, dn), 1)
     b.join(); b.sync()
     ob, rew, dn = ob.cpu().numpy(), rew.cpu().numpy(), dn.cpu().numpy()
-    final = state_of(b); ep_end = b.get(A.F_EPISODE)
+    final = physics_of(b); ep_end = b.get(A.F_EPISODE)
     b.close()
     assert np.isfinite(ob).all() and dn.any(axis=0).sum() >= 0.1 * n, "%d of %d envs reset" % (int(dn.any(axis=0).sum()), n)
     oms = {64: O.Model(dtype=64), 32: O.Model(dtype=32)}

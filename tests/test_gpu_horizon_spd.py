@@ -8,7 +8,6 @@ more with packed=True (DM_OPT_PACKED 1), where the step launches hand such an en
 4x a deviation the test measures itself between two paths that differ on exactly those env-steps (see there)."""
 import numpy as np
 import pytest
-import torch
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
@@ -17,15 +16,16 @@ from deepmimic_mujoco_amd.rollout import SegmentCollector
 from tests import helpers as H
 from tests import horizon_term_cases as HC
 from tests import spd_numpy as S
+from tests import gpu_batch as GB
+from tests.gpu_batch import DEV, assert_bits, horizon_rows, queued_steps, result, stacked, start
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 SEED = 5
 TOL = 1e-9                    # the bar of tests/test_gpu_spd.py against the restatement
 MODE_NAME = {3: "spd-target", 4: "spd-mocap"}
 DEEPMIMIC = TM.fall_body_mask("deepmimic")
-STATE = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE, A.F_CTRL)
-TERM_STATE = STATE + (A.F_EPISODE_STEPS, A.F_DONE_REASON)
+STATE = GB.STATE + (A.F_CTRL,)
+TERM_STATE = STATE + GB.TERM_FIELDS
 
 
 def make(n, mode, on, reward="imitation", autoreset=None, nsub=1, dtype=64, packed=2, step_queue=0, fall=None, limit=0, horizon_termination=False):
@@ -33,58 +33,6 @@ def make(n, mode, on, reward="imitation", autoreset=None, nsub=1, dtype=64, pack
                    action_mode=MODE_NAME[mode], horizon_spd=on, fall_contact_bodies=fall, max_episode_steps=limit, horizon_termination=horizon_termination)
     assert env.packed and env.horizon_spd == on and env.batch.options.get(A.OPT_HORIZON_SPD, 0) == (1 if on else 0)
     return env
-
-
-def start(b, idx, q, v):
-    b.set(A.F_QACC_WARMSTART, np.zeros((b.n, 34))); b.set(A.F_TIME, np.zeros(b.n))
-    b.set_state(q, v, frame_idx=idx)
-
-
-def buffers(T, n, act=None, a0=None):
-    ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=DEV)
-    if act is not None:
-        ac[:T] = torch.as_tensor(act, device=DEV)
-    if a0 is not None:
-        ac[0] = torch.as_tensor(a0, device=DEV)
-    return (ac, torch.zeros((T, n, 56), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.float64, device=DEV),
-            torch.zeros((T, n), dtype=torch.uint8, device=DEV), torch.zeros((T, n), dtype=torch.float32, device=DEV))
-
-
-def result(b, bufs, fields=STATE):
-    b.join(); b.sync()
-    out = {"rows%d" % k: x.cpu().numpy() for k, x in enumerate(bufs)}
-    out.update({f: b.get(f) for f in fields})
-    return out
-
-
-def assert_equal(got, ref):
-    assert got.keys() == ref.keys()
-    for k in ref:
-        if not np.array_equal(got[k], ref[k]):                                # where it starts: (step, env, ...) of a row array, (env, ...) of a state field
-            bad = np.argwhere(got[k] != ref[k])
-            print("%s differs in %d of %d values, first at %s" % (k, len(bad), ref[k].size, bad[0].tolist()))
-        np.testing.assert_array_equal(got[k], ref[k], err_msg=str(k))
-
-
-def queued_steps(b, act, t0, t1, nsub, keep, after=None):
-    """steps t0 .. t1 through dm_batch_step on buffers of their own (what DM_OPT_STEP_QUEUE can queue) -> queue_stats seen after every call"""
-    n, seen = b.n, []
-    for t in range(t0, t1):
-        a = torch.as_tensor(act[t], device=DEV)
-        out = (torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV))
-        b.step(a, nsub, out)
-        seen.append(b.queue_stats())
-        if after:
-            after(t)
-        keep.append((a,) + out)
-    b.join(); b.sync()
-    return seen
-
-
-def stacked(b, keep, fields=STATE):
-    out = {"rows%d" % k: np.stack([r[k].cpu().numpy() for r in keep]) for k in range(4)}      # actions, obs, reward, done
-    out.update({f: b.get(f) for f in fields})
-    return out
 
 
 # (the action seeds are those at which the inputs hold horizon_against_steps' input condition in every case of the grid: 3 does not in mode 4 with 2 substeps
@@ -133,9 +81,9 @@ def horizon_against_steps(mode, nsub, reward, dtype, action_seed=None):
         start(b, idx, q, v)
         redo0 = b.redo_total()
         if how == "rollout":
-            bufs = buffers(T, n, act=act)
+            bufs = horizon_rows(T, n, act=act)
             b.rollout(bufs[0], bufs[1:4], nsub)
-            res[how] = result(b, bufs[:4])
+            res[how] = result(b, bufs[:4], STATE)
             res[how]["rows0"] = res[how]["rows0"][:T]
         else:
             keep = []
@@ -143,7 +91,7 @@ def horizon_against_steps(mode, nsub, reward, dtype, action_seed=None):
                 rows[0] = b.get(A.F_NEFC).copy()
             queued_steps(b, act, 0, T, nsub, keep, (lambda t: rows.append(b.get(A.F_NEFC).copy())) if how == "off" else None)
             assert b.queue_stats() == ((1, T, 0) if how == "queue" else (0, 0, 0))
-            res[how] = stacked(b, keep)
+            res[how] = stacked(b, keep, STATE)
         redo[how] = b.redo_total() - redo0
         env.close()
     print("mode %d, %d substeps, %s, float%d: env-steps re-stepped by the one-env code: %s; constraint rows after every step launch (step x env):\n%s"
@@ -151,8 +99,8 @@ def horizon_against_steps(mode, nsub, reward, dtype, action_seed=None):
     assert min(redo.values()) > 0, "the many-row states must be re-stepped by the one-env code"
     assert redo["queue"] == redo["rollout"] == redo["off"], "input condition: an env-step the horizon's waves predicted lean landed at 33 .. 40 rows"
     assert np.isfinite(res["off"]["rows1"]).all()
-    assert_equal(res["queue"], res["off"])
-    assert_equal(res["rollout"], res["off"])
+    assert_bits(res["queue"], res["off"])
+    assert_bits(res["rollout"], res["off"])
 
 
 @pytest.mark.parametrize("reward", ["imitation", "alive"])
@@ -176,21 +124,20 @@ def weights_case(mode, stochastic=True):
     idx = np.random.RandomState(WEIGHTS_STATE_SEED).randint(0, mc.data_config.shape[0], size=n).astype(np.int32)
     q, v = mc.data_config[idx].copy(), mc.data_vel[idx].copy()
     a0 = mc.data_config[idx][:, 7:] if mode == 3 else np.zeros((n, 28))
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack()
+    pol, W = GB.fused_policy()
     res, redo = {}, {}
     for how in ("step_act", "on"):
         env = make(n, mode, how == "on", nsub=nsub)
         b = env.batch
         start(b, idx, q, v)
         redo0 = b.redo_total()
-        ac, ob, rew, dn, vp = buffers(T, n, a0=a0)
+        ac, ob, rew, dn, vp = horizon_rows(T, n, a0=a0)
         if how == "on":
             b.rollout(ac, (ob, rew, dn), nsub, W, vp, stochastic, pol._seed, 7)
         else:
             for t in range(T):
                 b.step_act(ac[t], nsub, (ob[t], rew[t], dn[t]), W, ac[t + 1], vp[t], stochastic, pol._seed, 7 + t)
-        res[how] = result(b, (ac, ob, rew, dn, vp))
+        res[how] = result(b, (ac, ob, rew, dn, vp), STATE)
         redo[how] = b.redo_total() - redo0
         env.close()
     return res, redo
@@ -206,7 +153,7 @@ def test_rollout_with_weights_equals_step_act_calls(mode):
     print("mode %d: env-steps re-stepped by the one-env code: %s" % (mode, redo))
     assert redo == {"step_act": 0, "on": 0}, "input condition: no re-stepped environment"
     assert np.isfinite(res["on"]["rows0"]).all() and np.abs(res["on"]["rows4"]).max() > 0
-    assert_equal(res["on"], res["step_act"])
+    assert_bits(res["on"], res["step_act"])
 
 
 @pytest.mark.parametrize("mode", [3, 4])
@@ -223,9 +170,9 @@ def test_rollout_matches_the_restatement(mode):
     env = make(n, mode, True, reward="v3-config", nsub=nsub, packed=True)
     b = env.batch
     start(b, idx, q, v)
-    bufs = buffers(T, n, act=act)
+    bufs = horizon_rows(T, n, act=act)
     b.rollout(bufs[0], bufs[1:4], nsub)
-    r = result(b, bufs[1:4])
+    r = result(b, bufs[1:4], STATE)
     env.close()
     ob, rew, dn = r["rows0"], r["rows1"], r["rows2"]
     fidx = idx.astype(np.int64).copy()
@@ -267,10 +214,10 @@ def test_step_queue_queues_again(mode):
             assert b.queue_stats() == (2, T, 0)
         else:
             assert seen == [(0, 0, 0)] * T
-        res.append(stacked(b, keep))
+        res.append(stacked(b, keep, STATE))
         env.close()
     assert res[0]["rows3"].sum() >= 1                                       # an auto-reset inside the horizon
-    assert_equal(res[1], res[0])
+    assert_bits(res[1], res[0])
 
 
 # ---- with early termination inside -------------------------------------------------------------------------------------------------------------------
@@ -284,11 +231,11 @@ def term_rollout(n, T, on, idx, q, v, act, W=None, pol=None, **cfg):
     b = env.batch
     start(b, idx, q, v)
     if W is None:
-        bufs = buffers(T, n, act=act)
+        bufs = horizon_rows(T, n, act=act)
         b.rollout(bufs[0], bufs[1:4], cfg["nsub"])
         r = result(b, bufs[:4], TERM_STATE)
     else:
-        bufs = buffers(T, n, a0=act[0])
+        bufs = horizon_rows(T, n, a0=act[0])
         b.rollout(bufs[0], bufs[1:4], cfg["nsub"], W, bufs[4], True, pol._seed, 7)
         r = result(b, bufs, TERM_STATE)
     stats = b.queue_stats()
@@ -301,24 +248,8 @@ def check_fall_decisions(n, act, idx, q, v, done_rows, **cfg):
     termination stepped from the reference's state, step by step — no fall decision lies within HC.BOUNDARY of the rule's boundary"""
     cm = H.compiled_model()
     mode = cfg.pop("mode")
-    T = act.shape[0]
-    ref = make(n, mode, False, **cfg)
-    probe = make(n, mode, False, **dict(cfg, fall=None, limit=0))
-    rb, pb = ref.batch, probe.batch
-    start(rb, idx, q, v)
-    pre_q, stepdone = np.zeros((T, n, 35)), np.zeros((T, n), dtype=bool)
-    for t in range(T):
-        s = {f: rb.get(f) for f in STATE[:8]}
-        pb.set(A.F_QACC_WARMSTART, s[A.F_QACC_WARMSTART]); pb.set(A.F_TIME, s[A.F_TIME])
-        pb.set_state(s[A.F_QPOS], s[A.F_QVEL], frame_idx=s[A.F_FRAME_IDX])
-        for f in (A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE):
-            pb.set(f, s[f])
-        a = torch.as_tensor(act[t], device=DEV)
-        _o, _r, d = pb.step(a, cfg["nsub"]); pb.join(); pb.sync()
-        stepdone[t] = d.cpu().numpy() != 0
-        pre_q[t] = pb.get(A.F_QPOS)
-        rb.step(a, cfg["nsub"]); rb.join(); rb.sync()
-    ref.close(); probe.close()
+    pre_q, stepdone = GB.states_before_termination(lambda: make(n, mode, False, **cfg), lambda: make(n, mode, False, **dict(cfg, fall=None, limit=0)),
+                                                   idx, q, v, act, cfg["nsub"])
     closest = HC.closest_decision(cm, pre_q, ~stepdone, TM.geoms_of_bodies(DEEPMIMIC, cm.geom_bodyid))
     ended = (done_rows != 0) & ~stepdone
     print("closest fall decision %.3e m from its boundary; %d ended by the step, %d by termination, %d env-steps went on" % (closest, stepdone.sum(), ended.sum(), (done_rows == 0).sum()))
@@ -334,14 +265,13 @@ def test_termination_inside_equals_step_terminate_act(mode, policy):
     n, T = 10, 7
     idx, q, v = HC.states(n)
     act = HC.actions(T, n)
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack() if policy else None
+    pol, W = GB.fused_policy() if policy else (None, None)
     cfg = term_cfg(mode, 2)
     ref, s0 = term_rollout(n, T, False, idx, q, v, act, W, pol, **dict(cfg))
     got, _s1 = term_rollout(n, T, True, idx, q, v, act, W, pol, **dict(cfg))
     assert s0 == (0, 0, 0)
     check_fall_decisions(n, ref["rows0"][:T], idx, q, v, ref["rows3"], **dict(cfg))
-    assert_equal(got, ref)
+    assert_bits(got, ref)
 
 
 @pytest.mark.parametrize("mode", [3, 4])
@@ -433,6 +363,6 @@ def test_option_off_after_on_restores_step_launches():
         seen = queued_steps(b, act, T, 2 * T, nsub, keep)
         assert s1 == ((1, T, 0) if toggled else (0, 0, 0))
         assert seen == [s1] * T                                            # with the option off (again) nothing is queued: step launches
-        res.append(stacked(b, keep))
+        res.append(stacked(b, keep, STATE))
         env.close()
-    assert_equal(res[1], res[0])
+    assert_bits(res[1], res[0])

@@ -17,7 +17,6 @@ rule's boundary is not defined between them.  Every comparison with a fall set f
 batch without termination stepped from the reference's state, step by step), that the inputs hold no such pair."""
 import numpy as np
 import pytest
-import torch
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import DPVecEnv, MlpPolicy
@@ -26,15 +25,15 @@ from deepmimic_mujoco_amd.rollout import SegmentCollector
 from tests import floor_numpy as FN
 from tests import helpers as H
 from tests import horizon_term_cases as HC
+from tests import gpu_batch as GB
+from tests.gpu_batch import DEV, assert_bits, assert_bits_or_close, horizon_rows, queued_steps, result, stacked, start, truncation_log
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 SEED = 5
 LIMIT = 3
 STEPS = 7
 DEEPMIMIC = TM.fall_body_mask("deepmimic")
-STATE = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE, A.F_EPISODE_STEPS, A.F_DONE_REASON)
-PLAIN_STATE = STATE[:8]
+STATE = GB.STATE + GB.TERM_FIELDS
 
 
 def make(n, on, fall="deepmimic", limit=LIMIT, autoreset="rsi", reward="alive", dtype=64, step_queue=0, log=0, packed=2):
@@ -42,28 +41,6 @@ def make(n, on, fall="deepmimic", limit=LIMIT, autoreset="rsi", reward="alive", 
                    fall_contact_bodies=fall, max_episode_steps=limit, truncation_log=log, horizon_termination=on)
     assert env.packed and env.batch.options.get(A.OPT_HORIZON_TERMINATION, 0) == (1 if on else 0)
     return env
-
-
-def start(b, idx, q, v):
-    b.set(A.F_QACC_WARMSTART, np.zeros((b.n, 34))); b.set(A.F_TIME, np.zeros(b.n))
-    b.set_state(q, v, frame_idx=idx)
-
-
-def buffers(T, n, a0=None, act=None):
-    ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=DEV)
-    if act is not None:
-        ac[:T] = torch.as_tensor(act, device=DEV)
-    if a0 is not None:
-        ac[0] = torch.as_tensor(a0, device=DEV)
-    return (ac, torch.zeros((T, n, 56), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.float64, device=DEV),
-            torch.zeros((T, n), dtype=torch.uint8, device=DEV), torch.zeros((T, n), dtype=torch.float32, device=DEV))
-
-
-def result(b, bufs):
-    b.join(); b.sync()
-    out = {"rows%d" % k: x.cpu().numpy() for k, x in enumerate(bufs)}
-    out.update({f: b.get(f) for f in STATE})
-    return out
 
 
 # packed=True (DM_OPT_PACKED 1, the lean per-step kernel): an env-step at 33 .. 40 rows is the one-env code's in the step launches and the packed three-set code's in
@@ -75,43 +52,14 @@ LEAN_TOL = 1e-12
 
 def assert_same(got, ref, packed=2):
     """packed == 2: bit for bit.  packed is True: integer arrays (done rows, reasons, counters, cursors, episodes) bit for bit, float arrays within LEAN_TOL"""
-    assert got.keys() == ref.keys()
-    for k in ref:
-        if packed == 2 or ref[k].dtype.kind in "iub":
-            np.testing.assert_array_equal(got[k], ref[k], err_msg=str(k))
-        else:
-            err = np.abs(got[k] - ref[k]) / np.maximum(1.0, np.abs(ref[k]))
-            assert np.isfinite(got[k]).all() and err.max() <= LEAN_TOL, "%s: %d values differ, by at most %.3e (relative to max(1, |x|))" % (k, (err > 0).sum(), err.max())
-
-
-def states_before_termination(n, act, idx, q, v, nsub=1, **cfg):
-    """the states the reference's steps leave, ahead of termination: a batch with termination behind step launches is stepped through `act`, and before
-    every step a probe without termination takes over its whole state and takes the same step -> (qpos [T, n, 35], the step's own done [T, n])"""
-    T = act.shape[0]
-    ref = make(n, False, **cfg)
-    probe = make(n, False, **dict(cfg, fall=None, limit=0))
-    rb, pb = ref.batch, probe.batch
-    start(rb, idx, q, v)
-    pre_q, stepdone = np.zeros((T, n, 35)), np.zeros((T, n), dtype=bool)
-    for t in range(T):
-        s = {f: rb.get(f) for f in PLAIN_STATE}
-        pb.set(A.F_QACC_WARMSTART, s[A.F_QACC_WARMSTART]); pb.set(A.F_TIME, s[A.F_TIME])
-        pb.set_state(s[A.F_QPOS], s[A.F_QVEL], frame_idx=s[A.F_FRAME_IDX])
-        for f in (A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE):
-            pb.set(f, s[f])
-        a = torch.as_tensor(act[t], device=DEV)
-        _o, _r, d = pb.step(a, nsub); pb.join(); pb.sync()
-        stepdone[t] = d.cpu().numpy() != 0
-        pre_q[t] = pb.get(A.F_QPOS)
-        rb.step(a, nsub); rb.join(); rb.sync()
-    ref.close(); probe.close()
-    return pre_q, stepdone
+    assert_bits(got, ref) if packed == 2 else assert_bits_or_close(got, ref, LEAN_TOL)
 
 
 def check_inputs(n, act, idx, q, v, done_rows, dtype=64, want_mix=True, **cfg):
     """the input condition, and the mix of endings in the horizon: a fall, a time-limit end, a step-own done, episodes that go on"""
     cm = H.compiled_model()
-    pre_q, stepdone = states_before_termination(n, act, idx, q, v, dtype=dtype, **cfg)
+    cfg = dict(cfg, dtype=dtype)
+    pre_q, stepdone = GB.states_before_termination(lambda: make(n, False, **cfg), lambda: make(n, False, **dict(cfg, fall=None, limit=0)), idx, q, v, act, 1)
     closest = HC.closest_decision(cm, pre_q, ~stepdone, TM.geoms_of_bodies(DEEPMIMIC, cm.geom_bodyid))      # (the geoms that decide: the fall set's)
     touch = (FN.floor_masks(cm, pre_q.reshape(-1, 35)).reshape(stepdone.shape) & TM.geoms_of_bodies(DEEPMIMIC, cm.geom_bodyid)) != 0
     fall = touch & ~stepdone
@@ -155,9 +103,9 @@ def test_rollout_equals_step_launches(n, autoreset, reward, dtype, packed):
         assert b.options[A.OPT_PACKED] == (2 if packed == 2 else 1)
         start(b, idx, q, v)
         redo0 = b.redo_total()
-        bufs = buffers(STEPS, n, act=act)
+        bufs = horizon_rows(STEPS, n, act=act)
         b.rollout(bufs[0], bufs[1:4], 1)
-        res.append(result(b, bufs[:4]))
+        res.append(result(b, bufs[:4], STATE))
         if on and n == 66:
             assert b.redo_total() - redo0 >= 1                            # the many-row environments were re-stepped inside their waves
         env.close()
@@ -172,15 +120,14 @@ def test_rollout_with_the_policy_is_step_then_terminate_then_act(dtype):
     launch's order (csrc/policy_wave_launch_order.h), so actions and values are equal bit for bit, not to float32 rounding."""
     n, Tn = 48, 4
     idx, q, v = HC.states(n)
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack()
+    pol, W = GB.fused_policy()
     a0 = HC.actions(1, n)[0]
     res = {}
     for how in ("reference", "off", "on"):
         env = make(n, how == "on", step_queue=8, dtype=dtype)
         b = env.batch
         start(b, idx, q, v)
-        ac, ob, rew, dn, vp = buffers(Tn, n, a0=a0)
+        ac, ob, rew, dn, vp = horizon_rows(Tn, n, a0=a0)
         if how == "reference":
             for t in range(Tn):
                 b.step(ac[t], 1, (ob[t], rew[t], dn[t])); b.join()
@@ -188,7 +135,7 @@ def test_rollout_with_the_policy_is_step_then_terminate_then_act(dtype):
                 pol.act(True, ob[t], out=ac[t + 1], vpred_out=vp[t])
         else:
             b.rollout(ac, (ob, rew, dn), 1, W, vp, True, pol._seed, 7)
-        res[how] = result(b, (ac, ob, rew, dn, vp))
+        res[how] = result(b, (ac, ob, rew, dn, vp), STATE)
         env.close()
     assert res["reference"]["rows3"].sum() >= 4 and res["reference"]["rows3"][0].sum() < n      # some episodes ended, by no means all
     check_inputs(n, res["reference"]["rows0"][:Tn], idx, q, v, res["reference"]["rows3"], want_mix=False, dtype=dtype)
@@ -200,16 +147,6 @@ def test_rollout_with_the_policy_is_step_then_terminate_then_act(dtype):
 
 
 # ---- the step queue ------------------------------------------------------------------------------------------------------------------------------------
-def queued_steps(b, act, t0, t1, keep):
-    n = b.n
-    for t in range(t0, t1):
-        a = torch.as_tensor(act[t], device=DEV)
-        out = (torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV))
-        b.step(a, 1, out)
-        keep.append((a,) + out)
-    b.join(); b.sync()
-
-
 @pytest.mark.parametrize("packed", [2, True])
 def test_step_queue_runs_one_horizon_launch_with_termination_inside(packed):
     n = 66
@@ -221,26 +158,16 @@ def test_step_queue_runs_one_horizon_launch_with_termination_inside(packed):
         b = env.batch
         start(b, idx, q, v)
         keep = []
-        queued_steps(b, act, 0, STEPS, keep)
+        queued_steps(b, act, 0, STEPS, keep=keep)
         stats = b.queue_stats()
         assert (stats[0] >= 1 and stats[1] == STEPS) if on else stats == (0, 0, 0)
-        out = {"rows%d" % k: np.stack([r[1 + k].cpu().numpy() for r in keep]) for k in range(3)}
-        out.update({f: b.get(f) for f in STATE})
-        res.append(out)
+        res.append(stacked(b, keep, STATE, actions=False))
         env.close()
     check_inputs(n, act, idx, q, v, res[0]["rows2"], reward="imitation", packed=packed)
     assert_same(res[1], res[0], packed)
 
 
 # ---- the truncation log ------------------------------------------------------------------------------------------------------------------------------
-def sorted_log(b, clear):
-    count, index, rq, rv = b.truncations(clear=clear)
-    count = int(count)
-    index, rq, rv = ((x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x))[:count] for x in (index, rq, rv))
-    order = np.lexsort((index[:, 0], index[:, 1]))                        # by (tick, env)
-    return count, index[order], rq[order], rv[order]
-
-
 @pytest.mark.parametrize("packed", [2, True])
 def test_truncation_log_and_ticks(packed):
     n = 66
@@ -251,13 +178,13 @@ def test_truncation_log_and_ticks(packed):
         env = make(n, on, fall=None, log=n * 6, packed=packed)                            # (n * 3 records per horizon: two horizons without clearing)
         b = env.batch
         start(b, idx, q, v)
-        first = buffers(STEPS, n, act=act[:STEPS])
+        first = horizon_rows(STEPS, n, act=act[:STEPS])
         b.rollout(first[0], first[1:4], 1)
-        one = sorted_log(b, clear=False)
-        second = buffers(STEPS, n, act=act[STEPS:])
+        one = truncation_log(b, clear=False)
+        second = horizon_rows(STEPS, n, act=act[STEPS:])
         b.rollout(second[0], second[1:4], 1)                               # the log was not cleared: the ticks go on at STEPS
-        two = sorted_log(b, clear=True)
-        logs.append((one, two, result(b, second[:4])))
+        two = truncation_log(b, clear=True)
+        logs.append((one, two, result(b, second[:4], STATE)))
         env.close()
     (one0, two0, res0), (one1, two1, res1) = logs
     assert one0[0] >= n // 2 and {2, 5} <= set(one0[1][:, 1].tolist()) and one0[1][:, 1].max() < STEPS
@@ -297,17 +224,15 @@ def test_option_off_after_on_restores_step_launches():
         b = env.batch
         start(b, idx, q, v)
         keep = []
-        queued_steps(b, act, 0, STEPS, keep)
+        queued_steps(b, act, 0, STEPS, keep=keep)
         s1 = b.queue_stats()
         if toggled:
             b.set_option(A.OPT_HORIZON_TERMINATION, 0)
-        queued_steps(b, act, STEPS, 2 * STEPS, keep)
+        queued_steps(b, act, STEPS, 2 * STEPS, keep=keep)
         s2 = b.queue_stats()
         assert (s1[0] >= 1 and s1[1] == STEPS) if toggled else s1 == (0, 0, 0)
         assert s2 == s1                                                    # with the option off (again) nothing is queued: step launches
-        out = {"rows%d" % k: np.stack([r[1 + k].cpu().numpy() for r in keep]) for k in range(3)}
-        out.update({f: b.get(f) for f in STATE})
-        res.append(out)
+        res.append(stacked(b, keep, STATE, actions=False))
         env.close()
     check_inputs(n, act, idx, q, v, res[0]["rows2"], want_mix=False)
     assert_same(res[1], res[0])

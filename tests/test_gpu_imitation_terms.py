@@ -80,7 +80,7 @@ def test_a_frame_outside_the_table():
 
 
 # ---- the batch's own states -----------------------------------------------------------------------------------------------------------
-def start(b, n, seed):
+def start_near_frames(b, n, seed):
     """mocap frames with a little noise; some environments start two frames before the clip wraps (cycle 0 -> 1)"""
     mc = H.mocap()
     F = len(mc.data_config)
@@ -89,8 +89,7 @@ def start(b, n, seed):
     idx[::3] = F - 3
     q = mc.data_config[idx].copy(); v = mc.data_vel[idx].copy()
     q[:, 7:] += 0.02 * rng.randn(n, 28)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=idx)
+    H.start(b, idx, q, v)
     return rng
 
 
@@ -111,7 +110,7 @@ def substeps():
 @pytest.mark.parametrize("n,packed", [(6, False), (66, True)])
 def test_batch_rows_are_the_steps_reward_taken_apart(n, packed, variant):
     b = imitation_batch(n, packed, pipeline=2 if variant == "pipelined" else 0)
-    rng = start(b, n, seed=n)
+    rng = start_near_frames(b, n, seed=n)
     ids = None
     if variant == "env_ids":
         ids = np.random.RandomState(7).permutation(n)[:max(3, n // 2)].astype(np.int32)
@@ -167,9 +166,9 @@ def test_batch_form_argument_rules():
 
 def test_the_call_changes_no_batch_state():
     n = 66
-    fields = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE, A.F_CTRL, A.F_NEFC)
+    fields = H.STATE + (A.F_CTRL, A.F_NEFC)
     a, twin = imitation_batch(n, True), imitation_batch(n, True)
-    ra, rb = start(a, n, seed=4), start(twin, n, seed=4)
+    ra, rb = start_near_frames(a, n, seed=4), start_near_frames(twin, n, seed=4)
     ids = np.arange(0, n, 5, dtype=np.int32)
     for t in range(8):
         act = ra.randn(n, 28) * 0.9
@@ -194,7 +193,7 @@ def test_float32_library_stays_inside_the_oracle_derived_bars():
     ratio = (np.abs(got - c["ref"][i]) / bar).max(0) * TI.FLOAT_MARGIN
     print("float32 library, explicit n=5: worst error per column as a multiple of the oracles' own difference (bar %g):\n%s" % (TI.FLOAT_MARGIN, np.array2string(ratio, precision=3)))
     assert (ratio <= TI.FLOAT_MARGIN).all(), ratio
-    rng = start(b, 6, seed=2)
+    rng = start_near_frames(b, 6, seed=2)
     worst = 0.0
     for t in range(8):
         _o, rew, _d = b.step(rng.randn(6, 28) * 0.9, substeps())

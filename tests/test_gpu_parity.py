@@ -91,7 +91,7 @@ def test_wide_tier_takes_over_when_rows_exceed_32():
     b2 = make_batch(n); b2.set_option(102, 0)              # wide kernel only
     b3 = make_batch(n)
     for bb in (b2, b3):
-        bb.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); bb.set(A.F_TIME, np.zeros(n)); bb.set_state(q, v)
+        H.start(bb, None, q, v)
     rng = np.random.RandomState(0)
     most = 0
     for t in range(3):
@@ -284,7 +284,7 @@ def test_overflow_strip_rows_match_oracle_and_the_all_register_tier():
     for tier in (1, 0):
         bb = make_batch(n)
         bb.set_option(102, tier)
-        bb.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); bb.set_state(q, v, frame_idx=idx)
+        H.start(bb, idx, q, v)
         rng = np.random.RandomState(0)
         o = [bb.step(rng.randn(n, 28) * 0.3)[0].copy() for _ in range(3)]
         assert bb.get(A.F_NEFC).max() > 40
@@ -302,7 +302,7 @@ def test_pgs_guarded_replay_path_gives_identical_results():
     for force in (0, 1):
         b = make_batch(n)
         b.set_option(103, force)
-        b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set_state(q, v, frame_idx=idx)
+        H.start(b, idx, q, v)
         rng = np.random.RandomState(1)
         o = [b.step(rng.randn(n, 28) * 0.5)[0].copy() for _ in range(4)]
         outs.append((np.stack(o), b.get(A.F_SOLVER_ITER).copy(), b.get(A.F_QACC_WARMSTART).copy()))
@@ -428,7 +428,7 @@ def test_float32_batch_tracks_the_float64_path():
     for dt in (64, 32, 32):
         b = Batch(H.compiled_model(), mc.data_config, mc.data_vel, n, device=0, mocap_dt=float(mc.dt), dtype=dt)
         assert b.dtype == dt
-        b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set_state(q, v, frame_idx=idx)
+        H.start(b, idx, q, v)
         if dt == 32:                                          # boundary conversion: float64 in, float32 state, float64 out
             assert np.array_equal(b.get(A.F_QPOS), q.astype(np.float32).astype(np.float64))
         nefc0 = b.get(A.F_NEFC).copy()
@@ -529,7 +529,7 @@ def test_packed_kernel_matches_oracle_full_contact(clip):
         b.close()
     # diagnostics of a packed step: PGS sweep counts, row / contact counts, contact geom lists
     b = make_batch(n, clip=clip); b.set_option(A.OPT_PACKED, 1)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set_state(q, v, frame_idx=idx)
+    H.start(b, idx, q, v)
     ods = [O.Data(om) for _ in range(n)]
     for e in range(n):
         ods[e].reset(); ods[e].set_state(q[e], v[e])

@@ -17,11 +17,10 @@ from deepmimic_mujoco_amd.termination import fall_body_mask
 from tests import helpers as H
 from tests import push_cases as PC
 from tests.float32_cases import MARGIN
+from tests.gpu_batch import DEV, STATE, assert_bits, horizon_rows, queued_step, stacked, state_of
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 STEPS = 24
-STATE = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_EPISODE, A.F_CYCLE)
 
 
 def make(n, dtype=64, packed=0, pipeline=1, autoreset=0, max_steps=0, seed=PC.SEED, schedule=None, reward_mode=0, queue=0):
@@ -39,26 +38,17 @@ def make(n, dtype=64, packed=0, pipeline=1, autoreset=0, max_steps=0, seed=PC.SE
     return b
 
 
-def start(b, n, rounded=False):
+def load_states(b, n, rounded=False):
     idx, q, v, ws = PC.states(n, rounded=rounded)
     PC.load(b, idx, q, v, ws)
     return idx, q, v, ws
-
-
-def snapshot(b, fields=STATE):
-    return {f: b.get(f) for f in fields}
-
-
-def assert_bitwise(a, b, what=""):
-    for k in a:
-        assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), (what, k)
 
 
 # ---- dm_batch_push against the restatement -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [13, 1])
 def test_push_matches_the_restatement(n):
     b = make(n)
-    start(b, n)
+    load_states(b, n)
     v0 = b.get(A.F_QVEL).copy(); keep = PC.untouched_fields(b)
     b.push(np.arange(n, dtype=np.int32) % 13 + 1, PC.impulses(n))
     dv = b.get(A.F_QVEL) - v0
@@ -73,7 +63,7 @@ def test_push_matches_the_restatement(n):
 def test_push_float32_library_within_the_float32_envelope():
     n = 13
     b = make(n, dtype=32)
-    start(b, n, rounded=True)
+    load_states(b, n, rounded=True)
     v0 = b.get(A.F_QVEL).copy(); keep = PC.untouched_fields(b)
     b.push(np.arange(n, dtype=np.int32) % 13 + 1, PC.impulses(n, rounded=True))
     dv = b.get(A.F_QVEL) - v0
@@ -89,7 +79,7 @@ def test_push_float32_library_within_the_float32_envelope():
 def test_push_untouched_envs_and_argument_errors():
     n = 4
     b = make(n)
-    start(b, n)
+    load_states(b, n)
     v0 = b.get(A.F_QVEL).copy(); keep = PC.untouched_fields(b)
     P = PC.impulses(n)
     b.push([3, 0, 5, 2], np.vstack([np.zeros(3), P[1], P[2], P[3]]), mask=[1, 1, 0, 0])          # zero impulse | body 0 | masked out twice
@@ -114,7 +104,7 @@ def test_push_changes_the_linear_momentum_by_the_impulse():
     n = 13
     cm = H.compiled_model()
     b = make(n)
-    _idx, q, _v, _ws = start(b, n)
+    _idx, q, _v, _ws = load_states(b, n)
     P = PC.impulses(n)
     f0 = b.state_features()
     b.push(np.arange(n, dtype=np.int32) % 13 + 1, P)
@@ -140,12 +130,7 @@ class DeviceSteps(object):
         self.keep = []
 
     def step(self, action):
-        n = self.b.n
-        a = torch.as_tensor(np.ascontiguousarray(action), device=DEV)
-        out = (torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV))
-        self.b.step(a, 1, out)
-        self.keep.append((a,) + out)
-        return out
+        return queued_step(self.b, action, 1, self.keep)
 
     def __getattr__(self, name):
         return getattr(self.b, name)
@@ -183,7 +168,7 @@ def test_scheduled_batch_equals_its_scripted_twin_bit_for_bit(packed, dtype):
         pushes += int((body > 0).sum())
         for x, y in zip(oa, ob):
             assert x.tobytes() == y.tobytes(), t
-        assert_bitwise(snapshot(a), snapshot(b), t)
+        assert_bits(state_of(a), state_of(b), t)
     assert pushes >= 3 * n
     a.close(); b.close()
 
@@ -195,7 +180,7 @@ def reference_loop(n, acts, **cfg):
     b.reset(0, 1)
     outs = [tuple(x.copy() for x in b.step(acts[t])) for t in range(len(acts))]
     res = {"rows%d" % k: np.stack([o[k] for o in outs]) for k in range(3)}
-    res.update(snapshot(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
+    res.update(state_of(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
     b.close()
     return res
 
@@ -212,13 +197,12 @@ def test_rollout_and_step_queue_with_a_schedule_are_step_launches(horizon_term):
     b.set_option(106, 1)                                       # one launch per horizon wherever the batch allows it: a schedule does not
     b.set_option(A.OPT_HORIZON_TERMINATION, horizon_term)
     b.reset(0, 1)
-    ac = torch.as_tensor(acts, device=DEV)
-    out = (torch.zeros((T, n, 56), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.uint8, device=DEV))
+    ac, *out = horizon_rows(T, n, act=acts)[:4]
     b.rollout(ac, out, 1)
     b.sync()
     got = {"rows%d" % k: out[k].cpu().numpy() for k in range(3)}
-    got.update(snapshot(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
-    assert_bitwise(ref, got, "rollout")
+    got.update(state_of(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
+    assert_bits(ref, got, "rollout")
     assert b.queue_stats() == (0, 0, 0)
     b.close()
     # DM_OPT_STEP_QUEUE
@@ -230,9 +214,8 @@ def test_rollout_and_step_queue_with_a_schedule_are_step_launches(horizon_term):
         drv.step(acts[t])
         assert b.queue_stats() == (0, 0, 0)
     b.join(); b.sync()
-    got = {"rows%d" % k: np.stack([r[1 + k].cpu().numpy() for r in drv.keep]) for k in range(3)}
-    got.update(snapshot(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
-    assert_bitwise(ref, got, "step queue")
+    got = stacked(b, drv.keep, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE), actions=False)
+    assert_bits(ref, got, "step queue")
     b.close()
 
 
@@ -244,21 +227,18 @@ def test_step_act_with_a_schedule_equals_the_step_loop(packed):
     W = pol.pack()
     b = make(n, schedule=PC.busy_schedule(), **cfg)
     b.reset(0, 1)
-    ac = torch.zeros((T + 1, n, A.NU), dtype=torch.float64, device=DEV)
-    ac[0] = torch.as_tensor(np.random.RandomState(4).randn(n, A.NU) * 0.3, device=DEV)
-    out = (torch.zeros((T, n, 56), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.float64, device=DEV), torch.zeros((T, n), dtype=torch.uint8, device=DEV))
-    vp = torch.zeros((T, n), dtype=torch.float32, device=DEV)
+    ac, *out, vp = horizon_rows(T, n, a0=np.random.RandomState(4).randn(n, A.NU) * 0.3)
     for t in range(T):
         b.step_act(ac[t], 1, (out[0][t], out[1][t], out[2][t]), W, ac[t + 1], vp[t], True, 11, t)
     b.sync()
     got = {"rows%d" % k: out[k].cpu().numpy() for k in range(3)}
-    got.update(snapshot(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
+    got.update(state_of(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
     acts = ac.cpu().numpy()
     b.close()
     assert np.abs(acts[1:]).max() > 0                           # the policy wrote the later actions
     ref = reference_loop(n, acts[:T], **cfg)
     assert ref[A.F_PUSH_STATE][:, 4].min() >= 1
-    assert_bitwise(ref, got, "step_act")
+    assert_bits(ref, got, "step_act")
 
 
 # ---- off after on ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -273,8 +253,8 @@ def test_a_schedule_turned_on_and_off_again_leaves_no_trace():
         b.reset(0, 1)
         outs = [tuple(x.copy() for x in b.step(a)) for a in acts]
         r = {"rows%d" % k: np.stack([o[k] for o in outs]) for k in range(3)}
-        r.update(snapshot(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
+        r.update(state_of(b, STATE + (A.F_PUSH_STATE, A.F_PUSH_FORCE)))
         res.append(r)
         b.close()
-    assert_bitwise(res[0], res[1])
+    assert_bits(res[0], res[1])
     assert (res[1][A.F_PUSH_STATE] == np.array([-1, 0, 0, 0, 0])).all() and not res[1][A.F_PUSH_FORCE].any()

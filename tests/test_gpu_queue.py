@@ -6,9 +6,9 @@ import torch
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import DPVecEnv
+from tests.gpu_batch import DEV, step_rows
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 
 
 def _state(b):
@@ -78,8 +78,7 @@ def test_queue_against_the_oracle_and_other_entry_points_flush_it():
     idx = ((np.arange(n) * 5) % mc.data_config.shape[0]).astype(np.int32)
     q = mc.data_config[idx].copy(); v = mc.data_vel[idx].copy()
     b.set_option(A.OPT_AUTORESET, 0)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=idx)
+    H.start(b, idx, q, v)
     ods = [O.Data(om) for _ in range(n)]
     for e in range(n):
         ods[e].reset(); ods[e].set_state(q[e], v[e])
@@ -144,7 +143,7 @@ def test_buffer_reuse_degenerates_to_step_by_step_and_closed_loops_stay_correct(
         b = env.batch
         env.reset("rsi")
         act = torch.zeros((n, 28), dtype=torch.float64, device=DEV)
-        out = (torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV))
+        out = step_rows(n)
         trace = []
         for t in range(T):
             act.copy_(acs[t])
@@ -221,7 +220,7 @@ def test_dpvecenv_step_queue_argument():
     env.reset("rsi")
     g = torch.Generator(device=DEV); g.manual_seed(4)
     acs = torch.randn((5, n, 28), generator=g, dtype=torch.float64, device=DEV) * 0.5
-    outs = [(torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV)) for _ in range(4)]
+    outs = [step_rows(n) for _ in range(4)]
     for t in range(4):
         env.batch.step(acs[t], 1, outs[t])
     assert env.batch.queue_stats() == (0, 0, 4)

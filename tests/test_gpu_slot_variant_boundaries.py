@@ -7,15 +7,16 @@ not the packed one's): such an environment is compared up to that step, and once
 explain, nothing later is compared."""
 import numpy as np
 import pytest
-import torch
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import DPVecEnv
 from tests import helpers as H
+from tests import gpu_batch as GB
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 T = 4
+# this file's launch-form ids -> tests/gpu_batch.py FORMS; each runs with DM_OPT_PACKED 1 and 2, the queue as deep as the run
+FORMS = {"per_step": GB.FORMS["packed"], "queue": GB.FORMS["queue"]._replace(queue_depth=T), "horizon": GB.FORMS["rollout"]}
 CASES = {"14_15": (0, 8), "16_17": (8, 16), "30_31": (16, 24), "32_partly_filled": (24, 30)}      # two waves of the fixture each
 LEADS = {"14_15": (14, 15), "16_17": (16, 17), "30_31": (30, 31), "32_partly_filled": (32, 31)}
 _ORACLE = {}
@@ -52,25 +53,17 @@ def _run(case, form, mode):
     env = DPVecEnv(n, motion="walk", device=0, reward="alive", autoreset=None, packed=True, frame_skip=1)
     b = env.batch
     b.set_option(A.OPT_PACKED, mode)
-    if form == "queue":
-        b.set_option(A.OPT_STEP_QUEUE, T)
-    b.set(A.F_QACC_WARMSTART, ws); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=f)
+    GB.start(b, f, q, v, ws=ws)
     assert np.array_equal(b.get(A.F_NEFC), ne0), "the states' row counts moved: the fixture no longer sits on the boundaries"
-    ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=DEV); ac[:T] = torch.as_tensor(acts, device=DEV)
-    ob = torch.zeros((T, n, 56), dtype=torch.float64, device=DEV)
-    rew = torch.zeros((T, n), dtype=torch.float64, device=DEV); dn = torch.zeros((T, n), dtype=torch.uint8, device=DEV)
+    ac, ob, rew, dn, _vp = GB.horizon_rows(T, n, act=acts)
     rows = redo_steps = None
     redo0 = b.redo_total()
-    if form == "horizon":
-        b.rollout(ac, (ob, rew, dn), 1)
-    else:
+    if form != "horizon":
         rows = np.zeros((T, n), dtype=np.int64); redo_steps = np.zeros(T, dtype=np.int64)
-        for t in range(T):
-            b.step(ac[t], 1, (ob[t], rew[t], dn[t]))
-            if form == "per_step":
-                rows[t] = b.get(A.F_NEFC); redo_steps[t] = b.redo_total() - redo0
-    b.join(); b.sync()
+
+    def read_rows(t):
+        rows[t] = b.get(A.F_NEFC); redo_steps[t] = b.redo_total() - redo0
+    GB.issue_steps(b, FORMS[form]._replace(packed=mode), ac, ob, rew, dn, 1, between=read_rows if form == "per_step" else None)
     out = dict(obs=ob.cpu().numpy(), rew=rew.cpu().numpy(), done=dn.cpu().numpy(), qpos=b.get(A.F_QPOS), qvel=b.get(A.F_QVEL),
                qacc=b.get(A.F_QACC_WARMSTART), solver_iter=b.get(A.F_SOLVER_ITER), nefc=b.get(A.F_NEFC), rows=rows, redo_steps=redo_steps, redo=b.redo_total() - redo0)
     env.close()

@@ -6,25 +6,17 @@ import pytest
 import torch
 
 from deepmimic_mujoco_amd import _abi as A
-from deepmimic_mujoco_amd import Batch, DPVecEnv, MlpPolicy
+from deepmimic_mujoco_amd import Batch, DPVecEnv
 from tests import helpers as H
 from tests import spd_numpy as S
+from tests import gpu_batch as GB
+from tests.gpu_batch import DEV, horizon_rows, start, step_rows
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 TOL = 1e-9
 
-# launch form -> (DM_OPT_PACKED, fused policy step, dm_batch_rollout)
-FORMS = {
-    "narrow": (0, False, False),            # k_step_narrow_spd
-    "packed": (1, False, False),            # k_step_packed_spd (+ k_step_redo_spd)
-    "packed-ext": (2, False, False),        # k_step_packed_ext_spd
-    "narrow-act": (0, True, False),         # k_step_act_spd (dm_batch_step_act)
-    "packed-act": (1, True, False),         # k_step_packed_act_spd
-    "rollout": (1, False, True),            # dm_batch_rollout without weights: step launches
-    "rollout-act": (1, True, True),         # dm_batch_rollout with weights
-    "rollout-narrow-act": (0, True, True),
-}
+# the launch forms of tests/gpu_batch.py that step in these modes (the *_spd kernels; dm_batch_rollout issues step launches)
+FORMS = {k: GB.FORMS[k] for k in ("narrow", "packed", "packed-ext", "narrow-act", "packed-act", "rollout", "rollout-act", "rollout-narrow-act")}
 
 
 def _make(n, mode, packed, reward_mode=1, dtype=64):
@@ -37,29 +29,14 @@ def _make(n, mode, packed, reward_mode=1, dtype=64):
 def _run(form, mode, nsub, idx, q, v, T, first_action, want_ctrl=True):
     """T steps of the batch through one launch form.  Returns the rows (actions [T, n, 28] as consumed, obs, rew, done), the per-step
     DM_F_CTRL where the form allows reading it between steps (else only the last), and the final state."""
-    packed, policy, rollout = FORMS[form]
+    lf = FORMS[form]
     n = len(q)
-    b = _make(n, mode, packed)
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=idx)
-    ac = torch.zeros((T + 1, n, 28), dtype=torch.float64, device=DEV)
-    ac[:] = torch.as_tensor(first_action, device=DEV)          # open loop: every row given; with a policy rows 1.. are overwritten
-    ob = torch.zeros((T, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((T, n), dtype=torch.float64, device=DEV)
-    dn = torch.zeros((T, n), dtype=torch.uint8, device=DEV); vp = torch.zeros((T, n), dtype=torch.float32, device=DEV)
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack() if policy else None
+    b = _make(n, mode, lf.packed)
+    start(b, idx, q, v)
+    ac, ob, rew, dn, vp = horizon_rows(T, n, act=first_action)   # open loop: every row given; with a policy rows 1.. are overwritten
+    pol, W = GB.fused_policy() if lf.policy else (None, None)
     ctrls = []
-    if rollout:
-        b.rollout(ac, (ob, rew, dn), nsub, W, vp if policy else None, True, pol._seed, 7)
-    else:
-        for t in range(T):
-            if policy:
-                b.step_act(ac[t], nsub, (ob[t], rew[t], dn[t]), W, ac[t + 1], vp[t], True, pol._seed, 7 + t)
-            else:
-                b.step(ac[t], nsub, (ob[t], rew[t], dn[t]))
-            if want_ctrl:
-                ctrls.append(b.get(A.F_CTRL))
-    b.join(); b.sync()
+    GB.issue_steps(b, lf, ac, ob, rew, dn, nsub, pol=pol, W=W, vp=vp, between=(lambda t: ctrls.append(b.get(A.F_CTRL))) if want_ctrl else None)
     if not ctrls:
         ctrls = [None] * (T - 1) + [b.get(A.F_CTRL)]
     final = (b.get(A.F_QPOS), b.get(A.F_QVEL), b.get(A.F_QACC_WARMSTART), b.get(A.F_TIME), b.get(A.F_FRAME_IDX), b.get(A.F_CTRL))
@@ -130,7 +107,7 @@ def test_rollout_falls_back_to_step_launches_bit_for_bit(pair, mode):
     for i in range(6):
         assert np.array_equal(x[2][i], y[2][i]), "final state differs (%d)" % i
     assert np.isfinite(x[0][1]).all()
-    if FORMS[pair[0]][0]:
+    if FORMS[pair[0]].packed:
         assert x[3][1] == y[3][1] > 0, "the many-row states must go through the redo kernel (%d / %d)" % (x[3][1], y[3][1])
 
 
@@ -145,8 +122,7 @@ def test_step_queue_launches_every_call_at_once(mode):
         b = env.batch
         g = torch.Generator(device=DEV); g.manual_seed(11)
         ac = torch.randn((T, n, 28), generator=g, dtype=torch.float64, device=DEV) * 0.3
-        ob = torch.zeros((T, n, 56), dtype=torch.float64, device=DEV); rew = torch.zeros((T, n), dtype=torch.float64, device=DEV)
-        dn = torch.zeros((T, n), dtype=torch.uint8, device=DEV)
+        _ac, ob, rew, dn, _vp = horizon_rows(T, n)
         env.reset("rsi")
         for t in range(T):
             b.step(ac[t], 1, (ob[t], rew[t], dn[t]))
@@ -193,7 +169,7 @@ def test_float32_library_tracks_the_float64_path_in_mode_3():
             outs = {}
             for dt in (64, 32, 32):
                 b = _make(n, mode, 0, reward_mode=reward_mode, dtype=dt)
-                b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set_state(q, v, frame_idx=idx)
+                start(b, idx, q, v)
                 if reward_mode == 2:
                     b.set(A.F_FRAME_IDX, cursor)
                 nefc0 = b.get(A.F_NEFC).copy()
@@ -222,7 +198,7 @@ def test_dpvecenv_spd_mocap_full_size_open_loop():
     assert env.frame_skip >= 2
     b = env.batch
     zero = torch.zeros((n, 28), dtype=torch.float64, device=DEV)
-    out = (torch.zeros((n, 56), dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.uint8, device=DEV))
+    out = step_rows(n)
     env.reset("rsi")
     ndone, rsum = 0, 0.0
     for t in range(64):

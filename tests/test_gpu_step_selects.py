@@ -7,17 +7,15 @@ with auto-reset 1, a fixed seed, 8 steps with device tensors (what DM_OPT_PIPELI
 fields of tests/test_gpu_push.py, DM_F_PUSH_STATE, DM_F_EPISODE_STEPS and DM_F_DONE_REASON.  Bar: bit for bit."""
 import numpy as np
 import pytest
-import torch
 
 from deepmimic_mujoco_amd import _abi as A
 from deepmimic_mujoco_amd import Batch
 from tests import clips_cases as CC
 from tests import helpers as H
 from tests import push_cases as PC
-from tests.test_gpu_push import STATE, assert_bitwise, snapshot
+from tests.gpu_batch import STATE, assert_bits, horizon_rows, result, state_of
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 STEPS, LIMIT = 8, 5
 FIELDS = STATE + (A.F_PUSH_STATE, A.F_EPISODE_STEPS, A.F_DONE_REASON)
 _PLAIN = {}
@@ -34,15 +32,10 @@ def configure(b, packed, options):
 def run(b):
     """STEPS device-tensor steps -> the stacked outputs and the final fields"""
     n = b.n
-    acts = torch.as_tensor(np.random.RandomState(4).randn(STEPS, n, A.NU) * 0.3, device=DEV)
-    out = (torch.zeros((STEPS, n, A.NOBS), dtype=torch.float64, device=DEV), torch.zeros((STEPS, n), dtype=torch.float64, device=DEV),
-           torch.zeros((STEPS, n), dtype=torch.uint8, device=DEV))
+    acts, *out = horizon_rows(STEPS, n, act=np.random.RandomState(4).randn(STEPS, n, A.NU) * 0.3)[:4]
     for t in range(STEPS):
         b.step(acts[t], 1, (out[0][t], out[1][t], out[2][t]))
-    b.sync()
-    res = {"rows%d" % k: out[k].cpu().numpy() for k in range(3)}
-    res.update(snapshot(b, FIELDS))
-    return res
+    return result(b, out, FIELDS)
 
 
 def walk(n, packed, options=()):
@@ -69,13 +62,13 @@ def plain(n, packed):
 
 @pytest.mark.parametrize("n,options", [(5, ((102, 0),)), (5, ((101, 1),)), (8, ((A.OPT_PIPELINE, 2),))], ids=["single-tier", "profiled", "pipeline-2"])
 def test_one_env_selects_equal_the_two_tier_form(n, options):
-    assert_bitwise(plain(n, 0), walk(n, 0, options), options)
+    assert_bits(plain(n, 0), walk(n, 0, options), options)
 
 
 @pytest.mark.parametrize("n,options", [(5, ((101, 1),)), (8, ((A.OPT_PIPELINE, 2),))], ids=["profiled", "pipeline-2"])
 def test_packed_selects_equal_the_plain_packed_form(n, options):
     """5 envs: the second slot group is partial"""
-    assert_bitwise(plain(n, 1), walk(n, 1, options), options)
+    assert_bits(plain(n, 1), walk(n, 1, options), options)
 
 
 def test_multi_clip_single_tier_equals_two_tier_and_profiling_stays_refused():
@@ -87,15 +80,15 @@ def test_multi_clip_single_tier_equals_two_tier_and_profiling_stays_refused():
         res.append(run(b))
         res[-1][A.F_CLIP] = b.get(A.F_CLIP)
         if not two_tier:              # option 101 on a multi-clip batch: refused before anything is launched, and the batch steps on afterwards
-            before = snapshot(b, FIELDS)
+            before = state_of(b, FIELDS)
             b.set_option(101, 1)
             with pytest.raises(A.DmenvError) as ei:
                 b.step(np.zeros((5, A.NU)))
             assert "-4" in str(ei.value)
-            assert_bitwise(before, snapshot(b, FIELDS), "refused step")
+            assert_bits(before, state_of(b, FIELDS), "refused step")
             b.set_option(101, 0)
             b.step(np.zeros((5, A.NU)))
             assert b.get(A.F_TIME).tobytes() != before[A.F_TIME].tobytes()
         b.close()
     assert res[0]["rows2"].any() and res[0][A.F_PUSH_STATE][:, 4].max() >= 1
-    assert_bitwise(res[0], res[1], "multi-clip single-tier")
+    assert_bits(res[0], res[1], "multi-clip single-tier")

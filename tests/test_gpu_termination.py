@@ -14,14 +14,14 @@ import pytest
 import torch
 
 from deepmimic_mujoco_amd import _abi as A
-from deepmimic_mujoco_amd import Batch, DPEnv, DPVecEnv, MlpPolicy
+from deepmimic_mujoco_amd import Batch, DPEnv, DPVecEnv
 from deepmimic_mujoco_amd import termination as T
 from tests import floor_numpy as FN
 from tests import helpers as H
 from tests import state_numpy as SN
+from tests.gpu_batch import DEV, fused_policy, horizon_rows, put_state, start, state_of, step_numpy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NEAR_CAP = 0.005
 SEED = 5
@@ -47,28 +47,6 @@ def states(n, seed):
     idx, q, v, _ws, _c = H.varied_states(n, seed=seed)
     q[0::8, 2] -= 0.10
     return idx, q, v
-
-
-def start(b, idx, q, v, steps0=None):
-    n = b.n
-    b.set(A.F_QACC_WARMSTART, np.zeros((n, 34))); b.set(A.F_TIME, np.zeros(n))
-    b.set_state(q, v, frame_idx=idx)
-    if steps0 is not None:
-        b.set(A.F_EPISODE_STEPS, steps0)
-
-
-def step(b, a, host=False):
-    """one step -> numpy (obs, rew, done)"""
-    if host:
-        o, r, d = b.step(np.ascontiguousarray(a), 1)
-        return o.copy(), r.copy(), d.copy()
-    o, r, d = b.step(torch.as_tensor(a, device=DEV), 1)
-    b.join(); b.sync()
-    return o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy()
-
-
-def state_of(b):
-    return {f: b.get(f) for f in (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE)}
 
 
 # ---- the query --------------------------------------------------------------------------------------------------------------------------
@@ -190,10 +168,10 @@ def test_one_step_against_the_twin_without_termination(form, autoreset):
     steps0 = (np.arange(n) % LIMIT).astype(np.int32)                 # a third of the envs reach the limit on this step
     off = make(n, autoreset=autoreset, **cfg)
     on = make(n, fall="deepmimic", limit=LIMIT, autoreset=autoreset, **cfg)
-    start(off.batch, idx, q, v); start(on.batch, idx, q, v, steps0)
+    start(off.batch, idx, q, v); start(on.batch, idx, q, v, steps0=steps0)
     ep0 = on.batch.get(A.F_EPISODE)
-    o0, r0, d0 = step(off.batch, a, host)
-    o1, r1, d1 = step(on.batch, a, host)
+    o0, r0, d0 = step_numpy(off.batch, a, host=host)
+    o1, r1, d1 = step_numpy(on.batch, a, host=host)
     s0, s1 = state_of(off.batch), state_of(on.batch)
     # the fall test on the state the step left (the off twin's, where the step did not end the episode itself)
     touch = FN.floor_masks(cm, s0[A.F_QPOS]) if dtype == 64 else off.batch.floor_contacts()
@@ -224,14 +202,10 @@ def test_one_step_against_the_twin_without_termination(form, autoreset):
         # parked kinematics of the old state are not used: one more step agrees with a twin that was SET to the state the batch is in
         twin = make(n, fall="deepmimic", limit=LIMIT, autoreset=autoreset, **cfg)
         tb = twin.batch
-        tb.set(A.F_QACC_WARMSTART, s1[A.F_QACC_WARMSTART]); tb.set(A.F_TIME, s1[A.F_TIME])
-        tb.set_state(s1[A.F_QPOS], s1[A.F_QVEL], frame_idx=s1[A.F_FRAME_IDX])
-        for f in (A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE):
-            tb.set(f, s1[f])
-        tb.set(A.F_EPISODE_STEPS, on.batch.get(A.F_EPISODE_STEPS))
+        put_state(tb, s1, on.batch.get(A.F_EPISODE_STEPS))
         a2 = rng.randn(n, 28) * 0.9 if cfg.get("action_mode") != "spd-target" else s1[A.F_QPOS][:, 7:] + 0.1 * rng.randn(n, 28)
-        o2, r2, d2 = step(on.batch, a2, host)
-        o3, r3, d3 = step(tb, a2, host)
+        o2, r2, d2 = step_numpy(on.batch, a2, host=host)
+        o3, r3, d3 = step_numpy(tb, a2, host=host)
         np.testing.assert_array_equal(o2, o3); np.testing.assert_array_equal(r2, r3); np.testing.assert_array_equal(d2, d3)
         s2, s3 = state_of(on.batch), state_of(tb)
         for f in s2:
@@ -245,21 +219,14 @@ def test_one_step_against_the_twin_without_termination(form, autoreset):
 def test_step_act_and_rollout_are_step_then_terminate_then_act(packed, pipeline):
     n, Tn = 48, 4
     idx, q, v = states(n, seed=9)
-    pol = MlpPolicy(device=DEV, seed=2); pol.seed(5)
-    W = pol.pack()
+    pol, W = fused_policy()
     a0 = np.random.RandomState(3).randn(n, 28) * 0.9
-
-    def bufs():
-        ac = torch.zeros((Tn + 1, n, 28), dtype=torch.float64, device=DEV); ac[0] = torch.as_tensor(a0, device=DEV)
-        return (ac, torch.zeros((Tn, n, 56), dtype=torch.float64, device=DEV), torch.zeros((Tn, n), dtype=torch.float64, device=DEV),
-                torch.zeros((Tn, n), dtype=torch.uint8, device=DEV), torch.zeros((Tn, n), dtype=torch.float32, device=DEV))
-
     results = []
     for how in ("reference", "step_act", "rollout"):
         env = make(n, fall="deepmimic", limit=3, autoreset="rsi", packed=packed, pipeline=pipeline, step_queue=8 if packed else 0)
         b = env.batch
         start(b, idx, q, v)
-        ac, ob, rew, dn, vp = bufs()
+        ac, ob, rew, dn, vp = horizon_rows(Tn, n, a0=a0)
         if how == "rollout":
             b.rollout(ac, (ob, rew, dn), 1, W, vp, True, pol._seed, 7)
         for t in range(Tn if how != "rollout" else 0):
@@ -290,7 +257,7 @@ def test_time_limit_from_a_standing_state(packed):
     a = np.zeros((n, 28))
     trace = []
     for t in range(1, 8):
-        _o, r, d = step(b, a)
+        _o, r, d = step_numpy(b, a)
         assert (r == 1.0).all()
         assert (d != 0).all() == (t in (3, 6)) and (d != 0).any() == (t in (3, 6))
         np.testing.assert_array_equal(b.get(A.F_DONE_REASON), np.full(n, T.DONE_TIME_LIMIT if t in (3, 6) else 0))
@@ -303,7 +270,7 @@ def test_time_limit_from_a_standing_state(packed):
     np.testing.assert_array_equal(b.get(A.F_EPISODE_STEPS), np.where(mask, 0, 2))
     b.set_option(A.OPT_MAX_EPISODE_STEPS, 1)
     for t in range(3):
-        _o, _r, d = step(b, a)
+        _o, _r, d = step_numpy(b, a)
         assert (d != 0).all() and (b.get(A.F_DONE_REASON) == T.DONE_TIME_LIMIT).all() and not b.get(A.F_EPISODE_STEPS).any()
     env.close()
 
@@ -435,7 +402,7 @@ def test_options_at_zero_change_nothing(packed):
             b.set_option(A.OPT_FALL_BODIES, DEEPMIMIC); b.set_option(A.OPT_MAX_EPISODE_STEPS, 5)
             b.set_option(A.OPT_FALL_BODIES, 0); b.set_option(A.OPT_MAX_EPISODE_STEPS, 0)
         start(b, idx, q, v)
-        rows = [step(b, acts[t]) for t in range(16)]
+        rows = [step_numpy(b, acts[t]) for t in range(16)]
         runs.append((rows, state_of(b), b.get(A.F_EPISODE_STEPS), b.get(A.F_DONE_REASON)))
         env.close()
     for (o0, r0, d0), (o1, r1, d1) in zip(runs[0][0], runs[1][0]):

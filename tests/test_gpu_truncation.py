@@ -20,14 +20,13 @@ from deepmimic_mujoco_amd.state_features import phase_of
 from tests import floor_numpy as FN
 from tests import helpers as H
 from tests.gae_numpy import gae_boot, random_segment
+from tests.gpu_batch import DEV, put_state, start, state_of, step_numpy, truncation_log
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 SEED = 5
 M = 3
 STEPS = 7
 RTOL, ATOL = 2e-5, 2e-4
-STATE = (A.F_QPOS, A.F_QVEL, A.F_QACC_WARMSTART, A.F_TIME, A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE)
 
 FORMS = {
     "one-env-6": dict(n=6),
@@ -52,51 +51,6 @@ def frames_start(n):
     return idx, mc.data_config[idx].copy(), mc.data_vel[idx].copy()
 
 
-def start(b, idx, q, v, steps0=None):
-    b.set(A.F_QACC_WARMSTART, np.zeros((b.n, 34))); b.set(A.F_TIME, np.zeros(b.n))
-    b.set_state(q, v, frame_idx=idx)
-    if steps0 is not None:
-        b.set(A.F_EPISODE_STEPS, steps0)
-
-
-def step(b, a, host=False):
-    if host:
-        o, r, d = b.step(np.ascontiguousarray(a), 1)
-        return o.copy(), r.copy(), d.copy()
-    o, r, d = b.step(torch.as_tensor(a, device=DEV), 1)
-    b.join(); b.sync()
-    return o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy()
-
-
-def state_of(b):
-    return {f: b.get(f) for f in STATE}
-
-
-def put_state(b, s, ep_steps):
-    """the batch into the state `s` (state_of of another batch)"""
-    b.set(A.F_QACC_WARMSTART, s[A.F_QACC_WARMSTART]); b.set(A.F_TIME, s[A.F_TIME])
-    b.set_state(s[A.F_QPOS], s[A.F_QVEL], frame_idx=s[A.F_FRAME_IDX])
-    for f in (A.F_FRAME_IDX, A.F_FRAME_INIT, A.F_CYCLE, A.F_EPISODE):
-        b.set(f, s[f])
-    b.set(A.F_EPISODE_STEPS, ep_steps)
-
-
-def read_log(b, host, clear=False, cap=None):
-    """-> (count, records sorted by (tick, env): index [k,4], qpos [k,35], qvel [k,34]) of the valid records"""
-    C = b.options[A.OPT_TRUNCATION_LOG] if cap is None else cap
-    if host:
-        out = (np.zeros(1, dtype=np.int32), np.zeros((C, 4), dtype=np.int32), np.zeros((C, 35)), np.zeros((C, 34)))
-        cnt, idx, qp, qv = b.truncations(clear=clear, out=out)
-    else:
-        cnt, idx, qp, qv = b.truncations(clear=clear, device=True)
-        assert cnt.is_cuda and idx.is_cuda and qp.dtype == torch.float64
-        b.sync()
-        cnt, idx, qp, qv = (x.cpu().numpy() for x in (cnt, idx, qp, qv))
-    k = min(int(cnt[0]), idx.shape[0])
-    order = np.lexsort((idx[:k, 0], idx[:k, 1]))
-    return int(cnt[0]), idx[:k][order], qp[:k][order], qv[:k][order]
-
-
 # ---- records against a twin; the log off against on --------------------------------------------------------------------------------------------
 CASES = [(f, ar, host, 64) for f in sorted(FORMS) for ar in (None, "rsi", "init") for host in (False, True)] + [(f, "rsi", False, 32) for f in sorted(FORMS)]
 
@@ -115,15 +69,15 @@ def test_records_against_a_twin_and_off_is_off(form, autoreset, host, dtype):
     compared = [0, 0]
     own_done = np.zeros(n, dtype=bool)
     for t in range(STEPS):
-        o1, r1, d1 = step(on.batch, acts[t], host)
-        o0, r0, d0 = step(off.batch, acts[t], host)
+        o1, r1, d1 = step_numpy(on.batch, acts[t], host=host)
+        o0, r0, d0 = step_numpy(off.batch, acts[t], host=host)
         for x, y in ((o1, o0), (r1, r0), (d1, d0)):
             np.testing.assert_array_equal(x, y)                                        # off is off: the log changes nothing a caller sees ...
         reason = on.batch.get(A.F_DONE_REASON)
         np.testing.assert_array_equal(reason, off.batch.get(A.F_DONE_REASON))
         np.testing.assert_array_equal(on.batch.get(A.F_EPISODE_STEPS), off.batch.get(A.F_EPISODE_STEPS))
         if t < 6:
-            _o, _r, dt = step(twin.batch, acts[t], host)
+            _o, _r, dt = step_numpy(twin.batch, acts[t], host=host)
             own_done |= dt != 0
         if t in (2, 5):
             # every env whose own done stayed 0 since the (re)start is truncated here, and its record is the twin's state
@@ -140,7 +94,7 @@ def test_records_against_a_twin_and_off_is_off(form, autoreset, host, dtype):
     s1, s0 = state_of(on.batch), state_of(off.batch)
     for f in s1:
         np.testing.assert_array_equal(s1[f], s0[f])                                    # ... and nothing in the batch's state
-    count, ridx, rq, rv = read_log(on.batch, host)
+    count, ridx, rq, rv = truncation_log(on.batch, host=host, device=not host)
     assert count == len(ridx) <= 3 * n
     got = {(int(r[1]), int(r[0])): k for k, r in enumerate(ridx)}
     assert len(got) == count                                                            # (tick, env) is a key
@@ -169,9 +123,9 @@ def test_no_record_for_a_step_done_or_a_fall_at_the_limit_step(packed):
     a = np.random.RandomState(1).randn(n, 28) * 0.9
     plain = make(n, packed=packed)
     on = make(n, limit=M, log=n, fall="deepmimic", autoreset="rsi", packed=packed)
-    start(plain.batch, idx, q, v); start(on.batch, idx, q, v, np.full(n, M - 1, dtype=np.int32))
-    _o, _r, d0 = step(plain.batch, a)
-    step(on.batch, a)
+    start(plain.batch, idx, q, v); start(on.batch, idx, q, v, steps0=np.full(n, M - 1, dtype=np.int32))
+    _o, _r, d0 = step_numpy(plain.batch, a)
+    step_numpy(on.batch, a)
     left = state_of(plain.batch)
     stepdone = d0 != 0
     gm = TM.geoms_of_bodies(TM.fall_body_mask("deepmimic"), cm.geom_bodyid)
@@ -180,7 +134,7 @@ def test_no_record_for_a_step_done_or_a_fall_at_the_limit_step(packed):
     assert stepdone.any() and fall.sum() >= max(1, n // 16) and trunc.sum() >= n // 8
     np.testing.assert_array_equal(on.batch.get(A.F_DONE_REASON),
                                   np.where(stepdone, TM.DONE_STEP, np.where(fall, TM.DONE_FALL | TM.DONE_TIME_LIMIT, TM.DONE_TIME_LIMIT)))
-    count, ridx, rq, rv = read_log(on.batch, host=True)
+    count, ridx, rq, rv = truncation_log(on.batch, host=True)
     np.testing.assert_array_equal(ridx[:, 0], np.nonzero(trunc)[0])                     # exactly the envs the limit alone ended
     assert count == trunc.sum() and not ridx[:, 1].any()
     np.testing.assert_array_equal(rq, left[A.F_QPOS][trunc]); np.testing.assert_array_equal(rv, left[A.F_QVEL][trunc])
@@ -195,9 +149,9 @@ def test_no_record_without_a_time_limit():
     q[0::8, 2] -= 0.10
     env = make(n, log=n, fall="deepmimic", autoreset="rsi")
     start(env.batch, idx, q, v)
-    step(env.batch, np.random.RandomState(1).randn(n, 28) * 0.9)
+    step_numpy(env.batch, np.random.RandomState(1).randn(n, 28) * 0.9)
     assert (env.batch.get(A.F_DONE_REASON) == TM.DONE_FALL).any()
-    assert read_log(env.batch, host=True)[0] == 0
+    assert truncation_log(env.batch, host=True)[0] == 0
     env.close()
 
 
@@ -208,7 +162,7 @@ def test_overflow_clear_and_resizing():
     b = env.batch
     b.reset(mode=2, hard=1)
     a = np.zeros((n, 28))
-    _o, _r, d = step(b, a)
+    _o, _r, d = step_numpy(b, a)
     assert (d != 0).all() and (b.get(A.F_DONE_REASON) == TM.DONE_TIME_LIMIT).all()
     guard = -7
     out = (np.full(1, guard, dtype=np.int32), np.full((6, 4), guard, dtype=np.int32), np.full((6, 35), float(guard)), np.full((6, 34), float(guard)))
@@ -222,23 +176,23 @@ def test_overflow_clear_and_resizing():
     assert int(cnt2[0]) == 6
     np.testing.assert_array_equal(idx2, idx[:2])
     # without a clear the tick goes on; with one, count and tick start again
-    step(b, a)
+    step_numpy(b, a)
     cnt, idx, _q, _v = b.truncations(clear=True, device=False)
     assert int(cnt[0]) == 12 and not idx[:4, 1].any()                                   # (the four stored records are still the first four)
     cnt, _i, _q, _v = b.truncations(clear=False, device=False)
     assert int(cnt[0]) == 0
-    step(b, a)
-    count, ridx, _q, _v = read_log(b, host=True)
+    step_numpy(b, a)
+    count, ridx, _q, _v = truncation_log(b, host=True)
     assert count == 6 and len(ridx) == 4 and not ridx[:, 1].any()                       # tick 0 again
     # device pointers: the same numbers, nothing waits
-    step(b, a)
-    count, ridx, _q, _v = read_log(b, host=False)
+    step_numpy(b, a)
+    count, ridx, _q, _v = truncation_log(b, device=True)
     assert count == 12 and len(ridx) == 4
     # resizing clears
     b.set_option(A.OPT_TRUNCATION_LOG, 8)
-    assert read_log(b, host=True)[0] == 0
-    step(b, a)
-    count, ridx, rq, _v = read_log(b, host=True)
+    assert truncation_log(b, host=True)[0] == 0
+    step_numpy(b, a)
+    count, ridx, rq, _v = truncation_log(b, host=True)
     assert count == 6 and sorted(ridx[:, 0]) == list(range(n)) and not ridx[:, 1].any()
     with pytest.raises(A.DmenvError):
         b.set_option(A.OPT_TRUNCATION_LOG, -1)
@@ -305,7 +259,7 @@ def test_collector_bootstrap_values(obs_mode, fused):
     seg = c.collect()
     vboot = seg["vboot"]
     assert vboot.is_cuda and vboot.dtype == torch.float32 and tuple(vboot.shape) == (T, n)
-    count, ridx, rq, rv = read_log(b, host=False)
+    count, ridx, rq, rv = truncation_log(b, device=True)
     assert seg.trunc_count() == count == len(ridx) and n <= count <= 2 * n               # most envs are truncated at rows 2 and 5
     # the record's observation, and the critic's value of it
     if obs_mode == "dp_env_v3":
@@ -340,7 +294,7 @@ def test_collector_bootstrap_values(obs_mode, fused):
     # a second segment: the log was cleared at its launch, ticks count from its first step
     c.launch()
     seg2 = c.collect()
-    count2, ridx2, _q, _v = read_log(b, host=False)
+    count2, ridx2, _q, _v = truncation_log(b, device=True)
     assert seg2.trunc_count() == count2 and ridx2[:, 1].max() < T and (seg2["vboot"] != 0).sum().item() == count2
     env.close(); env0.close()
 

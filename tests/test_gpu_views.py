@@ -32,7 +32,7 @@ def stepped_batch(dtype):
     return b
 
 
-def state_of(b):
+def kept_fields(b):
     return [b.get(f).copy() for f in (A.F_QPOS, A.F_QVEL, A.F_FRAME_IDX)]
 
 
@@ -57,8 +57,8 @@ def the_calls(b, device):
 @pytest.mark.parametrize("dtype", [64, 32])
 def test_host_and_device_callers_agree_through_one_staging_buffer(dtype):
     hb, db = stepped_batch(dtype), stepped_batch(dtype)
-    before = state_of(hb)
-    for x, y in zip(before, state_of(db)):
+    before = kept_fields(hb)
+    for x, y in zip(before, kept_fields(db)):
         np.testing.assert_array_equal(x, y)                               # twins
     host = the_calls(hb, False)
     dev = the_calls(db, True)
@@ -73,7 +73,7 @@ def test_host_and_device_callers_agree_through_one_staging_buffer(dtype):
     np.testing.assert_array_equal(res["floor_contacts of two ids"], res["floor_contacts of all"][[5, 0]])
     np.testing.assert_array_equal(res["state_features of one id"], hb.state_features()[[2]])
     for b in (hb, db):
-        for x, y in zip(before, state_of(b)):
+        for x, y in zip(before, kept_fields(b)):
             np.testing.assert_array_equal(x, y)                           # read-only
     hb.close(); db.close()
 
