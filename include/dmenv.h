@@ -262,6 +262,14 @@ enum {
 #define DM_PACKED_MAXCON 13
 #define DM_PACKED_MAXFRAME 8
 #define DM_PACKED_MAXCAND 32
+/* What dm_batch_redo_total counts an environment past one of them under — out[k], k in this order; tests/test_gpu_slot_capacities.py depends on it:
+ *   out[0]  every env-step re-stepped by the one-env code, whatever the reason (an env-step is counted here once, and once under each reason it met).
+ *   out[1]  candidates: more than DM_PACKED_MAXCAND geom pairs passed the bounding spheres in some evaluation of the step.
+ *   out[2]  box slots: a model with more box geoms than the packed narrow phase has staging slots for (never, for the humanoid's two feet).
+ *   out[3]  contacts: more than DM_PACKED_MAXCON contacts, or contacts from more than DM_PACKED_MAXFRAME geom pairs.
+ *   out[4]  rows: more than DM_PACKED_MAXROWS (per-step launches without the three-set code: DM_PACKED_MAXROWS_PER_STEP) constraint rows, or more than
+ *           DM_PACKED_MAXLIMROWS joint-limit rows.
+ *   out[5]  PGS test: a solver step the cost test would reject, which the packed loop does not replay. */
 #define DM_MAX_STEP_QUEUE 256
 #define DM_MAX_PIPELINE 8
 /* DM_OPT_CLIP_MODE: an option of dm_batch_set_option like those of the enum above (whose ids end at 12), for multi-clip batches (dm_mocap_create_set).

@@ -817,13 +817,14 @@ static void make_frame(dmo_real* f) {
 /* [MJ mj_collision]: walk the precompiled pair list; contact parameters by max / mix [MJ mj_contactParam] */
 static void collision(const dmo_model* m, dmo_data* d) {
   const dmo_spec* s = &m->s;
-  d->ncon = 0;
+  d->ncon = 0; d->nframe = 0;
   if (!m->enable_contact) return;
   for (int k = 0; k < m->npair; k++) {
     int g1 = m->pair_g1[k], g2 = m->pair_g2[k];
     dmo_real margin = fmax(s->geom_margin[g1], s->geom_margin[g2]);
     rawcon rc[8];
     int n = narrowphase(m, d, g1, g2, margin, rc);
+    if (n > 0) d->nframe++;
     for (int i = 0; i < n && d->ncon < DMO_MAXCON; i++) {
       dmo_contact* c = &d->contact[d->ncon++];
       c->geom1 = g1; c->geom2 = g2;
@@ -836,6 +837,8 @@ static void collision(const dmo_model* m, dmo_data* d) {
       c->friction[0] = f0; c->friction[1] = f0; c->friction[2] = f1; c->friction[3] = f2; c->friction[4] = f2;
     }
   }
+  if (d->ncon > d->ncon_peak) d->ncon_peak = d->ncon;
+  if (d->nframe > d->nframe_peak) d->nframe_peak = d->nframe;
 }
 
 /* ======================================= constraints ========================================== */
@@ -1057,7 +1060,7 @@ void dmo_step(const dmo_model* m, dmo_data* d) {
   int nq = m->nq, nv = m->nv;
   dmo_real h = m->s.timestep, t0 = d->time;
   dmo_real X[4][DMO_MAXQ + DMO_MAXV], F[4][DMO_MAXV], dX[2 * DMO_MAXV];
-  d->nefc_peak = 0; d->nlimit_peak = 0;
+  d->nefc_peak = 0; d->nlimit_peak = 0; d->ncon_peak = 0; d->nframe_peak = 0;
   dmo_forward(m, d);
   memcpy(X[0], d->qpos, nq * sizeof(dmo_real)); memcpy(X[0] + nq, d->qvel, nv * sizeof(dmo_real));
   memcpy(F[0], d->qacc, nv * sizeof(dmo_real));
@@ -1408,6 +1411,7 @@ int dmo_data_get(const dmo_model* m, const dmo_data* d, const char* field, dmo_r
   FIELD("qacc_smooth", d->qacc_smooth, nv) FIELD("qfrc_constraint", d->qfrc_constraint, nv) FIELD("qacc", d->qacc, nv)
   FIELD("ncon", &d->ncon, 1) FIELD("nefc", &d->nefc, 1) FIELD("nlimit", &d->nlimit, 1)
   FIELD("solver_iter", &d->solver_iter, 1) FIELD("nefc_peak", &d->nefc_peak, 1) FIELD("nlimit_peak", &d->nlimit_peak, 1) FIELD("solver_improvement", &d->solver_improvement, 1)
+  FIELD("nframe", &d->nframe, 1) FIELD("ncon_peak", &d->ncon_peak, 1) FIELD("nframe_peak", &d->nframe_peak, 1)
   FIELD("efc_pos", d->efc_pos, n) FIELD("efc_margin", d->efc_margin, n) FIELD("efc_R", d->efc_R, n)
   FIELD("efc_diagApprox", d->efc_diagApprox, n) FIELD("efc_vel", d->efc_vel, n) FIELD("efc_aref", d->efc_aref, n)
   FIELD("efc_b", d->efc_b, n) FIELD("efc_force", d->efc_force, n)

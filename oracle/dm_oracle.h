@@ -133,6 +133,7 @@ typedef struct {
   int solver_iter;
   dmo_real solver_improvement;
   int nefc_peak, nlimit_peak; /* diagnostics: the largest nefc / nlimit of the evaluations since dmo_step last began (its four RK stages), or since the fields were last set */
+  int nframe, ncon_peak, nframe_peak; /* nframe: geom pairs with at least one contact, last evaluation; the peaks as above (read-only) */
 } dmo_data;
 
 /* model */

@@ -30,6 +30,9 @@ def load_lib(directory, so_name):
     L.emu_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p]
     L.emu_redo_total.argtypes = [C.c_void_p]; L.emu_redo_total.restype = C.c_long
     L.emu_rollout.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, u8p, C.c_int, C.c_int]
+    if hasattr(L, "emu_redo_reasons"):            # libdmemu.so's own
+        L.emu_redo_reasons.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        L.emu_rollout_inputs.argtypes = [C.c_void_p, A._dp, A._dp, A._dp, u8p, C.c_int, C.c_int, A._dp]
     L.emu_debug_forward.argtypes = [C.c_void_p, C.c_int, A._dp]
     L.emu_dispatch.argtypes = [C.c_int, C.c_int, C.c_int, A._ip, A._ip, A._ip, C.c_int, A._ip, C.c_int, A._ip, A._ip]
     return L
@@ -87,14 +90,19 @@ class EmuBatch(object):
                        done.ctypes.data_as(C.POINTER(C.c_uint8)), n_substeps)
         return obs, rew, done
 
-    def rollout(self, actions, n_substeps=1):
-        """dm_batch_rollout on the packed path, open loop: actions [T, n, 28] -> (obs [T, n, 56], rew [T, n], done [T, n])"""
+    def rollout(self, actions, n_substeps=1, policy_inputs=False):
+        """dm_batch_rollout on the packed path, open loop: actions [T, n, 28] -> (obs [T, n, 56], rew [T, n], done [T, n]); policy_inputs: and what a policy
+        behind every step would read from the slots' LDS [T, n, 56]"""
         a = np.ascontiguousarray(actions, dtype=np.float64)
         T = a.shape[0]
         assert a.shape == (T, self.n, A.NU)
         obs = np.zeros((T, self.n, A.NOBS)); rew = np.zeros((T, self.n)); done = np.zeros((T, self.n), dtype=np.uint8)
-        lib().emu_rollout(self.h, a.ctypes.data_as(A._dp), obs.ctypes.data_as(A._dp), rew.ctypes.data_as(A._dp),
-                          done.ctypes.data_as(C.POINTER(C.c_uint8)), n_substeps, T)
+        args = (self.h, a.ctypes.data_as(A._dp), obs.ctypes.data_as(A._dp), rew.ctypes.data_as(A._dp), done.ctypes.data_as(C.POINTER(C.c_uint8)), n_substeps, T)
+        if policy_inputs:
+            pin = np.full((T, self.n, A.NOBS), np.nan)
+            lib().emu_rollout_inputs(*args, pin.ctypes.data_as(A._dp))
+            return obs, rew, done, pin
+        lib().emu_rollout(*args)
         return obs, rew, done
 
     def set_state(self, qpos, qvel, frame_idx=None, mask=None):
@@ -113,6 +121,12 @@ class EmuBatch(object):
     def redo_total(self):
         """envs the packed path handed to the one-env kernel so far (a capacity of slot_kernel.h exceeded)"""
         return int(lib().emu_redo_total(self.h))
+
+    def redo_reasons(self):
+        """Batch.redo_reasons: [total, candidates, box slots, contacts (or contact pairs), rows (or limit rows), PGS test]"""
+        v = (C.c_long * 6)()
+        lib().emu_redo_reasons(self.h, v)
+        return [int(x) for x in v]
 
     def get_obs(self, out=None):
         q = self.get(A.F_QPOS); v = self.get(A.F_QVEL)

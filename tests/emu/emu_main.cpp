@@ -72,6 +72,22 @@ void emu_rollout(void* h, const double* action, double* obs, double* reward, uns
   e->redo_total += horizon_launch<false>(*e, action, obs, reward, done, nsub, T, [](int, int) {});
 }
 long emu_redo_total(void* h) { return ((EmuBatch*)h)->redo_total; }
+// dm_batch_redo_total's six counters: the total, then the reasons the packed step tallies in B.redo_why[1 .. 5] (candidates, box slots, contacts, rows, PGS test)
+void emu_redo_reasons(void* h, long* out) {
+  EmuBatch* e = (EmuBatch*)h;
+  out[0] = e->redo_total;
+  for (int r = 1; r < 6; r++) out[r] = e->B.redo_why[r];
+}
+// emu_rollout, and what a policy behind every step would read: the slots' qpos[7 ..] and qvel[6 ..] at the place of the policy's step -> pin [T, n, 56]
+void emu_rollout_inputs(void* h, const double* action, double* obs, double* reward, unsigned char* done, int nsub, int T, double* pin) {
+  EmuBatch* e = (EmuBatch*)h;
+  const int n = e->B.n_envs;
+  e->redo_total += horizon_launch<false>(*e, action, obs, reward, done, nsub, T, [&](int first, int t) {
+    const int lane = dmw::lane(), slot = lane >> 4, sl = lane & 15, env = first + slot;
+    if (env >= n) return;
+    for (int o = sl; o < NOBS; o += SW) pin[((size_t)t * n + env) * NOBS + o] = o < 28 ? e->roll.sh[slot].qpos[7 + o] : e->roll.sh[slot].qvel[6 + (o - 28)];
+  });
+}
 // Self-ordering per-step launches (env_step.h order_ticket / dispatch_env) without the physics: `count` envs first .. first + count - 1 of a batch of n take
 // their tickets in the order `arrival` names them (n_arrival of them; keys from nefc / iter), then the waves of the next launch look their envs up — one env per wave
 // (out1[count]) and four per wave (out4[4 * ceil(count / 4)], spare slots repeat the last position).  with_tickets = 0: no tickets -> `order` / identity.
